@@ -2,6 +2,8 @@
 """bench.py -- cells/sec through pca + neighbors + leiden on MI355X (BASELINE.json metric).
 
     python bench.py --gpus 1 --steps 3 --warmup 1
+    python bench.py --gpus 1 --steps 3 --warmup 1 --full
+    python bench.py --gpus 1 --steps 3 --warmup 1 --dump-outputs DIR
     python -m torch.distributed.run --nnodes=1 --nproc-per-node N --master-addr 127.0.0.1 --master-port P \
         bench.py --gpus N --steps K --warmup W
 
@@ -10,6 +12,11 @@ Leiden res 1.0) over the synthetic planted-cluster log-normal CSR (1M cells x 2k
 configs[2], the 1x MI355X roofline configuration; the 1M cells are row-sharded over the N ranks for N > 1,
 i.e. strong scaling of configs[3]).  The CSR shard is resident in HBM before the timed region starts; the
 timed region ends with the labels on the device.  Rank 0 prints ONE JSON line.
+
+A plain run sets up, warms up, times `--steps` steps and prints the line: `value`, `ms_per_step`, `stage_ms_per_step`,
+`roofline` (from the counters of the timed steps themselves), `leiden` and `result`.  `--dump-outputs DIR` writes what
+the last timed step returned as DIR/<name>.npy (`dump_outputs`).  Everything that takes runs of its own -- the side
+measurements, the CPU baseline, the parity and property gates -- runs only under `--full` (rank 0 of a 1-GPU run):
 
 Extra objects in the line:
   roofline      knn_select_reg_kernel, 3 x bf16 engine (v_mfma_f32_32x32x16_bf16 on the hi / lo split of the float32
@@ -41,7 +48,7 @@ Extra objects in the line:
                 (`measured_at_full_size`, ~170 s on the GPU box's 256 cores), `extrapolated_seconds_at_full_size` what
                 the two small samples predicted (kNN fitted with the n^2 law, the other stages linearly; BASELINE.md
                 section 3); a box on which the full size does not fit `--cpu-budget-s` reports the fit and says so.
-  parity        (`--verify`, default at N=1) the GPU path against that CPU chain on the largest CPU sample, stage by
+  parity        (`--verify`, default at N=1 under `--full`) the GPU path against that CPU chain on the largest CPU sample, stage by
                 stage (every stage fed the CPU chain's previous output, so a gate isolates one stage) and end to end;
                 the process exits non-zero when a north_star gate breaks.
 """
@@ -63,6 +70,12 @@ def parse_args():
     ap.add_argument("--gpus", type=int, default=1)
     ap.add_argument("--steps", type=int, default=3)
     ap.add_argument("--warmup", type=int, default=1)
+    ap.add_argument("--full", action="store_true",
+                    help="also run what takes runs of its own (N=1): side measurements, structure variants, host-to-host, "
+                         "full-size properties, CPU baseline and parity; a plain run measures the timed steps only")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="write what the last timed step returned as DIR/<name>.npy (float32 / float64; a fixed row sample "
+                         "of the per-cell arrays)")
     ap.add_argument("--n-obs", type=int, default=1_000_000)
     ap.add_argument("--n-vars", type=int, default=2000)
     ap.add_argument("--n-comps", type=int, default=50)
@@ -91,6 +104,8 @@ def parse_args():
                          "probing this many cells; the line then reports the sampled recall instead of gating exactness, and the "
                          "CPU-chain parity (an exact chain) is skipped")
     a = ap.parse_args()
+    if a.steps < 1 or a.warmup < 0:
+        ap.error("--steps must be >= 1 and --warmup >= 0")
     if a.cpu_sample is not None:
         a.cpu_sizes = str(a.cpu_sample)
     a.cpu_sizes = [int(v) for v in a.cpu_sizes.split(",") if v.strip() and int(v) > 0]
@@ -768,6 +783,55 @@ def umap_layout(res, n: int, n_epochs: int = 200) -> dict:
             "frac_of_8TBps": bytes_total / (ms * 1e-3) / 1e9 / 8000.0, "finite": bool(torch.isfinite(y).all())}
 
 
+DUMP_SEED, DUMP_MAX_ROWS, DUMP_BUDGET_BYTES = 0, 32768, 48e6
+
+
+def dump_outputs(res, n: int, lo: int, out_dir) -> dict:
+    """`--dump-outputs DIR`: what the last timed step handed back (PathResult), as DIR/<name>.npy in float32 / float64, so
+    that two builds can be compared output for output on identical inputs.  Per-cell arrays are cut to a fixed row sample
+    (seed DUMP_SEED, the same for every run of the same size: `sample_rows`) so that the files stay far below 64 MB;
+    integer arrays are stored as float64 (exact).  `lo` = first global row of this rank's shard."""
+    import numpy as np
+    import torch
+
+    def host(t, ix=None):
+        if hasattr(t, "detach"):
+            t = t.detach()
+            a = (t if ix is None else t[torch.as_tensor(ix, dtype=torch.int64, device=t.device)]).cpu().numpy()
+        else:
+            a = np.asarray(t) if ix is None else np.asarray(t)[ix]
+        return a if a.dtype in (np.float32, np.float64) else a.astype(np.float64)
+
+    k = res.knn_indices.shape[1]
+    per_row = 4 * res.x_pca.shape[1] + 16 * k + 12 * 2 * k + 16  # scores, kNN lists, ~2k graph entries, label, row id
+    m = int(min(n, DUMP_MAX_ROWS, DUMP_BUDGET_BYTES // per_row))
+    rows = np.sort(np.random.default_rng(DUMP_SEED).choice(n, size=m, replace=False))
+    n_local = res.x_pca.shape[0]
+    loc = rows[(rows >= lo) & (rows < lo + n_local)] - lo
+    arrays = {"sample_rows": rows.astype(np.float64),
+              "components": host(res.components), "variance": host(res.variance), "variance_ratio": host(res.variance_ratio),
+              "x_pca_sample": host(res.x_pca, loc), "knn_indices_sample": host(res.knn_indices, loc),
+              "knn_distances_sample": host(res.knn_distances, loc),
+              "labels_sample": host(res.labels, rows),
+              "modularity": np.array([res.modularity], dtype=np.float64),
+              "n_communities": np.array([res.n_communities], dtype=np.float64)}
+    if res.conn_indptr is not None:  # the graph's rows of the sample: their lengths, column ids and weights
+        ip = res.conn_indptr.detach().cpu().numpy().astype(np.int64)
+        start, lens = ip[rows], ip[rows + 1] - ip[rows]
+        sel = np.repeat(start - (np.cumsum(lens) - lens), lens) + np.arange(int(lens.sum()))
+        arrays["conn_row_nnz_sample"] = lens.astype(np.float64)
+        arrays["conn_indices_sample"] = host(res.conn_indices, sel)
+        arrays["conn_data_sample"] = host(res.conn_data, sel)
+    total = sum(a.nbytes for a in arrays.values())
+    if total > 64e6:
+        raise SystemExit(f"--dump-outputs: {total / 1e6:.1f} MB of outputs, the limit is 64 MB")
+    out_dir = Path(out_dir)
+    out_dir.mkdir(parents=True, exist_ok=True)
+    for name, a in arrays.items():
+        np.save(out_dir / f"{name}.npy", np.ascontiguousarray(a))
+    return {"dir": str(out_dir), "arrays": sorted(arrays), "sample_rows": m, "bytes": int(total)}
+
+
 def main() -> None:
     args = parse_args()
     import torch
@@ -814,7 +878,8 @@ def main() -> None:
     torch.cuda.synchronize()
     t_h2d = time.perf_counter() - t_h2d
     nnz_local = x.nnz
-    side = world == 1  # the side measurements and the CPU legs need the host matrix: rank 0 of a single-GPU run only
+    # the side measurements and the CPU legs (`--full`) need the host matrix: rank 0 of a single-GPU run only
+    side = world == 1 and args.full
     if not side:
         del x
 
@@ -863,6 +928,7 @@ def main() -> None:
         per_rank = [{k_: float(v) for k_, v in zip(stage_names, row)} for row in allr.view(world, len(stage_names)).cpu().tolist()]
 
     if rank == 0:
+        dumped = dump_outputs(res, n, lo, args.dump_outputs) if args.dump_outputs else None
         sel = sum(select_ms) / max(len(select_ms), 1)
         n_query = hi - lo
         pairs = sum(select_pairs) / max(len(select_pairs), 1)  # (query, candidate) pairs the kernel evaluated
@@ -956,6 +1022,8 @@ def main() -> None:
             "setup_s": {"generate": t_gen, "h2d": t_h2d},
         }
         out["config"]["structure"] = args.structure
+        if dumped:
+            out["dump_outputs"] = dumped
         rc = 0
         if side:
             if not args.no_side:

@@ -15,6 +15,11 @@ Sources (all under /root/reference):
                                       -> hvg_golden.npz       (the Seurat / Cell Ranger outputs that
                                          tests/test_highly_variable_genes.py:367-422 compares against)
   * tests/test_scaling.py:13-72       -> scale_toy.npz        (X_original, X_scaled_*, X_centered_*, mask cases)
+  * data files the reader tests open, copied byte for byte (REFERENCE_DATA): the Cell Ranger / Visium files of
+    tests/_data/10x_data and tests/_data/visium_data, the zarr-v2 store tests/_data/10x-10k-subset.zarr, and the
+    zarr-v3 zip above cut into parts below the 1 MiB limit of a committed file (10x_pbmc68k_reduced.zarr.zip.part<i>)
+  * the line count of every reference file that include/scanpy_amd.h, INTEGRATION.md and DESIGN.md cite
+                                      -> reference_line_counts.json (tests/test_reference_citations_cpu.py)
 
 The reference cannot be imported here (needs Python >= 3.12), so the literal arrays are
 pulled out of the test modules with `ast`, and the zarr-v3 store is decoded by hand
@@ -109,6 +114,57 @@ def read_csr(z: zipfile.ZipFile, path: str) -> dict[str, np.ndarray]:
     )
 
 
+REFERENCE_DATA = [
+    "10x_data/1.2.0/filtered_gene_bc_matrices/hg19_chr21/genes.tsv",
+    "10x_data/1.2.0/filtered_gene_bc_matrices/hg19_chr21/barcodes.tsv",
+    "10x_data/1.2.0/filtered_gene_bc_matrices/hg19_chr21/matrix.mtx",
+    "10x_data/1.2.0/filtered_gene_bc_matrices_h5.h5",
+    "10x_data/1.2.0/multiple_genomes.h5",
+    "10x_data/3.0.0/filtered_feature_bc_matrix/matrix.mtx.gz",
+    "10x_data/3.0.0/filtered_feature_bc_matrix/features.tsv.gz",
+    "10x_data/3.0.0/filtered_feature_bc_matrix/barcodes.tsv.gz",
+    "10x_data/3.0.0/filtered_feature_bc_matrix.h5",
+    "visium_data/2.1.0/raw_probe_bc_matrix.h5",
+    "10x-10k-subset.zarr",
+]
+ZIP_PART_BYTES = 900_000
+
+
+def repack_lzma(npz: Path) -> None:
+    src = zipfile.ZipFile(npz)
+    members = [(i.filename, src.read(i.filename)) for i in src.infolist()]
+    src.close()
+    with zipfile.ZipFile(npz, "w", compression=zipfile.ZIP_LZMA) as z:
+        for name, raw in members:
+            z.writestr(name, raw)
+
+
+def copy_reference_data() -> None:
+    import shutil
+
+    for rel in REFERENCE_DATA:
+        src, dst = REF / "tests/_data" / rel, OUT / rel
+        dst.parent.mkdir(parents=True, exist_ok=True)
+        if src.is_dir():
+            shutil.copytree(src, dst, dirs_exist_ok=True)
+        else:
+            shutil.copyfile(src, dst)
+    raw = (REF / "src/scanpy/datasets/10x_pbmc68k_reduced.zarr.zip").read_bytes()
+    for i in range(0, len(raw), ZIP_PART_BYTES):
+        (OUT / f"10x_pbmc68k_reduced.zarr.zip.part{i // ZIP_PART_BYTES}").write_bytes(raw[i:i + ZIP_PART_BYTES])
+
+
+def citation_line_counts() -> None:
+    import re
+
+    root = OUT.parent.parent
+    cite = re.compile(r"(?<![\w/.])((?:src/scanpy|tests)/[\w/]+\.py):(\d+)(?:-(\d+))?")  # as the test's CITE
+    paths = sorted({m[0] for doc in ("include/scanpy_amd.h", "INTEGRATION.md", "DESIGN.md")
+                    for m in cite.findall((root / doc).read_text())})
+    counts = {p: len((REF / p).read_text().splitlines()) for p in paths if (REF / p).is_file()}
+    (OUT / "reference_line_counts.json").write_text(json.dumps(counts, indent=1, sort_keys=True) + "\n")
+
+
 def main() -> None:
     if not REF.exists():
         raise SystemExit("/root/reference not present: fixtures can only be regenerated in the build container")
@@ -143,6 +199,7 @@ def main() -> None:
     fx["n_neighbors"] = read_zarr_array(z, "uns/neighbors/params/n_neighbors")
     fx["obs_n_counts"] = read_zarr_array(z, "obs/n_counts")
     np.savez_compressed(OUT / "pbmc68k_reduced.npz", **fx)
+    repack_lzma(OUT / "pbmc68k_reduced.npz")  # deflate leaves it above 1 MiB; np.load reads LZMA members too
 
     import pandas as pd
 
@@ -168,6 +225,9 @@ def main() -> None:
     np.savez_compressed(OUT / "loess_seurat_v3.npz", mean=vst["mean"].to_numpy(), variance=vst["variance"].to_numpy(),
                         variance_expected=vst["variance.expected"].to_numpy(),
                         variance_standardized=vst["variance.standardized"].to_numpy())
+
+    copy_reference_data()
+    citation_line_counts()
 
     for f in ("pca_toy.npz", "neighbors_toy.npz", "pbmc68k_reduced.npz", "hvg_golden.npz", "scale_toy.npz"):
         print(f, (OUT / f).stat().st_size, "bytes")

@@ -1,9 +1,10 @@
 """The HDF5 reader (scanpy_amd/_hdf5.py) and the readers on top of it (`read_h5ad`, `read_10x_h5`).
 
 Pinned against files written by the HDF5 library: (1) committed fixtures that h5py wrote (tests/golden/make_h5_golden.py:
-an AnnData-layout file, container variants old and new, a 10x v3 layout) with the arrays that went in; (2) when the
-reference checkout is on this machine, its own Cell Ranger / PyTables files against the Matrix Market exports next to
-them -- the comparison the reference makes in tests/test_read_10x.py:38-95."""
+an AnnData-layout file, container variants old and new, a 10x v3 layout) with the arrays that went in; (2) the reference's
+own Cell Ranger / PyTables files (copied to tests/golden/10x_data and tests/golden/visium_data by
+tests/golden/make_golden.py) against the Matrix Market exports next to them -- the comparison the reference makes in
+tests/test_read_10x.py:38-95."""
 from __future__ import annotations
 
 import gzip
@@ -20,9 +21,8 @@ from scanpy_amd import _hdf5 as h5
 from scanpy_amd._backed import BackedCsr
 
 H5 = Path(__file__).parent / "golden" / "h5"
-REF_10X = Path("/root/reference/tests/_data/10x_data")
-REF_VISIUM = Path("/root/reference/tests/_data/visium_data")
-needs_reference = pytest.mark.skipif(not REF_10X.is_dir(), reason="the reference checkout is not on this machine")
+REF_10X = Path(__file__).parent / "golden" / "10x_data"
+REF_VISIUM = Path(__file__).parent / "golden" / "visium_data"
 
 
 @pytest.fixture(scope="module")
@@ -216,7 +216,6 @@ def _read_mtx_dir(d: Path):
     return m, barcodes, genes
 
 
-@needs_reference
 @pytest.mark.parametrize(("mtx_rel", "h5_rel"), [
     ("1.2.0/filtered_gene_bc_matrices/hg19_chr21", "1.2.0/filtered_gene_bc_matrices_h5.h5"),
     ("3.0.0/filtered_feature_bc_matrix", "3.0.0/filtered_feature_bc_matrix.h5"),
@@ -233,7 +232,6 @@ def test_read_10x_h5_equals_the_matrix_market_export(mtx_rel, h5_rel):
         assert list(a.var["feature_types"]) == list(genes[2]) and "genome" in a.var.columns
 
 
-@needs_reference
 def test_read_10x_h5_legacy_genomes_and_probe_matrices():
     """tests/test_read_10x.py:98-131 (multiple genomes), :194-225 (probe-barcode matrices)"""
     multi = REF_10X / "1.2.0" / "multiple_genomes.h5"
@@ -336,7 +334,6 @@ def test_read_10x_mtx_layouts(tmp_path):
         sc.read_10x_mtx(tmp_path / "v2", var_names="nope")
 
 
-@needs_reference
 @pytest.mark.parametrize(("mtx_rel", "h5_rel"), [
     ("1.2.0/filtered_gene_bc_matrices/hg19_chr21", "1.2.0/filtered_gene_bc_matrices_h5.h5"),
     ("3.0.0/filtered_feature_bc_matrix", "3.0.0/filtered_feature_bc_matrix.h5"),

@@ -1,9 +1,9 @@
 """Zarr format 2 stores and Blosc frames (scanpy_amd/_zarr2.py).
 
 Pins: (1) the reference's own v2 test store `tests/_data/10x-10k-subset.zarr` (Blosc-LZ4 + byte shuffle, split and
-unsplit blocks, record arrays), read in place when the checkout is on this machine: the decoded matrix must be what a
+unsplit blocks, record arrays), committed as tests/golden/10x-10k-subset.zarr: the decoded matrix must be what a
 count matrix is -- non-negative integers, ~7 % non-zero -- and the names must be barcodes and mouse genes; one 14 KB
-chunk of it (`var/0`, real c-blosc output) is committed as tests/golden/zarr2/var_chunk.blosc; (2) stores and Blosc
+chunk of it (`var/0`, real c-blosc output) is also committed as tests/golden/zarr2/var_chunk.blosc; (2) stores and Blosc
 frames built by this file's own encoder (LZ4 through liblz4), covering every branch of the frame decoder."""
 from __future__ import annotations
 
@@ -20,7 +20,7 @@ import scanpy_amd as sc
 from scanpy_amd import _zarr2 as z2
 from scanpy_amd import _zarr3 as z3
 
-REF = Path("/root/reference/tests/_data/10x-10k-subset.zarr")
+REF = Path(__file__).parent / "golden" / "10x-10k-subset.zarr"
 GOLD = Path(__file__).parent / "golden" / "zarr2"
 
 
@@ -40,7 +40,6 @@ def test_real_cblosc_chunk_of_record_strings():
         z2.blosc_decompress_into(frame, np.empty(10, dtype=np.uint8))
 
 
-@pytest.mark.skipif(not REF.is_dir(), reason="the reference checkout is not on this machine")
 def test_reads_the_reference_v2_store():
     a = sc.read_zarr(REF)
     assert a.shape == (10000, 1000) and a.X.dtype == np.float32

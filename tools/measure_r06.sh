@@ -40,10 +40,10 @@ for STEP in "$@"; do
     build) python -c "import __graft_entry__ as g; g.build()" > "$OUT/build.log" 2>&1; echo "build rc=$?";;
     oracle_iters)  # background: single-threaded CPU job beside the GPU steps
       ( timeout -k 5 1500 python tools/oracle_iters_probe.py 1000000 "${ARG:-weak}" ${ORACLE_SEEDS:-0} ${GPU_SEEDS:-0} > "$OUT/oracle_iters_${ARG:-weak}.log" 2>&1 < /dev/null ) & ;;
-    bench_short) timeout -k 5 600 python bench.py --steps 20 --warmup 5 --cpu-sizes 0 --no-noise-variant --no-side --no-verify > "$OUT/bench_short.json" 2> "$OUT/bench_short.err" < /dev/null; echo "bench_short rc=$?"; line "$OUT/bench_short.json";;
-    bench_full) timeout -k 5 1500 python bench.py --steps 20 --warmup 5 ${ARG_FULL:-} > "$OUT/bench.json" 2> "$OUT/bench.err" < /dev/null; echo "bench rc=$?"; tail -2 "$OUT/bench.err" | cut -c1-300; line "$OUT/bench.json";;
-    bench_weak|bench_none) ST="${NAME#bench_}"; timeout -k 5 600 python bench.py --structure $ST --steps 5 --warmup 1 --cpu-sizes 0 --no-noise-variant --h2h-reps 0 --no-side > "$OUT/bench_$ST.json" 2> "$OUT/bench_$ST.err" < /dev/null; echo "bench $ST rc=$?"; line "$OUT/bench_$ST.json";;
-    bench_default) ( time timeout -k 5 900 python bench.py > "$OUT/bench_default.json" 2> "$OUT/bench_default.err" < /dev/null ) 2> "$OUT/bench_default.time"; echo "bench default rc=$? $(grep real "$OUT/bench_default.time")"; line "$OUT/bench_default.json";;
+    bench_short) timeout -k 5 600 python bench.py --full --steps 20 --warmup 5 --cpu-sizes 0 --no-noise-variant --no-side --no-verify > "$OUT/bench_short.json" 2> "$OUT/bench_short.err" < /dev/null; echo "bench_short rc=$?"; line "$OUT/bench_short.json";;
+    bench_full) timeout -k 5 1500 python bench.py --full --steps 20 --warmup 5 ${ARG_FULL:-} > "$OUT/bench.json" 2> "$OUT/bench.err" < /dev/null; echo "bench rc=$?"; tail -2 "$OUT/bench.err" | cut -c1-300; line "$OUT/bench.json";;
+    bench_weak|bench_none) ST="${NAME#bench_}"; timeout -k 5 600 python bench.py --full --structure $ST --steps 5 --warmup 1 --cpu-sizes 0 --no-noise-variant --h2h-reps 0 --no-side > "$OUT/bench_$ST.json" 2> "$OUT/bench_$ST.err" < /dev/null; echo "bench $ST rc=$?"; line "$OUT/bench_$ST.json";;
+    bench_default) ( time timeout -k 5 900 python bench.py --full > "$OUT/bench_default.json" 2> "$OUT/bench_default.err" < /dev/null ) 2> "$OUT/bench_default.time"; echo "bench default rc=$? $(grep real "$OUT/bench_default.time")"; line "$OUT/bench_default.json";;
     prof|prof_weak|prof_none) ST=planted; [ "$NAME" != prof ] && ST="${NAME#prof_}"
       ( cd /tmp; timeout -k 5 500 rocprofv3 --kernel-trace --stats --output-format csv -d /tmp/prof_${TAG}_$ST -o bench -- python "$R/bench.py" --structure $ST --steps 3 --warmup 1 --cpu-sizes 0 --no-noise-variant --h2h-reps 0 --no-side --no-verify --no-properties > "$OUT/bench_prof_$ST.log" 2>&1 < /dev/null; echo "prof $ST rc=$?" )
       find /tmp/prof_${TAG}_$ST -name '*kernel_stats.csv' -exec cp {} "$OUT/bench_${ST}_kernel_stats.csv" \;
