@@ -71,8 +71,8 @@ class _PinnedTransfer:
     Staging buffers, events and the copy stream are kept PER DEVICE (a stream belongs to one device: a singleton created
     for the first device would record its events on the wrong stream for the second); one transfer at a time (lock)."""
 
-    PIECE = int(os.environ.get("SCAMD_UPLOAD_PIECE_MB", "32")) << 20
-    THREADS = int(os.environ.get("SCAMD_UPLOAD_THREADS", "8"))
+    PIECE = 32 << 20
+    THREADS = 8
 
     def __init__(self) -> None:
         import threading
@@ -112,7 +112,7 @@ class _PinnedTransfer:
         src = torch.from_numpy(arr)
         nbytes = arr.nbytes
         # (small arrays, and arrays that already live in page-locked memory: direct DMA)
-        if nbytes < (8 << 20) or os.environ.get("SCAMD_PINNED_UPLOAD") == "0" or src.is_pinned():
+        if nbytes < (8 << 20) or src.is_pinned():
             return src.to(device)
         with self._lock:
             stages, events, stream = self._state(device)
@@ -145,7 +145,7 @@ class _PinnedTransfer:
         src = torch.from_numpy(arr)
         nbytes = arr.nbytes
         assert out.is_contiguous() and out.numel() * out.element_size() == nbytes
-        if nbytes < (8 << 20) or os.environ.get("SCAMD_PINNED_UPLOAD") == "0" or src.is_pinned():
+        if nbytes < (8 << 20) or src.is_pinned():
             out.copy_(src.view(out.dtype) if src.dtype != out.dtype else src, non_blocking=False)
             return
         with self._lock:
@@ -217,10 +217,9 @@ def to_host(t: torch.Tensor):
     * larger ones (10M cells: gigabytes) go through the staging pipeline of `_PinnedTransfer.download` into ordinary
       pageable memory: nothing stays page-locked beyond the two staging buffers (the pipeline costs ~4 ms per
       320 MB against the direct route -- first-touch page faults of the fresh array -- measured in bench.py's host-to-host
-      leg: 116.8 vs 112.5 ms).
-    SCAMD_PINNED_DOWNLOAD=0: plain `.cpu()`."""
+      leg: 116.8 vs 112.5 ms)."""
     nbytes = t.numel() * t.element_size()
-    if not t.is_cuda or nbytes < (8 << 20) or os.environ.get("SCAMD_PINNED_DOWNLOAD") == "0":
+    if not t.is_cuda or nbytes < (8 << 20):
         return t.cpu().numpy()
     if nbytes <= _PINNED_RESULT_MAX:
         t = t.contiguous()

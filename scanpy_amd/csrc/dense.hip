@@ -559,12 +559,7 @@ static int dense_block_size(int64_t g, int k) {
   // iteration (Jacobi b^3, Cholesky b^3) dominate the solve; measured at 1M x 2k, k = 50: b = 128 / 112 / 96 -> fit
   // 15.96 / 14.85 / 13.76 ms on the planted matrix (same 11 GEMMs, residual 2e-11 .. 4e-11, loadings equal to 1e-10)
   // and 40.8 / 37.8 / 34.9 ms on the structure-less one (8 / 9 / 10 outer iterations, each cheaper).
-  int b = (k + 32 + 15) / 16 * 16;
-  if (const char* e = getenv("SCAMD_DENSE_BLOCK")) {  // experiments: block size of the subspace iteration (>= k + 32)
-    const int v = atoi(e);
-    if (v >= k + 32 && v % 16 == 0) b = v;
-  }
-  b = std::min<int>(b, DB_MAX);
+  const int b = std::min<int>((k + 32 + 15) / 16 * 16, DB_MAX);
   return (int)std::min<int64_t>(b, g);
 }
 
@@ -575,10 +570,6 @@ struct DenseCtx {
   int g, b;
   DenseBuffers d;
   int n_gemm = 0, n_chol_retry = 0;
-  bool shift_first = [] {  // (A/B knob: SCAMD_DENSE_SHIFT_FIRST=0)
-    const char* e = getenv("SCAMD_DENSE_SHIFT_FIRST");
-    return !(e && e[0] == '0');
-  }();
 };
 
 static constexpr size_t CHOL_LDS = (size_t)(DB_MAX * DB_LD + DB_MAX) * sizeof(double);
@@ -600,7 +591,7 @@ static int cholqr2(DenseCtx& cx, double* zin, double* tmp, double* zout, bool fi
   while (plain_ok < plain_rounds) {
     int rc = dgemm_tn(cx.s, cur, b, cur, b, b, b, g, 1.0, nullptr, 0, 0.0, nullptr, 0, 0.0, cx.d.gm, b);
     if (rc != SCAMD_OK) return rc;
-    double shift = (filtered && plain_ok == 0 && shifted_rounds == 0 && cx.shift_first) ? s0 : 0.0;
+    double shift = (filtered && plain_ok == 0 && shifted_rounds == 0) ? s0 : 0.0;
     for (int attempt = shift > 0.0 ? 1 : 0;; ++attempt) {
       int bad = 0;
       hipLaunchKernelGGL(chol_factor_kernel, dim3(1), dim3(1024), CHOL_LDS, cx.s, cx.d.gm, b, shift, cx.d.s, cx.d.flags);
@@ -717,12 +708,8 @@ static int dense_topk(DenseCtx& cx, int k, unsigned int seed, double tol, int* n
   cx.n_gemm += 2;
   // (ONE plain round here: the block has been through two power steps, kappa ~ (lambda_1 / lambda_b)^2, and serves for the
   // Rayleigh quotients that bound the first filter and as that filter's start -- orthonormal to ~kappa^2 u is enough for both;
-  // the block is orthonormalised properly after the filter.  SCAMD_DENSE_FIRST_QR_ROUNDS=2: as until round 6)
-  static const int first_rounds = [] {
-    const char* e = getenv("SCAMD_DENSE_FIRST_QR_ROUNDS");
-    return (e && e[0] == '2') ? 2 : 1;
-  }();
-  rc = cholqr2(cx, z, tmp, v, false, first_rounds);
+  // the block is orthonormalised properly after the filter; two rounds, as until round 6: pca_fit 9.41 against 9.20 ms, same residual)
+  rc = cholqr2(cx, z, tmp, v, false, 1);
   if (rc != SCAMD_OK) return rc;
   // First filter straight on this basis, bounds from its Rayleigh quotients: a Rayleigh-Ritz here would only re-mix
   // the block (the filter does not care) at the price of one more 128 x 128 eigenproblem, the most expensive kernel of
@@ -738,12 +725,8 @@ static int dense_topk(DenseCtx& cx, int k, unsigned int seed, double tol, int* n
   if (h_rq[2] > h_rq[1] && h_rq[1] > 0.0) {
     // degree of the first filter: 7 (8 until round 6).  On the bench's matrix 8 / 7 / 6 / 5 leave the residual at 4.5e-11 / 4.6e-10 /
     // 4.8e-9 / 5e-8 against the tolerance 2e-8: 8 buys nothing but a block so ill-conditioned that CholeskyQR needs a second
-    // shifted round (pca_fit 9.76 / 9.45 / 9.35 ms; 5: a second outer iteration).  SCAMD_DENSE_FIRST_DEGREE: A/B.
-    static const int first_degree = [] {
-      const char* e = getenv("SCAMD_DENSE_FIRST_DEGREE");
-      return e ? std::max(2, std::min(16, atoi(e))) : 7;
-    }();
-    rc = filter(v, av, h_rq[1], h_rq[2], first_degree);
+    // shifted round (pca_fit 9.76 / 9.45 / 9.35 ms; 5: a second outer iteration)
+    rc = filter(v, av, h_rq[1], h_rq[2], 7);
     if (rc != SCAMD_OK) return rc;
     rc = cholqr2(cx, z, tmp, y0, true);
     if (rc != SCAMD_OK) return rc;

@@ -16,7 +16,7 @@
 //   * round 6 (g <= 8192): the matrix is first rewritten as per-tile record slabs, one 128-byte line per (row, tile),
 //     the rows of every block of 1024 ranked by their entry count per tile; four lanes work on one row, sixteen rows
 //     per wave step (gram_pack_kernel, gram_rank_kernel, gram_quad_kernel below: 3.7 + 0.8 ms at 1M x 2k);
-//   * wider matrices (and SCAMD_GRAM_LEGACY=1) take the round-2 kernel: a per-row tile pointer table (uint16) gives
+//   * wider matrices take the round-2 kernel: a per-row tile pointer table (uint16) gives
 //     each item the entries of a row that fall into gene tiles a and b without searching; 8 lanes work on one row
 //     (lane = entry of tile b, loop over the entries of tile a), 8 rows per wave step (gram_tile_kernel: 6.7 ms).
 // Work: sum_i r_i^2 products (r_i = stored entries of row i) -- 5e9 at 1M x 2k, 5 % dense.
@@ -84,8 +84,8 @@ __global__ __launch_bounds__(256) void gram_tileptr_kernel(const int64_t* __rest
 // SIXTEEN entries per row and tile instead of eight (10.3 -> 9.0 ms), column sums from the prefetched registers.  What
 // is left is instruction issue: ~45 % of the lanes of a product instruction carry a product (8 lanes per row against
 // 6.4 entries per tile, the a-loop runs to the longest of 8 rows).
-// A_FROM_MEM: every lane reads the tile-a entry of its row group straight from memory (one address per 8 lanes, L1
-// hits) instead of receiving it by a broadcast: slower (17.5 ms), kept behind SCAMD_GRAM_A_FROM_MEM for measurements.
+// Measured: every lane reading the tile-a entry of its row group straight from memory (one address per 8 lanes, L1
+// hits) instead of receiving it by a broadcast is slower (17.5 ms).
 // Broadcast lane PP of every aligned group of 8 lanes to the whole group.  Tried: ds_bpermute (two LDS instructions with
 // a lane-address register), DPP (quad broadcast + bank-masked row shift: three VALU with the copy the tied operand
 // needs) and ds_swizzle (one instruction): 7.0 ms with DPP, 6.9 with the swizzle once the kernel was issue-bound.
@@ -109,7 +109,7 @@ __device__ __forceinline__ long long fixed_round(double x) {
 // branch -- which returns at once unless the flag is up, after a kernel that clears the (then meaningless) sums.  The
 // branchy form cost the common case dearly: the compiler does not jump over the llrint side, its six float64
 // instructions issue with an empty exec mask behind EVERY product, plus four scalar instructions of mask bookkeeping.
-template <bool A_FROM_MEM, bool FAST>
+template <bool FAST>
 __global__ __launch_bounds__(GRAM_THREADS) void gram_tile_kernel(
     const int64_t* __restrict__ indptr, const int32_t* __restrict__ indices, const float* __restrict__ data,
     int64_t n, int ntile, const unsigned short* __restrict__ ptr, int rows_per_chunk, double scale,
@@ -260,35 +260,24 @@ __global__ __launch_bounds__(GRAM_THREADS) void gram_tile_kernel(
           if constexpr (FAST) amax = fmaxf(amax, fabsf(va_l));
           if (diag && qc == 0 && pc + q < na)  // column sums ride along on the diagonal items
             atomicAdd(&csum[ja_l], (unsigned long long)llrint((double)va_l * scale));
-          if constexpr (!A_FROM_MEM) {
-            // the 16 permutes of a group of eight tile-a entries are issued back to back and waited for once, the eight
-            // (predicated) atomics follow without a wait in between; the float64 -> int64 rounding is the 2^52 trick
-            // (exact for |x| < 2^51, llrint otherwise)
-            int ja8[8];
-            float va8[8];
-            const int vai = __float_as_int(va_l);
-            ja8[0] = bcast8<0>(ja_l); va8[0] = __int_as_float(bcast8<0>(vai));
-            ja8[1] = bcast8<1>(ja_l); va8[1] = __int_as_float(bcast8<1>(vai));
-            ja8[2] = bcast8<2>(ja_l); va8[2] = __int_as_float(bcast8<2>(vai));
-            ja8[3] = bcast8<3>(ja_l); va8[3] = __int_as_float(bcast8<3>(vai));
-            ja8[4] = bcast8<4>(ja_l); va8[4] = __int_as_float(bcast8<4>(vai));
-            ja8[5] = bcast8<5>(ja_l); va8[5] = __int_as_float(bcast8<5>(vai));
-            ja8[6] = bcast8<6>(ja_l); va8[6] = __int_as_float(bcast8<6>(vai));
-            ja8[7] = bcast8<7>(ja_l); va8[7] = __int_as_float(bcast8<7>(vai));
+          // the 16 permutes of a group of eight tile-a entries are issued back to back and waited for once, the eight
+          // (predicated) atomics follow without a wait in between; the float64 -> int64 rounding is the 2^52 trick
+          // (exact for |x| < 2^51, llrint otherwise)
+          int ja8[8];
+          float va8[8];
+          const int vai = __float_as_int(va_l);
+          ja8[0] = bcast8<0>(ja_l); va8[0] = __int_as_float(bcast8<0>(vai));
+          ja8[1] = bcast8<1>(ja_l); va8[1] = __int_as_float(bcast8<1>(vai));
+          ja8[2] = bcast8<2>(ja_l); va8[2] = __int_as_float(bcast8<2>(vai));
+          ja8[3] = bcast8<3>(ja_l); va8[3] = __int_as_float(bcast8<3>(vai));
+          ja8[4] = bcast8<4>(ja_l); va8[4] = __int_as_float(bcast8<4>(vai));
+          ja8[5] = bcast8<5>(ja_l); va8[5] = __int_as_float(bcast8<5>(vai));
+          ja8[6] = bcast8<6>(ja_l); va8[6] = __int_as_float(bcast8<6>(vai));
+          ja8[7] = bcast8<7>(ja_l); va8[7] = __int_as_float(bcast8<7>(vai));
 #pragma unroll
-            for (int pp = 0; pp < 8; ++pp) {
-              if (has_b && pc + pp < na)
-                atomicAdd(&tile[ja8[pp] * GT + jb], round_product((double)va8[pp] * vb));
-            }
-          } else {
-            const int cnt = min(8, max_na - pc);
-            for (int pp = 0; pp < cnt; ++pp) {
-              if (has_b && pc + pp < na) {
-                const int ja = indices[pa + pc + pp] - a0;
-                const float va = data[pa + pc + pp];
-                atomicAdd(&tile[ja * GT + jb], round_product((double)va * vb));
-              }
-            }
+          for (int pp = 0; pp < 8; ++pp) {
+            if (has_b && pc + pp < na)
+              atomicAdd(&tile[ja8[pp] * GT + jb], round_product((double)va8[pp] * vb));
           }
         }
       }
@@ -769,12 +758,8 @@ struct GramCarve {
   bool packed = false;
 };
 static bool gram_use_packed(int64_t n, int64_t ntile) {
-  static const bool legacy = [] {
-    const char* e = getenv("SCAMD_GRAM_LEGACY");
-    return e && e[0] == '1';
-  }();
   const int64_t n_pad = (n + RB - 1) / RB * RB;
-  return !legacy && ntile <= PACK_MAX_TILES && n_pad * REC * 8 < ((int64_t)1 << 32);
+  return ntile <= PACK_MAX_TILES && n_pad * REC * 8 < ((int64_t)1 << 32);
 }
 static GramCarve gram_carve(Workspace& ws, int64_t n, int64_t ntile) {
   GramCarve c;
@@ -792,7 +777,7 @@ static GramCarve gram_carve(Workspace& ws, int64_t n, int64_t ntile) {
 }
 // The packed kernels are built around <= 8 entries per (row, tile) with a tail up to 16: measured at 200k x 2k, 6.4 / 10.2 /
 // 15.4 / 25.6 entries per tile (5 / 8 / 12 / 20 % dense): 1.33 / 4.13 / 12.0 / 33.7 ms against 2.47 / 3.57 / 6.49 / 14.1 ms of
-// the round-2 kernel (tools/gram_density_probe.py) -- denser matrices keep the round-2 kernel (its uint16 tile pointers fit
+// the round-2 kernel -- denser matrices keep the round-2 kernel (its uint16 tile pointers fit
 // the records' space).
 static bool gram_sparse_enough(int64_t n, int64_t ntile, int64_t nnz) { return (double)nnz <= 8.0 * (double)n * (double)ntile; }
 
@@ -874,7 +859,6 @@ extern "C" int scamd_csr_gram_f32(const int64_t* indptr, const int32_t* indices,
     // take 4.86 / 4.44 / 4.36 / 4.20-4.26 / 4.24 / 4.56 / 5.30 ms for the entry -- shorter items even out the XCD queues' tails,
     // until the 128 KB flush per item shows)
     int n_chunks = pick_chunks(std::max(1, (nblk + 3) / 4), 24);
-    if (const char* e = getenv("SCAMD_GRAM_CHUNKS")) n_chunks = std::max(1, std::min(nblk, atoi(e)));  // (A/B knob)
     const int blocks_per_chunk = (nblk + n_chunks - 1) / n_chunks;
     n_chunks = (nblk + blocks_per_chunk - 1) / blocks_per_chunk;
     auto gram_kernel = gram_quad_kernel<true>;
@@ -899,15 +883,10 @@ extern "C" int scamd_csr_gram_f32(const int64_t* indptr, const int32_t* indices,
     hipLaunchKernelGGL(gram_tileptr_kernel, dim3((unsigned)ceil_div(n, 4)), dim3(256), 0, s, indptr, indices, n, ntile, cv.ptr);
     SCAMD_LAUNCH_CHECK();
     int n_chunks = pick_chunks((n + 4095) / 4096);
-    if (const char* e = getenv("SCAMD_GRAM_CHUNKS")) n_chunks = std::max(1, std::min<int>((int)((n + 255) / 256), atoi(e)));  // (A/B knob)
     const int rows_per_chunk = (int)((n + n_chunks - 1) / n_chunks);
     n_chunks = (int)((n + rows_per_chunk - 1) / rows_per_chunk);
-    static const bool a_from_mem = [] {
-      const char* e = getenv("SCAMD_GRAM_A_FROM_MEM");
-      return e && e[0] == '1';
-    }();
-    auto gram_kernel = a_from_mem ? gram_tile_kernel<true, true> : gram_tile_kernel<false, true>;
-    auto gram_exact = gram_tile_kernel<false, false>;
+    auto gram_kernel = gram_tile_kernel<true>;
+    auto gram_exact = gram_tile_kernel<false>;
     SCAMD_HIP_CHECK(hipFuncSetAttribute(reinterpret_cast<const void*>(gram_kernel),
                                         hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
     SCAMD_HIP_CHECK(hipFuncSetAttribute(reinterpret_cast<const void*>(gram_exact),

@@ -429,7 +429,7 @@ struct RegCfg {
   static constexpr int TILE_KB = TILE_BYTES / 1024;
   // tile buffers in LDS: the float32 engine stages through registers into two; the bf16 engine's tiles arrive by LDS-DMA
   // into a ring of three, two requests in flight behind the tile being scored (round 4: see `sweep`)
-  static constexpr bool GLDS = B3 && TC_ == 64;  // (the 128-candidate tiles of SCAMD_KNN_BIG_TILES keep the register staging)
+  static constexpr bool GLDS = B3 && TC_ == 64;
   static constexpr int NBUF = GLDS ? 3 : 2;
   static constexpr size_t LDS_BYTES = NBUF * (size_t)TILE_BYTES;
   static_assert(TILE_BYTES % 1024 == 0, "tile must be a whole number of 1 KiB pieces");
@@ -560,13 +560,9 @@ struct IvfArgs {
   unsigned long long* pairs; // (query, candidate) pairs evaluated, for the roofline figure
   const int* block_perm;     // [n_blocks] launch slot -> block: cells with the longest expected sweep first (LPT)
   int* qorder;               // [n_blocks * 128] out (may be null): query number (row - q_begin) of every query slot, -1 = padding
-  int prepass_tiles;         // tiles of the own cell the threshold pre-pass scores (SCAMD_KNN_PREPASS_TILES, default 32 bf16 / 16 float32)
-  int prepass_cells;         // cells (own cell first, then by ascending lower bound) the pre-pass covers (SCAMD_KNN_PREPASS_CELLS, default 1)
+  int prepass_tiles;         // tiles of the own cell the threshold pre-pass scores (32 bf16 / 16 float32)
   int prepass_min2;          // 1: the starting threshold is taken from the two smallest scores per lane (SCAMD_KNN_PREPASS_MIN2, default 1)
   const unsigned int* cmax_bits;  // float bits of the largest ||c||^2 of the image (the COARSE sweep's slack, see knn_select_reg_block)
-  int debug_no_insert;       // debug (SCAMD_KNN_DEBUG_NO_INSERT=1): survivors are dropped -- WRONG results, MFMA-side ceiling
-  int cell_preload;          // 1: (bf16 engine) the tile requests run on into the next cell of the block's order while the
-                             // current cell's last tiles are scored (SCAMD_KNN_CELL_PRELOAD, default 1; 0: every cell starts cold)
   unsigned long long* trace; // debug (SCAMD_KNN_TRACE=<file>): per block {start, end (100 MHz clock), tiles swept, hw id,
                              // end of the prologue, end of the pre-pass, ticks inside the sweeps of the cells, cells swept}
   int n_cells, dc;          // dc = stride of `centers` (>= d)
@@ -773,20 +769,7 @@ __device__ __forceinline__ void knn_select_reg_block(const int blk, const float*
   auto chain = [&](const BFrag& b, float athr_op) -> f32x16 {
     if constexpr (B3) {
       (void)athr_op;
-#ifdef SCAMD_KNN_PROBE_HH
-      // PROBE BUILD ONLY (tools/knn_coarse_probe.sh compiles a second library with this macro; WRONG results): the hi.hi product
-      // alone -- what a coarse first stage of the sweep would cost.  (As a RUN-TIME switch on `iv` this branch made the
-      // production kernel 4.3 x slower -- 50.1 instead of 11.7 ms: DESIGN.md section 8, round 6.)
-      f32x16 acc;
-#pragma unroll
-      for (int r = 0; r < 16; ++r) acc[r] = 0.f;
-#pragma unroll
-      for (int s = 0; s < 4; ++s)
-        acc = __builtin_amdgcn_mfma_f32_32x32x16_bf16(__builtin_bit_cast(bf16x8, qh[s]), __builtin_bit_cast(bf16x8, b.h[s]), acc, 0, 0, 0);
-      return acc;
-#else
       return b3_chain(qh, ql, b);
-#endif
     } else {
       f32x16 acc;
 #pragma unroll
@@ -885,10 +868,7 @@ __device__ __forceinline__ void knn_select_reg_block(const int blk, const float*
         // and two fragment sets live across the refinement: 1408 B of scratch per lane and 2.2 s instead of 0.26 s, measured);
         // the deferred tests of the plain pipeline are skipped in this mode (here, and at the end of the sweep)
         acc_cur = b3_chain_hh(qh, b_cur);
-        if (coarse_hit(acc_cur)) {
-          if (iv.debug_no_insert) return;
-          refine(acc_cur, b_cur, athr_cur, row0 + g * 32);
-        }
+        if (coarse_hit(acc_cur)) refine(acc_cur, b_cur, athr_cur, row0 + g * 32);
         return;
       }
     }
@@ -918,9 +898,6 @@ __device__ __forceinline__ void knn_select_reg_block(const int blk, const float*
         }
         return;
       }
-    }
-    if constexpr (IVF) {
-      if (iv.debug_no_insert) return;
     }
     if (lane == 0) {
       SCAMD_EMU_COUNT(3, 1);              // [3] sub-tiles tested by a wave (32 queries x 32 candidates)
@@ -1090,8 +1067,6 @@ __device__ __forceinline__ void knn_select_reg_block(const int blk, const float*
     const unsigned long long trace_t0 = iv.trace ? wall_clock64() : 0ull;
     unsigned long long trace_tiles = 0;
     const int a = iv.block_cell[blk];
-    const int* order = iv.order + (int64_t)a * iv.n_cells;
-    const float* lb2 = iv.order_lb2 + (int64_t)a * iv.n_cells;
     // the head of the order with its tile ranges -> LDS (one gather by wave 0, under the latency of the query operand's)
     int* s_t0 = reinterpret_cast<int*>(wmax + 16);
     int* s_nt = s_t0 + IVF_META_CELLS;
@@ -1136,20 +1111,10 @@ __device__ __forceinline__ void knn_select_reg_block(const int blk, const float*
       const int pre_tiles = min(iv.cell_ntiles[a], iv.prepass_tiles);
       if (tid == 0) atomicAdd(iv.pairs + 1, (unsigned long long)pre_tiles * TC * C::QB);  // counted apart: not useful work
       // (the real sweep starts with the own cell's first tile again: requested under the pre-pass's last tile)
-      next_tile0 = (iv.cell_preload && iv.prepass_cells <= 1) ? meta_t0(0) : -1;
+      next_tile0 = meta_t0(0);
       next_n = meta_nt(0);
       sweep(iv.cell_tile0[a], pre_tiles, false);
       next_tile0 = -1;
-      // round 4: the pre-pass may go on over the next nearest cells (iv.prepass_cells - 1 of them, whole cells).  The sweep
-      // is bound by the instructions of the list insertions, not by the matrix pipe (counters: profiles/r04a_knn_pmc*.csv),
-      // and an insertion-free pass over more candidates starts the lists nearer their final thresholds.
-      for (int ci = 1; ci < iv.prepass_cells && ci < iv.n_cells; ++ci) {
-        if (!(lb2[ci] < INFINITY)) break;
-        const int pb = order[ci];
-        block_sync();
-        if (tid == 0) atomicAdd(iv.pairs + 1, (unsigned long long)iv.cell_ntiles[pb] * TC * C::QB);
-        sweep(iv.cell_tile0[pb], iv.cell_ntiles[pb], false);
-      }
       minima = false;
       block_sync();
       // compare-exchange constants: a lane whose bit b (of l31) is clear keeps the SMALLER value of its pair --
@@ -1242,7 +1207,7 @@ __device__ __forceinline__ void knn_select_reg_block(const int blk, const float*
       const int c_t0 = meta_t0(ci), c_nt = meta_nt(ci);
       trace_tiles += c_nt;  // (also the block's count of evaluated pairs: one atomic when it is done)
       // (no request across a refill of the table, nor past the last cell: the table's entries beyond n_cells are INF)
-      next_tile0 = (iv.cell_preload && ((ci + 1) & (IVF_META_CELLS - 1)) != 0 && meta_lb(ci + 1) < INFINITY) ? meta_t0(ci + 1) : -1;
+      next_tile0 = (((ci + 1) & (IVF_META_CELLS - 1)) != 0 && meta_lb(ci + 1) < INFINITY) ? meta_t0(ci + 1) : -1;
       next_n = meta_nt((ci + 1) & (IVF_META_CELLS - 1));
       const unsigned long long ts = iv.trace ? wall_clock64() : 0ull;
       sweep(c_t0, c_nt, first);
@@ -2377,11 +2342,7 @@ static bool knn_plan(int64_t n, int d, int64_t n_query, int k, KnnPlan* p, int n
     p->NW = 2;
     p->KP = std::max(p->KP, 128);
   }
-  static const bool legacy = [] {
-    const char* e = getenv("SCAMD_KNN_LEGACY");
-    return e && e[0] == '1';
-  }();
-  p->reg = (p->KP == 32 && p->H <= 32 && !legacy);
+  p->reg = (p->KP == 32 && p->H <= 32);
   {
     // k columns = self + k-1 others must be certified below the threshold: keep a margin of 6 ranks
     static const int margin = [] {
@@ -2566,15 +2527,9 @@ template <int H>
 static int launch_select_reg(const KnnPlan& p, const KnnBuffers& b, int64_t q_begin, hipStream_t s) {
   // 64-candidate tiles (30 KB of LDS per block) and <= 168 VGPRs: three 4-wave blocks share a CU and cover each
   // other's barrier / insertion stalls (measured 812 vs 831 ms at 1M against 128-candidate tiles, two blocks)
-  static const bool big_tiles = [] {
-    const char* e = getenv("SCAMD_KNN_BIG_TILES");
-    return e && e[0] == '1';
-  }();
   if constexpr (H == 25) {
-    if (p.b3) return big_tiles ? launch_select_reg_mode<25, 128, 2, true>(p, b, q_begin, s)
-                               : launch_select_reg_mode<25, 64, 2, true>(p, b, q_begin, s);
+    if (p.b3) return launch_select_reg_mode<25, 64, 2, true>(p, b, q_begin, s);
   }
-  if (big_tiles) return launch_select_reg_mode<H, 128, 2>(p, b, q_begin, s);
   return launch_select_reg_mode<H, 64, 3>(p, b, q_begin, s);
 }
 
@@ -2660,11 +2615,8 @@ static int run_ivf_select(const KnnPlan& p, const KnnBuffers& b, const float* x,
   SCAMD_LAUNCH_CHECK();
   const int64_t n_sample = std::min<int64_t>(n, (int64_t)64 * nc);
   const int64_t step = n / n_sample;
-  static const int lloyd_iters = [] {  // (A/B knob; 3 since round 1)
-    const char* e = getenv("SCAMD_KNN_LLOYD_ITERS");
-    return e ? std::max(0, std::min(16, atoi(e))) : 3;
-  }();
-  for (int it = 0; it < lloyd_iters; ++it) {
+  // (Lloyd iterations of the quantiser: 1 / 2 / 3 / 5 all leave the stage at 15.3-15.4 ms)
+  for (int it = 0; it < 3; ++it) {
     SCAMD_HIP_CHECK(hipMemsetAsync(b.sums, 0, sizeof(long long) * nc * d, s));
     SCAMD_HIP_CHECK(hipMemsetAsync(counts, 0, sizeof(int) * nc, s));
     const int rca = run_assign(0, step, n_sample, 1, 0, 0, nullptr);
@@ -2732,19 +2684,18 @@ static int run_ivf_select(const KnnPlan& p, const KnnBuffers& b, const float* x,
   }
   const int n_blocks = (int)h_block_cell.size();
   SCAMD_REQUIRE(rows <= p.n_img_max && slots <= p.n_slot_max, SCAMD_EWORKSPACE, "knn: cell layout exceeds its bound");
-  // launch slots: block-id order = n_blocks; XCD-aware order (SCAMD_KNN_XCD_ORDER=0 disables it) = 8 queues of at most
+  // launch slots: block-id order = n_blocks; XCD-aware order = 8 queues of at most
   // ceil(n_blocks / 8) + (blocks of the largest cell) slots, if the table has room
   int n_launch = n_blocks, xcd_mode = 0;
   {
     // (the queues are built on the device from the device's work estimates; the host sizes the launch for queues of twice
     // the mean length plus the largest cell -- slots beyond a queue's end hold -1 and exit at once, a queue that would
     // not fit is cut off by `slot < n_slots` in ivf_block_order_kernel ... which must not happen: checked there)
-    const char* e = getenv("SCAMD_KNN_XCD_ORDER");
     int maxb = 0;
     for (int c = 0; c < nc; ++c) maxb = std::max(maxb, h_blk[nc + c]);
     const int64_t want = (int64_t)8 * (2 * ((n_blocks + 7) / 8) + maxb);
     const int64_t cap = (int64_t)(p.n_slot_max / 128 + 1) * 2 + 64;
-    if (!(e && e[0] == '0') && n_blocks >= 64 && want <= cap) {
+    if (n_blocks >= 64 && want <= cap) {
       xcd_mode = 1;
       n_launch = (int)want;
     }
@@ -2771,12 +2722,8 @@ static int run_ivf_select(const KnnPlan& p, const KnnBuffers& b, const float* x,
                      row_cur, q_begin, q_begin + n_query, slot_off, slot_cur, b.perm, b.qpos, b.qrow, nc);
   SCAMD_LAUNCH_CHECK();
   {
-    // (a group of 16 lanes per image row, 16 groups per workgroup; SCAMD_KNN_PACK_BLOCKS: A/B of the grid)
-    static const int pack_blocks_env = [] {
-      const char* e = getenv("SCAMD_KNN_PACK_BLOCKS");
-      return e ? atoi(e) : 0;
-    }();
-    const int blocks = (int)std::min<int64_t>((rows + 15) / 16, pack_blocks_env > 0 ? pack_blocks_env : 256 * 16);
+    // (a group of 16 lanes per image row, 16 groups per workgroup)
+    const int blocks = (int)std::min<int64_t>((rows + 15) / 16, 256 * 16);
     hipLaunchKernelGGL(ivf_pack_image_kernel, dim3(blocks), dim3(256), 0, s, x, b.mu, d, ld, H, C::HP, C::DPL, rows, b.perm,
                        b.labels, cell_map, b.cent, b.xp, b.cmax, b.radius_bits, B3 ? 1 : 0);
     SCAMD_LAUNCH_CHECK();
@@ -2798,17 +2745,13 @@ static int run_ivf_select(const KnnPlan& p, const KnnBuffers& b, const float* x,
     SCAMD_LAUNCH_CHECK();
   }
   // 6. pruned sweep
-  // register budget: cut for 3 resident blocks per CU by default (168 VGPRs; the H = 25 / 32 instantiations then spill
-  // 96 / 236 bytes per lane to scratch, `-Rpass-analysis=kernel-resource-usage`); SCAMD_KNN_IVF_WPS=2 selects the
-  // build cut for 2 blocks per CU (no spills) -- an A/B switch until both have been measured
-  const char* wps_env = getenv("SCAMD_KNN_IVF_WPS");
-  // (bf16 engine, round 4: with its tiles arriving by LDS-DMA the staging registers are gone -- 175 VGPRs uncut, 5 of them
-  // spilled in the build cut for 3 blocks per CU (was 47), and 3 x 53 KB of LDS just fit the CU's 160: 13.31 ms against
-  // 16.11 with 2 blocks on one box, profiles/r04s_knn_lds_dma_ring_ab.log -- a third block covers the other two's insertion
-  // stalls.  SCAMD_KNN_IVF_WPS=2 selects the uncut build)
-  auto kern = B3 ? ((wps_env && atoi(wps_env) == 2) ? knn_select_reg_kernel<H, 64, 2, true, B3> : knn_select_reg_kernel<H, 64, 3, true, B3>)
-                 : ((wps_env && atoi(wps_env) == 2) ? knn_select_reg_kernel<H, 64, 2, true, false>
-                                                     : knn_select_reg_kernel<H, 64, 3, true, false>);
+  // register budget: cut for 3 resident blocks per CU (168 VGPRs; the H = 25 / 32 instantiations then spill 96 / 236
+  // bytes per lane to scratch, `-Rpass-analysis=kernel-resource-usage`; measured against the build cut for 2 blocks per
+  // CU, which does not spill).  (bf16 engine, round 4: with its tiles arriving by LDS-DMA the staging registers are gone --
+  // 175 VGPRs uncut, 5 of them spilled in the build cut for 3 blocks per CU (was 47), and 3 x 53 KB of LDS just fit the
+  // CU's 160: 13.31 ms against 16.11 with 2 blocks on one box, profiles/r04s_knn_lds_dma_ring_ab.log -- a third block
+  // covers the other two's insertion stalls)
+  auto kern = knn_select_reg_kernel<H, 64, 3, true, B3>;
   // COARSE first stage (bf16 engine; knn_select_reg_block): pays when a query meets so many candidates that few 32 x 32
   // sub-tiles hold one below its threshold -- the sweeps in which the cell bounds prune little.  Decided from the device's own
   // work estimates (tiles within a cell's radius, ivf_cell_order_kernel), weighted by the cells' query blocks: expected
@@ -2855,22 +2798,11 @@ static int run_ivf_select(const KnnPlan& p, const KnnBuffers& b, const float* x,
   iv.block_perm = b.block_perm;
   iv.qorder = b.qorder;
   {
-    const char* e = getenv("SCAMD_KNN_PREPASS_TILES");
     // float32 engine, measured at 1M: 48 -> 29.3 ms, 24 / 12 -> 29.0, 6 -> 29.6, 2 -> 30.2; bf16 engine (the pre-pass
     // costs a quarter): 8 -> 17.1, 16 -> 16.8, 32 -> 16.15, 64 -> 16.1
-    iv.prepass_tiles = e ? std::max(1, atoi(e)) : (B3 ? 32 : 16);
-    const char* e2 = getenv("SCAMD_KNN_PREPASS_CELLS");
-    iv.prepass_cells = e2 ? std::max(1, atoi(e2)) : 1;
+    iv.prepass_tiles = B3 ? 32 : 16;
     const char* e3 = getenv("SCAMD_KNN_PREPASS_MIN2");
     iv.prepass_min2 = (e3 && e3[0] == '0') ? 0 : 1;
-  }
-  {
-    const char* e = getenv("SCAMD_KNN_DEBUG_NO_INSERT");
-    iv.debug_no_insert = (e && e[0] == '1') ? 1 : 0;
-  }
-  {
-    const char* e = getenv("SCAMD_KNN_CELL_PRELOAD");  // A/B switch: 0 = every cell's sweep requests its first tile itself
-    iv.cell_preload = (e && e[0] == '0') ? 0 : 1;
   }
   iv.trace = nullptr;
   const char* trace_path = getenv("SCAMD_KNN_TRACE");  // debug: per-block timeline of the sweep, dumped to this file
@@ -2885,7 +2817,7 @@ static int run_ivf_select(const KnnPlan& p, const KnnBuffers& b, const float* x,
   iv.n_slots = n_launch;
   {
     const char* e = getenv("SCAMD_KNN_PERSISTENT");
-    const int want = e ? atoi(e) : 256 * ((wps_env && atoi(wps_env) == 2) ? 2 : 3);
+    const int want = e ? atoi(e) : 768;
     if (want > 0 && n_launch > want) {
       n_groups = (want + 7) / 8 * 8;
       iv.queue_ctr = b.counters + 8;
@@ -3008,10 +2940,7 @@ static int run_ivf_tier2(const KnnPlan& p, const KnnBuffers& b, const float* x, 
   iv.block_perm = b.block_perm;
   iv.qorder = nullptr;
   iv.prepass_tiles = 16;
-  iv.prepass_cells = 1;
   iv.prepass_min2 = 1;
-  iv.debug_no_insert = 0;
-  iv.cell_preload = 1;
   iv.trace = nullptr;
   iv.queue_ctr = nullptr;  // (a few hundred queries: one workgroup per block)
   iv.n_slots = n_blocks;

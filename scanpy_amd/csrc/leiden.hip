@@ -36,29 +36,9 @@ namespace scamd {
 //     active rows x (12 B per entry + 16 B per vertex), SURVEY.md 8(d)'s per-sweep figure restricted to the rows a sweep visits,
 // [10] communities the polish split off because a departure had cut them in two, [11] 1 if the iteration cap ended the run,
 // [12] 1 if a polish pass stopped at MAX_POLISH_ROUNDS (node optimality then NOT proven), [13] the iteration cap in force
-// register budgets of the decision kernels (second launch bound = waves per SIMD the compiler must fit; A/B builds: -D...)
-#ifndef SCAMD_LD_PROPOSE_WAVES
-#define SCAMD_LD_PROPOSE_WAVES 0
-#endif
-#ifndef SCAMD_LD_MOVE_WAVES
-#define SCAMD_LD_MOVE_WAVES 0
-#endif
-#if SCAMD_LD_PROPOSE_WAVES > 0
-#define SCAMD_LD_PROPOSE_LB __launch_bounds__(256, SCAMD_LD_PROPOSE_WAVES)
-#else
-#define SCAMD_LD_PROPOSE_LB __launch_bounds__(256)
-#endif
-#if SCAMD_LD_MOVE_WAVES > 0
-#define SCAMD_LD_MOVE_LB __launch_bounds__(256, SCAMD_LD_MOVE_WAVES)
-#else
-#define SCAMD_LD_MOVE_LB __launch_bounds__(256)
-#endif
 // table slots of a vertex of the sixteen-lanes-per-vertex kernels (the kNN graph itself); rows longer than 3/4 of them go to
 // the wave-per-vertex tier
-#ifndef SCAMD_LD_G16_SLOTS
-#define SCAMD_LD_G16_SLOTS 128
-#endif
-constexpr int G16_SLOTS = SCAMD_LD_G16_SLOTS;
+constexpr int G16_SLOTS = 128;
 constexpr int G16_MAX = G16_SLOTS * 3 / 4;
 constexpr int LD_NSTATS = 16;
 static thread_local int g_ld_stats[LD_NSTATS] = {0};
@@ -657,7 +637,7 @@ __device__ __forceinline__ void ld_move_body(int bid, int nblk, const MoveArgs& 
   }
 }
 template <int G>
-__global__ SCAMD_LD_MOVE_LB void ld_move_kernel(
+__global__ __launch_bounds__(256) void ld_move_kernel(
     int n_act, const int* __restrict__ list, const int* __restrict__ sub_list, const int* __restrict__ sub_count,
     const int64_t* __restrict__ indptr, const int* __restrict__ indices, const long long* __restrict__ wq,
     const long long* __restrict__ k, const int* __restrict__ comm, const unsigned long long* __restrict__ Ktot,
@@ -859,7 +839,7 @@ __global__ __launch_bounds__(256) void ld_requeue_kernel(int n_act, const int* _
 // write their own buffer and lists.  The first nb_rq workgroups re-queue, the rest decide.  One launch of ~16 us less per
 // sub-round (152 per call at 1M cells).
 template <int G>
-__global__ SCAMD_LD_MOVE_LB void ld_requeue_move_kernel(int nb_rq, int rq_n_act, const int* __restrict__ rq_list,
+__global__ __launch_bounds__(256) void ld_requeue_move_kernel(int nb_rq, int rq_n_act, const int* __restrict__ rq_list,
                                                               const int* __restrict__ rq_decision,
                                                               const int64_t* __restrict__ indptr,
                                                               const int* __restrict__ indices, const int* __restrict__ comm,
@@ -1214,7 +1194,7 @@ __device__ __forceinline__ double refine_noise(int v, int c, int round, unsigned
 // `list` holds the candidates of class `round` (the sub-round's number).  target[v] = refined community to join,
 // -1 = no admissible target, -2 = no longer a singleton (somebody joined it) or "stay" was drawn.
 template <int G>
-__global__ SCAMD_LD_PROPOSE_LB void ld_refine_propose_kernel(
+__global__ __launch_bounds__(256) void ld_refine_propose_kernel(
     const int* __restrict__ list, const int* __restrict__ sub_list, const int* __restrict__ sub_count,
     const int64_t* __restrict__ indptr, const int* __restrict__ indices, const long long* __restrict__ wq,
     const long long* __restrict__ k, const int* __restrict__ comm, const unsigned long long* __restrict__ Ktot,
@@ -2015,7 +1995,7 @@ __device__ __forceinline__ int small_compact(int n, P pred, unsigned short* orde
   return base;
 }
 
-constexpr int SMALL_SEQ_N = 16;   // levels of at most this many vertices: local moving one vertex at a time (SCAMD_LEIDEN_SMALL_SEQ)
+constexpr int SMALL_SEQ_N = 16;   // levels of at most this many vertices: local moving one vertex at a time
 __global__ __launch_bounds__(SM_THREADS) void ld_small_levels_kernel(SmallArgs a) {
   extern __shared__ __attribute__((aligned(16))) unsigned char small_smem[];
   SmallLds& L = *reinterpret_cast<SmallLds*>(small_smem);
@@ -2552,15 +2532,6 @@ struct LeidenBuffers {
   unsigned long long* ckeys; int* cids; int* newlabel; int* minmember;
 };
 
-// class sub-rounds the SCAMD_LEIDEN_LM_CLASSES / SCAMD_LEIDEN_RF_CLASSES overrides can ask for on a level of any size
-static int classes_env(const char* name) {
-  const char* e = getenv(name);
-  const int v = e ? atoi(e) : 0;
-  return (v == 1 || v == 2 || v == 4 || v == 8 || v == 16 || v == 32) ? v : 0;
-}
-static int carve_classes() {
-  return std::max((int)DEF_CLASSES, std::max(classes_env("SCAMD_LEIDEN_LM_CLASSES"), classes_env("SCAMD_LEIDEN_RF_CLASSES")));
-}
 // member entries per part of a split coarse row / entries from which a row is split (SCAMD_LEIDEN_AGG_SPLIT_CHUNK / _WORK:
 // tests push small graphs through the split path; resolved here so that the workspace query and the run agree)
 static int64_t agg_split_chunk() {
@@ -2584,11 +2555,10 @@ static void leiden_carve(Workspace& ws, int64_t n, int64_t nnz, LeidenBuffers* b
   b->comm = ws.take<int>(N);
   b->csize = ws.take<int>(N);
   b->Ktot = ws.take<unsigned long long>(N);
-  // class lists of a sweep (local moving) / of the refinement: lists[c * n_level ..].  Levels above 4096 vertices use
-  // DEF_CLASSES lists unless the SCAMD_LEIDEN_*_CLASSES overrides ask for more (resolved here, so that the workspace query
-  // and the run agree); only levels of <= 4096 vertices take MAX_CLASSES refinement sub-rounds.  (Round 3 carved
+  // class lists of a sweep (local moving) / of the refinement: lists[c * n_level ..].  Levels above 4096 vertices use at
+  // most DEF_CLASSES lists; only levels of <= 4096 vertices take MAX_CLASSES refinement sub-rounds.  (Round 3 carved
   // MAX_CLASSES x N: 1.28 GB at 10M cells for lists of which 8 were ever used)
-  b->cls_lists = ws.take<int>(std::max((size_t)carve_classes() * N, (size_t)MAX_CLASSES * std::min<size_t>(N, 4096)));
+  b->cls_lists = ws.take<int>(std::max((size_t)DEF_CLASSES * N, (size_t)MAX_CLASSES * std::min<size_t>(N, 4096)));
   b->rlist = ws.take<int>(N);
   b->hub_list = ws.take<int>(N);
   b->touched = ws.take<int>(N);
@@ -2641,6 +2611,16 @@ static void leiden_carve(Workspace& ws, int64_t n, int64_t nnz, LeidenBuffers* b
 #define GRIDW(n) dim3((unsigned)ceil_div((n), 4)), dim3(256)
 #define GRIDK(n) dim3((unsigned)ceil_div((n), 1024)), dim3(1024)
 constexpr int HUB_GRID = 512;
+// workgroups of the 512-thread tier of the coarse-row builder (the 1024-thread tier launches HUB_GRID); each loops over
+// its share of the listed rows: a launch of N such workgroups costs ~0.27 us x N before any work is done (fewer were
+// measured slower: DESIGN section 8)
+constexpr int AGG_MID_GRID = 768;
+// local moving of a level stops once < 2 % of its vertices move in a sweep (first iteration)
+constexpr int LM_STOP_PERMILLE = 20;
+// ... < 4 % on the levels that run four classes per sweep (lm_classes): 0.9 ms / 11 ms faster on the planted / weak 1M graph
+// at the same Q / inside the seeds' spread (profiles/r06ze_lm_stop_with_4_classes.log); everywhere, one seed of the 700-cell
+// fixture fell out of the oracle's seed distribution
+constexpr int LM_STOP_PERMILLE_BIG = 40;
 constexpr size_t HUB_LDS = (size_t)BHUB_SLOTS * 12;
 
 struct LeidenCtx {
@@ -2662,35 +2642,20 @@ struct LeidenCtx {
   double inv_beta = 0.0;  // 1 / (beta * 2^32): randomness of the refinement's merge rule (0 = greedy)
   int iter = 0;           // outer iteration: part of the refinement's noise seed
   unsigned int seed;
-  int lm_stop_permille = 20;  // local moving of a level stops once < 2 % of its vertices move in a sweep (first iteration)
-  int lm_stop_permille_big = 40;  // ... < 4 % on the levels that run four classes per sweep (lm_classes): 0.9 ms / 11 ms faster on the
-                                  // planted / weak 1M graph at the same Q / inside the seeds' spread (profiles/r06ze_lm_stop_with_4_classes.log);
-                                  // everywhere, one seed of the 700-cell fixture fell out of the oracle's seed distribution
-  int lm_classes = 0;         // class sub-rounds per local-moving sweep (0 = by level size; SCAMD_LEIDEN_LM_CLASSES)
-  int rf_classes = 0;         // class sub-rounds of the refinement (0 = by level size; SCAMD_LEIDEN_RF_CLASSES)
   bool small_levels = true;   // levels of <= SMALL_N nodes in one workgroup (SCAMD_LEIDEN_SMALL=0: separate kernels)
   int l0_moves = -1;          // moves of the last iteration's level-0 local moving (0: its input was node optimal)
   int n_levels = 0;           // levels the last iteration went through
   bool polish = true;         // SCAMD_LEIDEN_POLISH=0: no final polish (A/B; the round-4 behaviour)
-  bool no_fuse = false;       // SCAMD_LEIDEN_FUSE=0: re-queue and the next sub-round's decisions as separate launches (A/B)
-  int small_seq_n = SMALL_SEQ_N;  // ... of which those of <= small_seq_n vertices move one vertex at a time (SCAMD_LEIDEN_SMALL_SEQ)
   // coarse-row build tiers (distinct-neighbour bounds); the env overrides exist so the tests can push small graphs
   // through the workgroup and multi-pass tiers
   int agg_wave_max = WH_MAX_DEG;
   int agg_mid_max = AGG_MID_MAX;
   int agg_pass_keys = AGG_BIG_PASS;
-  // workgroups of the two workgroup tiers of the coarse-row builder (each loops over its share of the listed rows): a
-  // launch of N such workgroups costs ~0.27 us x N before any work is done (SCAMD_LEIDEN_AGG_MID_GRID / _BIG_GRID)
-  int agg_mid_grid = 768;
-  int agg_big_grid = HUB_GRID;
   // member entries beyond which a coarse row leaves the wave tier / the 512-thread tier whatever its table size
   // (SCAMD_LEIDEN_AGG_WAVE_WORK / _MID_WORK)
   int agg_wave_work = 2048;
   int agg_mid_work = 65536;
   int hub_try_probes = HUB_TRY_PROBES;  // 0: no optimistic single pass over multi-pass rows (SCAMD_LEIDEN_HUB_TRY_PROBES; tests)
-  // sweeps of the local moving that follow a sweep with at most `small_sweep_act` active vertices use `small_sweep_classes`
-  // class sub-rounds instead of the level's (0: off) -- see local_moving
-  int small_sweep_act = 0, small_sweep_classes = 2;
 };
 
 static bool g_leiden_debug = false;  // SCAMD_LEIDEN_DEBUG=1, read at every entry (tools switch it inside one process)
@@ -2754,11 +2719,8 @@ static int compute_totals(LeidenCtx& cx, const LevelGraph& g, const int* comm, F
 // (b.total[1], the accumulator of the internal weight, was zeroed by the ld_totals_kernel launch of compute_totals)
 static int quality(LeidenCtx& cx, const LevelGraph& g, const int* comm, double* q) {
   // (a group walks its vertices one after the other, three dependent loads each: the more groups, the fewer steps of that
-  // walk -- and one same-word atomic per workgroup at the end; SCAMD_LEIDEN_QUALITY_GRID: A/B)
-  static const int qgrid = [] {
-    const char* e = getenv("SCAMD_LEIDEN_QUALITY_GRID");
-    return e ? std::max(64, atoi(e)) : 2048;
-  }();
+  // walk -- and one same-word atomic per workgroup at the end)
+  constexpr int qgrid = 2048;
   if (g.nnz <= (int64_t)48 * g.n)
     hipLaunchKernelGGL(ld_internal_kernel<16>, dim3((unsigned)std::min(qgrid, ceil_div(g.n, 16))), dim3(256), 0, cx.s, g.n,
                        g.indptr, g.indices, g.wq, comm, cx.b.total + 1);
@@ -2806,30 +2768,17 @@ static bool level_is_short_rowed(const LevelGraph& g) { return level_lanes(g) ==
 // neighbours, half of which deciding on the same snapshot costs nothing the next sweep does not repair -- it is the SMALL levels
 // where fewer classes lose quality (see rf_classes; with four classes from 65536 vertices on, the 100k weak sample of the bench
 // fell below its agreement gate against the oracle: median ARI over seed pairs 0.02 under the oracle's own).  Four from 262144
-// vertices on; SCAMD_LEIDEN_LM_BIG_N moves that size (0: eight everywhere).
+// vertices on.
 static int lm_classes(const LeidenCtx& cx, int n) {
-  static const int big_n = [] {
-    const char* e = getenv("SCAMD_LEIDEN_LM_BIG_N");
-    return e ? atoi(e) : 262144;
-  }();
-  if (cx.lm_classes > 0) return cx.lm_classes;
   // (the iterations after the first move a few hundred vertices of a large level per sweep: TWO classes there -- weak 1M graph 429 ->
   // 418 ms over three seeds at the same Q, the others unchanged; one class: everybody on one snapshot, far slower to settle)
-  static const int later_cls = [] {
-    const char* e = getenv("SCAMD_LEIDEN_LM_LATER_CLASSES");
-    const int v = e ? atoi(e) : 2;
-    return (v == 1 || v == 2 || v == 4 || v == 8) ? v : 2;
-  }();
-  if (big_n > 0 && n >= big_n) return cx.iter >= 1 ? later_cls : 4;
+  if (n >= 262144) return cx.iter >= 1 ? 2 : 4;
   return DEF_CLASSES;
 }
 // (refinement: a singleton cannot join a singleton of its OWN class -- with 8 classes an eighth of the targets the
 // sequential algorithm would see are excluded, which on small graphs costs quality: 700-cell fixture over 30 seeds, runs
 // ending below Q 0.8115: oracle 0, 32 classes 0, 8 classes 2, 2 classes 5.  Small levels therefore take 32 sub-rounds.)
-static int rf_classes(const LeidenCtx& cx, int n) {
-  if (cx.rf_classes > 0) return cx.rf_classes;
-  return n <= 4096 ? MAX_CLASSES : DEF_CLASSES;
-}
+static int rf_classes(int n) { return n <= 4096 ? MAX_CLASSES : DEF_CLASSES; }
 
 static int local_moving(LeidenCtx& cx, const LevelGraph& g, int* total_moves) {
   LeidenBuffers& b = cx.b;
@@ -2842,11 +2791,9 @@ static int local_moving(LeidenCtx& cx, const LevelGraph& g, int* total_moves) {
   if (rc != SCAMD_OK) return rc;
   const int lanes = level_lanes(g);
   const int thr_mid = lanes == 16 ? (int)G16_MAX : (lanes == 32 ? (int)(WH_SLOTS / 2 * 3 / 4) : -1);
-  const int n_cls_level = lm_classes(cx, g.n);
-  int n_act_prev = g.n;
+  const int n_cls = lm_classes(cx, g.n);
   int moved_before = 0, quiet = 0, moved_prev2 = 0;
   for (int sweep = 0; sweep < MAX_LM_SWEEPS; ++sweep) {
-    const int n_cls = (sweep > 0 && n_act_prev <= cx.small_sweep_act) ? std::min(n_cls_level, cx.small_sweep_classes) : n_cls_level;
     // [0, MAX_CLASSES): class list lengths of the sweep; then one block per sub-round: hub / overflow counts
     int* sw = b.rcounters + (sweep & 1) * CTR_AREA;
     const unsigned int salt = hash32(cx.seed + 0x85EBCA77u * (unsigned int)(sweep + 1) + 0xC2B2AE3Du * (unsigned int)cx.iter);
@@ -2861,7 +2808,6 @@ static int local_moving(LeidenCtx& cx, const LevelGraph& g, int* total_moves) {
     SCAMD_REQUIRE(ht[7] == 0, SCAMD_EINTERNAL, "leiden: hub table overflow (local moving)");
     int n_act = 0;
     for (int c = 0; c < n_cls; ++c) n_act += hc[c];
-    n_act_prev = n_act;
     const int moved_last = ht[0] - moved_before;  // moves of the previous sweep
     moved_before = ht[0];
     *total_moves = ht[0];
@@ -2879,7 +2825,7 @@ static int local_moving(LeidenCtx& cx, const LevelGraph& g, int* total_moves) {
       quiet = (moved_last == 0) ? quiet + 1 : 0;
       if (quiet >= 2) break;
       // Vertex-by-vertex merging of whole communities is what the coarser levels are for: once fewer than
-      // lm_stop_permille/1000 of the level's vertices move in a sweep, go on to refinement + aggregation (the
+      // LM_STOP_PERMILLE/1000 of the level's vertices move in a sweep, go on to refinement + aggregation (the
       // outer iterations repeat until nothing improves, so no move is lost, it is only made at a cheaper level).
       // (first outer iteration only: the later ones polish, and a level of theirs moves few vertices anyway)
       // The other half of the rule: the move counts of a level fall geometrically while vertices settle (749k, 178k,
@@ -2887,7 +2833,7 @@ static int local_moving(LeidenCtx& cx, const LevelGraph& g, int* total_moves) {
       // coalesce one boundary vertex at a time -- exactly the work that is cheaper one level up.  A sweep that does not
       // move at least a tenth fewer vertices than the one before it ends the level (first outer iteration only).
       if (cx.iter == 0 && sweep >= 2) {
-        if ((long long)moved_last * 1000 < (long long)g.n * (n_cls_level < DEF_CLASSES ? cx.lm_stop_permille_big : cx.lm_stop_permille)) break;
+        if ((long long)moved_last * 1000 < (long long)g.n * (n_cls < DEF_CLASSES ? LM_STOP_PERMILLE_BIG : LM_STOP_PERMILLE)) break;
         if (sweep >= 3 && (long long)moved_last * 10 > (long long)moved_prev2 * 9) break;
       }
       moved_prev2 = moved_last;
@@ -2945,7 +2891,7 @@ static int local_moving(LeidenCtx& cx, const LevelGraph& g, int* total_moves) {
       hipLaunchKernelGGL(ld_apply_kernel, GRID1(cnt), 0, cx.s, cnt, list, tg, g.k, b.comm, b.Ktot, b.csize, b.flag,
                          b.counters);
       SCAMD_LAUNCH_CHECK();
-      if (i + 1 < ncl && !cx.no_fuse) {
+      if (i + 1 < ncl) {
         const int cn = cls[i + 1];
         const MoveArgs ma = move_args(cn, tgt[(i + 1) & 1]);
         const int nb_rq = ceil_div(cnt, 256);
@@ -2963,23 +2909,6 @@ static int local_moving(LeidenCtx& cx, const LevelGraph& g, int* total_moves) {
       } else {
         hipLaunchKernelGGL(ld_requeue_kernel, GRID1(cnt), 0, cx.s, cnt, list, tg, g.indptr, g.indices, b.comm, b.flag);
         SCAMD_LAUNCH_CHECK();
-        if (i + 1 < ncl) {  // (SCAMD_LEIDEN_FUSE=0: the next sub-round's decisions as a launch of their own)
-          const MoveArgs ma = move_args(cls[i + 1], tgt[(i + 1) & 1]);
-          const unsigned nbm = (unsigned)move_blocks(hc[cls[i + 1]]);
-          if (lanes == 32)
-            hipLaunchKernelGGL(ld_move_kernel<32>, dim3(nbm), dim3(256), 0, cx.s, ma.n_act, ma.list, ma.sub_list, ma.sub_count,
-                               ma.indptr, ma.indices, ma.wq, ma.k, ma.comm, ma.Ktot, ma.csize, ma.g, ma.round, ma.seed, ma.decision,
-                               ma.ovf_list, ma.hub_list, ma.counters);
-          else if (lanes == 16)
-            hipLaunchKernelGGL(ld_move_kernel<16>, dim3(nbm), dim3(256), 0, cx.s, ma.n_act, ma.list, ma.sub_list, ma.sub_count,
-                               ma.indptr, ma.indices, ma.wq, ma.k, ma.comm, ma.Ktot, ma.csize, ma.g, ma.round, ma.seed, ma.decision,
-                               ma.ovf_list, ma.hub_list, ma.counters);
-          else
-            hipLaunchKernelGGL(ld_move_kernel<64>, dim3(nbm), dim3(256), 0, cx.s, ma.n_act, ma.list, ma.sub_list, ma.sub_count,
-                               ma.indptr, ma.indices, ma.wq, ma.k, ma.comm, ma.Ktot, ma.csize, ma.g, ma.round, ma.seed, ma.decision,
-                               ma.ovf_list, ma.hub_list, ma.counters);
-          SCAMD_LAUNCH_CHECK();
-        }
       }
     }
   }
@@ -3147,7 +3076,7 @@ static int refinement(LeidenCtx& cx, const LevelGraph& g, int* n_merged) {
   else
     hipLaunchKernelGGL(ld_within_kernel<64>, GRIDW(g.n), 0, cx.s, g.n, g.indptr, g.indices, g.wq, b.comm, b.a_in);
   SCAMD_LAUNCH_CHECK();
-  const int n_cls = rf_classes(cx, g.n);
+  const int n_cls = rf_classes(g.n);
   int* rc0 = b.rcounters;  // [0, MAX_CLASSES): class list lengths; then per sub-round c: [0] joiners, [4] hubs, [5] overflow
   // (also clears rc0, the phase counters and the join stamps b.touched: three memsets until round 6)
   hipLaunchKernelGGL(ld_refine_init_kernel, GRID1(g.n), 0, cx.s, g.n, g.k, b.a_in, b.comm, b.ref, b.refsize, b.Kref,
@@ -3276,13 +3205,13 @@ static int aggregate(LeidenCtx& cx, const LevelGraph& g, int n_orig, int dst, Le
     fprintf(stderr, "[leiden] aggregate n=%d -> %d: %d rows through the workgroup tier, %d through the 8192-slot tier\n", g.n, inn,
             htier[0], htier[1]);
   if (htier[0] > 0) {
-    hipLaunchKernelGGL((ld_agg_block_kernel<AGG_MID_SLOTS, 512>), dim3((unsigned)std::min(cx.agg_mid_grid, htier[0])), dim3(512),
+    hipLaunchKernelGGL((ld_agg_block_kernel<AGG_MID_SLOTS, 512>), dim3((unsigned)std::min(AGG_MID_GRID, htier[0])), dim3(512),
                        (size_t)AGG_MID_SLOTS * 12, cx.s, b.mid_list, b.counters + 4, inn, b.moff, b.eoff, b.members, g.indptr,
                        g.indices, g.wq, b.cid, b.agg_col, b.agg_w, b.rowcnt, b.counters + 7, AGG_MID_MAX, cx.hub_try_probes);
     SCAMD_LAUNCH_CHECK();
   }
   if (htier[1] > 0) {
-    hipLaunchKernelGGL((ld_agg_block_kernel<BHUB_SLOTS, 1024>), dim3((unsigned)std::min(cx.agg_big_grid, htier[1])), dim3(1024),
+    hipLaunchKernelGGL((ld_agg_block_kernel<BHUB_SLOTS, 1024>), dim3((unsigned)std::min(HUB_GRID, htier[1])), dim3(1024),
                        HUB_LDS, cx.s, b.big_list, b.counters + 5, inn, b.moff, b.eoff, b.members, g.indptr, g.indices, g.wq,
                        b.cid, b.agg_col, b.agg_w, b.rowcnt, b.counters + 7, cx.agg_pass_keys, cx.hub_try_probes);
     SCAMD_LAUNCH_CHECK();
@@ -3296,7 +3225,7 @@ static int aggregate(LeidenCtx& cx, const LevelGraph& g, int n_orig, int dst, Le
                        b.pmoff, b.part_list, b.rlist, b.touched);
     SCAMD_LAUNCH_CHECK();
     const int64_t parts_bound = (int64_t)htier[2] + g.nnz / chunk + 1;
-    hipLaunchKernelGGL((ld_agg_block_kernel<BHUB_SLOTS, 1024>), dim3((unsigned)std::min<int64_t>(cx.agg_big_grid, parts_bound)), dim3(1024),
+    hipLaunchKernelGGL((ld_agg_block_kernel<BHUB_SLOTS, 1024>), dim3((unsigned)std::min<int64_t>(HUB_GRID, parts_bound)), dim3(1024),
                        HUB_LDS, cx.s, (const int*)b.part_list, (const int*)(b.counters + 3), inn, (const int64_t*)b.pmoff, b.eoff,
                        b.members, g.indptr, g.indices, g.wq, b.cid, b.agg_col, b.agg_w, b.part_cnt, b.counters + 7,
                        cx.agg_pass_keys, cx.hub_try_probes);
@@ -3373,8 +3302,8 @@ static int small_levels(LeidenCtx& cx, const LevelGraph& g, int level) {
   a.inv_beta = cx.inv_beta;
   a.seed = cx.seed;
   a.iter = cx.iter;
-  a.lm_stop_permille = cx.lm_stop_permille;
-  a.seq_n = cx.small_seq_n;
+  a.lm_stop_permille = LM_STOP_PERMILLE;
+  a.seq_n = SMALL_SEQ_N;
   a.info = b.counters + 12;
   hipLaunchKernelGGL(ld_small_levels_kernel, dim3(1), dim3(SM_THREADS), sizeof(SmallLds), cx.s, a);
   SCAMD_LAUNCH_CHECK();
@@ -3612,27 +3541,18 @@ static int leiden_run(const int64_t* indptr, const int32_t* indices, const float
   cx.gamma = resolution;
   cx.inv_beta = beta > 0.0 ? 1.0 / (beta * WSCALE) : 0.0;  // beta <= 0: the greedy limit (largest gain, no "stay")
   cx.seed = (unsigned int)(seed ^ (seed >> 32)) * 0x9E3779B1u + 0x632BE5ABu;
-  if (const char* e = getenv("SCAMD_LEIDEN_LM_STOP_PERMILLE")) cx.lm_stop_permille = cx.lm_stop_permille_big = atoi(e);
-  cx.lm_classes = classes_env("SCAMD_LEIDEN_LM_CLASSES");
-  cx.rf_classes = classes_env("SCAMD_LEIDEN_RF_CLASSES");
   if (const char* e = getenv("SCAMD_LEIDEN_SMALL")) cx.small_levels = e[0] != '0';
-  if (const char* e = getenv("SCAMD_LEIDEN_FUSE")) cx.no_fuse = e[0] == '0';
   if (const char* e = getenv("SCAMD_LEIDEN_POLISH")) cx.polish = e[0] != '0';
   cx.cpm = objective == 1;
   cx.node_weights = node_weights;
   if (cx.cpm) cx.small_levels = false;  // (ld_small_levels_kernel derives its coarse vertex weights from row sums: strengths)
   for (int i = 0; i < LD_NSTATS; ++i) g_ld_stats[i] = 0;
   g_ld_sweep_bytes = 0.0;
-  if (const char* e = getenv("SCAMD_LEIDEN_SMALL_SEQ")) cx.small_seq_n = atoi(e);
   if (const char* e = getenv("SCAMD_LEIDEN_AGG_WAVE_MAX")) cx.agg_wave_max = std::min(atoi(e), (int)WH_MAX_DEG);
   if (const char* e = getenv("SCAMD_LEIDEN_AGG_MID_MAX")) cx.agg_mid_max = std::min(atoi(e), (int)AGG_MID_MAX);
   if (const char* e = getenv("SCAMD_LEIDEN_HUB_TRY_PROBES")) cx.hub_try_probes = std::max(0, atoi(e));
-  if (const char* e = getenv("SCAMD_LEIDEN_SMALL_SWEEP_ACT")) cx.small_sweep_act = std::max(0, atoi(e));
-  if (const char* e = getenv("SCAMD_LEIDEN_SMALL_SWEEP_CLASSES")) cx.small_sweep_classes = std::max(1, std::min(atoi(e), (int)MAX_CLASSES));
   if (const char* e = getenv("SCAMD_LEIDEN_AGG_WAVE_WORK")) cx.agg_wave_work = std::max(1, atoi(e));
   if (const char* e = getenv("SCAMD_LEIDEN_AGG_MID_WORK")) cx.agg_mid_work = std::max(1, atoi(e));
-  if (const char* e = getenv("SCAMD_LEIDEN_AGG_MID_GRID")) cx.agg_mid_grid = std::max(1, atoi(e));
-  if (const char* e = getenv("SCAMD_LEIDEN_AGG_BIG_GRID")) cx.agg_big_grid = std::max(1, atoi(e));
   if (const char* e = getenv("SCAMD_LEIDEN_AGG_PASS_KEYS"))
     cx.agg_pass_keys = std::max(16, std::min(atoi(e), (int)AGG_BIG_PASS));
   Workspace ws(workspace, workspace_bytes);

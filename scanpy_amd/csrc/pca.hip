@@ -530,11 +530,7 @@ extern "C" int scamd_spmm_csr_f32(const int64_t* indptr, const int32_t* indices,
                 (long long)n, (long long)g, l);
   if (n == 0) return SCAMD_OK;
   const int blocks = (int)std::min<int64_t>((n + 3) / 4, 256 * 32);
-  static const bool quad = [] {  // (A/B knob: SCAMD_SPMM_QUAD=0 runs the one-entry-per-load kernel)
-    const char* e = getenv("SCAMD_SPMM_QUAD");
-    return !(e && e[0] == '0');
-  }();
-  if (l <= 64 && l >= 4 && quad)
+  if (l <= 64 && l >= 4)
     hipLaunchKernelGGL(spmm_rows_quad_f32_kernel, dim3(blocks), dim3(256), 0, stream, indptr, indices, data, n, b, l, shift, y);
   else if (l <= 64)
     hipLaunchKernelGGL(spmm_rows_f32_kernel<1>, dim3(blocks), dim3(256), 0, stream, indptr, indices, data, n, b, l,

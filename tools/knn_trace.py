@@ -39,16 +39,10 @@ def main():
     backend = GpuBackend()
     res = pca_fit(backend.upload(x), 50, backend=backend)
     emb = res.scores
-    no_insert = os.environ.pop("SCAMD_KNN_DEBUG_NO_INSERT", None)  # (only the traced call runs in the debug mode)
     K.knn(emb, 15)
     path = "/tmp/knn_trace.bin"
     os.environ["SCAMD_KNN_TRACE"] = path
-    if no_insert:
-        os.environ["SCAMD_KNN_DEBUG_NO_INSERT"] = no_insert
-    try:
-        K.knn(emb, 15)
-    except _lib.ScamdError as e:  # SCAMD_KNN_DEBUG_NO_INSERT=1: the lists are empty, the float64 scan overflows
-        print("knn raised (expected in the no-insert debug mode):", str(e)[:120])
+    K.knn(emb, 15)
     os.environ.pop("SCAMD_KNN_TRACE")
     lib = _lib.load()
     sel_ms, pairs = float(lib.scamd_knn_last_select_ms()), float(lib.scamd_knn_last_select_pairs())

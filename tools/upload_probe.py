@@ -1,4 +1,4 @@
-import sys, time, os
+import sys, time
 sys.path.insert(0,'/root/repo')
 import torch, numpy as np
 import bench
@@ -9,4 +9,4 @@ for _ in range(2): h=be.upload(x); torch.cuda.synchronize()
 best=1e9
 for _ in range(5):
     t0=time.perf_counter(); h=be.upload(x); torch.cuda.synchronize(); best=min(best,time.perf_counter()-t0)
-print("threads", os.environ.get("SCAMD_UPLOAD_THREADS","8"), "piece", os.environ.get("SCAMD_UPLOAD_PIECE_MB","32"), f"upload {best*1e3:.1f} ms = {x.data.nbytes*2/best/1e9:.1f} GB/s", flush=True)
+print(f"upload {best*1e3:.1f} ms = {x.data.nbytes*2/best/1e9:.1f} GB/s", flush=True)
