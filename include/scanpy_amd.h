@@ -65,6 +65,7 @@ int scamd_device_count(void);
  * Exactness: pass 1 (FP32 MFMA, ||c||^2 - 2 q.c) keeps KP > k candidates per query; pass 2 re-ranks
  * them in float64; a query is accepted only if its k-th exact distance is provably below every
  * rejected candidate given the float32 rounding bound, otherwise pass 3 rescans it in float64.
+ * Ties, however many rows share the k-th distance, are broken by the lower row index in every pass.
  * ---------------------------------------------------------------------------------------- */
 size_t scamd_knn_workspace_bytes(int64_t n, int d, int64_t n_query, int k);
 int scamd_knn_l2_f32(const float* x, int64_t n, int d, int64_t ld_x,

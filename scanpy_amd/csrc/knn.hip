@@ -1768,16 +1768,18 @@ static size_t rerank_rows_lds_bytes(int d, int n_rank) {
 
 // ------------------------------------------------------------------------------------------------
 // pass 3: float64 scan for uncertified queries, two kernels.
-//   scan: grid (row chunks, queries): every block scans one chunk of the rows and appends each row whose exact d^2
-//         is <= bound (the k-th exact distance among the candidates, an upper bound of the true k-th distance)
-//         to the query's collection (one global counter per query; order irrelevant, the rank step sorts);
-//   rank: one block per query rank-sorts the collection by (distance, index) and writes the k-1 best.
+//   scan: grid (row chunks, queries): every block scans one chunk of the rows and appends each row whose key
+//         (exact d^2, row index) is <= the query's bound key to the query's collection (one global counter per query;
+//         order irrelevant, the rank step sorts).  The bound starts as (the k-th exact distance among the candidates,
+//         no index bound): an upper bound of the true k-th key;
+//   rank: one block per query rank-sorts the collection by (distance, index) and writes the k-1 best -- or, when the
+//         collection overflowed, tightens the bound key for another scan.
 // ------------------------------------------------------------------------------------------------
 constexpr int FALLBACK_ROW_CHUNKS = 128;
 
 __global__ __launch_bounds__(256) void knn_fallback_scan_kernel(
     const float* __restrict__ x, int64_t n, int d, int64_t ld, int64_t q_begin,
-    const int* __restrict__ flag_list, int flag_begin, const double* __restrict__ kth_d2,
+    const int* __restrict__ flag_list, int flag_begin, const double* __restrict__ kth_d2, const int* __restrict__ kth_idx,
     double* __restrict__ scratch_d, int* __restrict__ scratch_i, int* __restrict__ counts) {
   __shared__ float qs[KNN_MAX_D];
   const int fb = blockIdx.y;
@@ -1788,6 +1790,7 @@ __global__ __launch_bounds__(256) void knn_fallback_scan_kernel(
   for (int c = threadIdx.x; c < d; c += blockDim.x) qs[c] = x[q * ld + c];
   __syncthreads();
   const double bound = kth_d2[qi];
+  const unsigned int ibound = (unsigned int)kth_idx[qi];  // (-1 = no index bound)
   const int64_t rows_per_chunk = (n + gridDim.x - 1) / gridDim.x;
   const int64_t r0 = (int64_t)blockIdx.x * rows_per_chunk, r1 = std::min<int64_t>(n, r0 + rows_per_chunk);
   for (int64_t r = r0 + threadIdx.x; r < r1; r += blockDim.x) {
@@ -1798,7 +1801,7 @@ __global__ __launch_bounds__(256) void knn_fallback_scan_kernel(
       double df = (double)qs[c] - (double)cp[c];
       s = fma(df, df, s);
     }
-    if (s <= bound) {
+    if (s < bound || (s == bound && (unsigned int)r <= ibound)) {
       int slot = atomicAdd(&counts[fb], 1);
       if (slot < FALLBACK_CAP) {
         bd[slot] = s;
@@ -1814,8 +1817,9 @@ __global__ __launch_bounds__(256) void knn_fallback_scan_kernel(
 // with ~2.5 % of the rows in reach it is noise again.  grid (cell chunks, queries).
 __global__ __launch_bounds__(256) void knn_fallback_scan_cells_kernel(
     const float* __restrict__ x, int d, int64_t ld, int64_t q_begin, const int* __restrict__ flag_list, int flag_begin,
-    const double* __restrict__ kth_d2, double* __restrict__ scratch_d, int* __restrict__ scratch_i, int* __restrict__ counts,
-    const float* __restrict__ cent, const float* __restrict__ radius, const int* __restrict__ cell_tile0,
+    const double* __restrict__ kth_d2, const int* __restrict__ kth_idx, double* __restrict__ scratch_d,
+    int* __restrict__ scratch_i, int* __restrict__ counts, const float* __restrict__ cent,
+    const float* __restrict__ radius, const int* __restrict__ cell_tile0,
     const int* __restrict__ cell_ntiles, const int* __restrict__ perm, int n_cells) {
   __shared__ float qs[KNN_MAX_D];
   const int fb = blockIdx.y;
@@ -1826,6 +1830,7 @@ __global__ __launch_bounds__(256) void knn_fallback_scan_cells_kernel(
   for (int c = threadIdx.x; c < d; c += blockDim.x) qs[c] = x[q * ld + c];
   __syncthreads();
   const double bound = kth_d2[qi];
+  const unsigned int ibound = (unsigned int)kth_idx[qi];  // (-1 = no index bound)
   const int per = (n_cells + gridDim.x - 1) / gridDim.x;
   const int c0 = blockIdx.x * per, c1 = min(n_cells, c0 + per);
   for (int c = c0; c < c1; ++c) {
@@ -1861,7 +1866,7 @@ __global__ __launch_bounds__(256) void knn_fallback_scan_cells_kernel(
         const double df = (double)qs[t] - (double)cp[t];
         s = fma(df, df, s);
       }
-      if (s <= bound) {
+      if (s < bound || (s == bound && (unsigned int)orig <= ibound)) {
         const int slot = atomicAdd(&counts[fb], 1);
         if (slot < FALLBACK_CAP) {
           bd[slot] = s;
@@ -1875,27 +1880,39 @@ __global__ __launch_bounds__(256) void knn_fallback_scan_cells_kernel(
 __global__ __launch_bounds__(256) void knn_fallback_rank_kernel(
     int k, const int* __restrict__ flag_list, int flag_begin, const double* __restrict__ scratch_d,
     const int* __restrict__ scratch_i, const int* __restrict__ counts, int32_t* __restrict__ out_idx,
-    double* __restrict__ out_dist, double* __restrict__ kth_d2, int* __restrict__ retry_list, int* __restrict__ n_retry) {
+    double* __restrict__ out_dist, double* __restrict__ kth_d2, int* __restrict__ kth_idx, int* __restrict__ retry_list,
+    int* __restrict__ n_retry, int* __restrict__ n_stuck) {
   const int fb = blockIdx.x;
   const int64_t qi = flag_list[flag_begin + fb];
   const double* bd = scratch_d + (int64_t)fb * FALLBACK_CAP;
   const int* bi = scratch_i + (int64_t)fb * FALLBACK_CAP;
   int m = counts[fb];
   // More rows within the bound than the table holds: the bound came from a list the scoring engine could not order
-  // (norms far larger than the neighbour distances: clusters at +-3000 with unit spread -- tests/test_gpu_knn_certificate.py).
-  // The k-1 smallest of ANY FALLBACK_CAP rows bound the true (k-1)-th distance from above: tighten the bound to that and scan
-  // again (each round keeps about (k - 1) / FALLBACK_CAP of the rows; only more than FALLBACK_CAP rows tied AT the k-th
-  // distance cannot be resolved, which the host reports after a few rounds).
-  const bool overflow = m > FALLBACK_CAP;
-  if (overflow) m = FALLBACK_CAP;
+  // (norms far larger than the neighbour distances: clusters at +-3000 with unit spread -- tests/test_gpu_knn_certificate.py),
+  // or more than FALLBACK_CAP rows are tied at the k-th distance (thousands of identical rows).  The bound is a KEY
+  // (distance, row index) in the order of key_less, as everything the search returns.  The k-1 smallest keys of ANY
+  // FALLBACK_CAP collected rows bound the true (k-1)-th key from above: tighten the bound to that and scan again.  Which rows
+  // won the race for the table decides only how fast the bound falls, never where it ends: a round drops at least the
+  // FALLBACK_CAP - (k - 1) collected rows above the new bound (about (k - 1) / FALLBACK_CAP of all rows survive when the
+  // table is a fair sample), the last round collects all rows within the bound and writes the k-1 smallest keys -- among
+  // tied rows those of lowest index.  The new bound is strictly smaller than the old one by construction; n_stuck counts
+  // the queries for which it is not, and the host stops there instead of scanning for ever.
   const int kk = k - 1;
+  const bool overflow = m > FALLBACK_CAP && kk > 0;  // (k = 1: nothing but the self column to write)
+  if (m > FALLBACK_CAP) m = FALLBACK_CAP;
   for (int u = threadIdx.x; u < m; u += blockDim.x) {
     double du = bd[u];
     int iu = bi[u];
     int rank = 0;
     for (int v = 0; v < m; ++v) rank += key_less(bd[v], bi[v], du, iu) ? 1 : 0;
     if (overflow) {
-      if (rank == kk - 1) kth_d2[qi] = du;
+      if (rank == kk - 1) {
+        const double old_d = kth_d2[qi];
+        const unsigned int old_i = (unsigned int)kth_idx[qi];
+        if (!(du < old_d || (du == old_d && (unsigned int)iu < old_i))) atomicAdd(n_stuck, 1);
+        kth_d2[qi] = du;
+        kth_idx[qi] = iu;
+      }
     } else if (rank < kk) {
       out_idx[qi * k + 1 + rank] = iu;
       out_dist[qi * k + 1 + rank] = sqrt(du);
@@ -2419,6 +2436,7 @@ struct KnnBuffers {
   float* xp; float* cn; float* mu; double* mean_partial; unsigned int* cmax; int* cand_idx; float* cand_tau; double* kth_d2;
   int* flag_list; int* counters; double* scratch_d; int* scratch_i; int* fb_counts;
   int* fb_retry[2];  // queries whose float64 scan overflowed its table: scanned again with a tighter bound
+  int* kth_idx;      // [n_query] row-index part of the float64 scan's bound key (-1 = none), set once a query is scanned
   // cell-pruned search
   int* labels; int* perm; int* qpos; int* block_cell; float* cent; float* centp; long long* sums; int* cell_ints;
   unsigned int* radius_bits; int* cell_order; float* cell_lb2; int* cell_aux; int* block_perm;
@@ -2437,12 +2455,13 @@ static void knn_carve(Workspace& ws, const KnnPlan& p, int64_t n_query, KnnBuffe
   b->cand_tau = ws.take<float>((size_t)p.nq_pad);
   b->kth_d2 = ws.take<double>((size_t)n_query);
   b->flag_list = ws.take<int>((size_t)n_query);
-  b->counters = ws.take<int>(16);  // [0] uncertified, [1] overflow, [2..3] swept pairs, [4..5] pre-pass pairs (u64), [6] launch-order error, [8..15] XCD queue positions
+  b->counters = ws.take<int>(16);  // [0] uncertified, [1] overflow, [2..3] swept pairs, [4..5] pre-pass pairs (u64), [6] launch-order error, [7] float64 scans without progress, [8..15] XCD queue positions
   b->scratch_d = ws.take<double>((size_t)FALLBACK_CHUNK * FALLBACK_CAP);
   b->scratch_i = ws.take<int>((size_t)FALLBACK_CHUNK * FALLBACK_CAP);
   b->fb_counts = ws.take<int>((size_t)FALLBACK_CHUNK);
   b->fb_retry[0] = ws.take<int>((size_t)n_query);
   b->fb_retry[1] = ws.take<int>((size_t)n_query);
+  b->kth_idx = ws.take<int>((size_t)n_query);
   b->labels = b->perm = b->qpos = b->block_cell = b->cell_ints = nullptr;
   b->cent = b->centp = nullptr;
   b->sums = nullptr;
@@ -3019,7 +3038,8 @@ extern "C" int scamd_knn_l2_ivf_f32(const float* x, int64_t n, int d, int64_t ld
 static int knn_l2_impl(const float* x, int64_t n, int d, int64_t ld_x, int64_t q_begin, int64_t n_query, int k,
                        int32_t* out_idx, double* out_dist, double cert_scale, int64_t* n_fallback_host, void* workspace,
                        size_t workspace_bytes, scamd_stream_t stream, int nprobe) {
-  SCAMD_REQUIRE(x && out_idx && out_dist, SCAMD_EINVAL, "knn: null pointer");
+  // (an empty query range has empty outputs: an allocator may hand out null for them)
+  SCAMD_REQUIRE(x && ((out_idx && out_dist) || n_query == 0), SCAMD_EINVAL, "knn: null pointer");
   SCAMD_REQUIRE(n >= 1 && d >= 1 && ld_x >= d, SCAMD_EINVAL, "knn: bad shape n=%lld d=%d ld=%lld",
                 (long long)n, d, (long long)ld_x);
   SCAMD_REQUIRE(n < (int64_t)1 << 31, SCAMD_EUNSUPPORTED, "knn: n=%lld exceeds int32 row ids", (long long)n);
@@ -3139,9 +3159,8 @@ static int knn_l2_impl(const float* x, int64_t n, int d, int64_t ld_x, int64_t q
   // float64 scan of what is left; a query whose table overflowed comes back with a tighter bound (knn_fallback_rank_kernel)
   int n_todo = n_flag;
   const int* todo = flag_list;
+  if (n_todo > 0) SCAMD_HIP_CHECK(hipMemsetAsync(b.kth_idx, 0xff, sizeof(int) * (size_t)n_query, s));
   for (int round = 0; n_todo > 0; ++round) {
-    SCAMD_REQUIRE(round < 8, SCAMD_EUNSUPPORTED, "knn: %d queries have more than %d rows tied within their k-th distance",
-                  n_todo, FALLBACK_CAP);
     int* retry = b.fb_retry[round & 1];
     SCAMD_HIP_CHECK(hipMemsetAsync(b.counters + 1, 0, sizeof(int), s));
     for (int begin = 0; begin < n_todo; begin += FALLBACK_CHUNK) {
@@ -3152,20 +3171,25 @@ static int knn_l2_impl(const float* x, int64_t n, int d, int64_t ld_x, int64_t q
         const int nc = p.n_cells;
         // (few queries: one workgroup per cell and query -- a launch lasts as long as its busiest workgroup)
         hipLaunchKernelGGL(knn_fallback_scan_cells_kernel, dim3(count <= 128 ? nc : std::min(nc, 64), count), dim3(256), 0, s, x, d, ld_x, q_begin,
-                           todo, begin, b.kth_d2, b.scratch_d, b.scratch_i, b.fb_counts, b.cent,
+                           todo, begin, b.kth_d2, b.kth_idx, b.scratch_d, b.scratch_i, b.fb_counts, b.cent,
                            reinterpret_cast<const float*>(b.radius_bits), b.cell_ints + 7 * nc,
                            reinterpret_cast<const int*>(b.sums), b.perm, nc);
       } else {
         const int chunks = (int)std::max<int64_t>(1, std::min<int64_t>(FALLBACK_ROW_CHUNKS, n / 2048));
         hipLaunchKernelGGL(knn_fallback_scan_kernel, dim3(chunks, count), dim3(256), 0, s, x, n, d, ld_x, q_begin,
-                           todo, begin, b.kth_d2, b.scratch_d, b.scratch_i, b.fb_counts);
+                           todo, begin, b.kth_d2, b.kth_idx, b.scratch_d, b.scratch_i, b.fb_counts);
       }
       SCAMD_LAUNCH_CHECK();
       hipLaunchKernelGGL(knn_fallback_rank_kernel, dim3(count), dim3(256), 0, s, k, todo, begin, b.scratch_d,
-                         b.scratch_i, b.fb_counts, out_idx, out_dist, b.kth_d2, retry, b.counters + 1);
+                         b.scratch_i, b.fb_counts, out_idx, out_dist, b.kth_d2, b.kth_idx, retry, b.counters + 1,
+                         b.counters + 7);
       SCAMD_LAUNCH_CHECK();
     }
-    SCAMD_READBACK_NOW(h_counters, b.counters, 16, s);
+    SCAMD_READBACK_NOW(h_counters, b.counters, 32, s);
+    // every round lowers the bound key of every query it sends back (knn_fallback_rank_kernel), so the loop ends; a round
+    // that did not is a defect and is reported at once instead of being repeated
+    SCAMD_REQUIRE(h_counters[7] == 0, SCAMD_EINTERNAL, "knn: float64 scan round %d made no progress on %d of %d queries",
+                  round, h_counters[7], n_todo);
     n_todo = h_counters[1];
     todo = retry;
   }

@@ -109,18 +109,20 @@ def leiden(lib, adj, *, resolution=1.0, n_iterations=-1, beta=0.01, seed=0, init
     return memb, float(q.value), int(nc.value)
 
 
-def knn(lib, x, k, *, q_begin=0, n_query=None, cert_scale=1.0, nprobe=0):
+def knn(lib, x, k, *, q_begin=0, n_query=None, cert_scale=1.0, nprobe=0, d=None):
+    """d: the first d columns of the [n, ld_x] buffer x are the data, the rest is padding the library must not read"""
     x = np.ascontiguousarray(x, dtype=np.float32)
-    n, d = x.shape
+    n, ld = x.shape
+    d = ld if d is None else d
     nq = n if n_query is None else n_query
     idx = np.empty((nq, k), dtype=np.int32)
     dist = np.empty((nq, k), dtype=np.float64)
     ws = _ws(lib.scamd_knn_workspace_bytes(n, d, nq, k))
     nfb = C.c_int64(0)
     if nprobe:
-        rc = lib.scamd_knn_l2_ivf_f32(_p(x), n, d, d, q_begin, nq, k, int(nprobe), _p(idx), _p(dist), C.byref(nfb), _p(ws), ws.size, None)
+        rc = lib.scamd_knn_l2_ivf_f32(_p(x), n, d, ld, q_begin, nq, k, int(nprobe), _p(idx), _p(dist), C.byref(nfb), _p(ws), ws.size, None)
     else:
-        rc = lib.scamd_knn_l2_f32(_p(x), n, d, d, q_begin, nq, k, _p(idx), _p(dist), float(cert_scale), C.byref(nfb), _p(ws), ws.size, None)
+        rc = lib.scamd_knn_l2_f32(_p(x), n, d, ld, q_begin, nq, k, _p(idx), _p(dist), float(cert_scale), C.byref(nfb), _p(ws), ws.size, None)
     _check(lib, rc, "knn")
     return idx, dist, int(nfb.value)
 

@@ -560,3 +560,150 @@ def test_front_ends_and_widening_kernels_on_the_emulator(emu):
     assert out.returncode == 0, tail
     m = re.search(r"(\d+) passed", tail)
     assert m and int(m.group(1)) >= 42, tail
+
+
+# ---------------------------------------------------------------------------------------------------------------------
+# The shape tables of tests/test_gpu_knn_shapes.py at emulator sizes (tables and checker: tests/knn_shape_cases.py).  The
+# emulator says nothing about LDS limits, occupancy or the hardware's accumulation order; it does say whether every
+# instantiation indexes, pads and merges correctly, and it counts cross-lane operations of partial waves.
+# ---------------------------------------------------------------------------------------------------------------------
+def _no_partial_wave_collectives(H, lib):
+    st = H.stats(lib)
+    assert st["partial_collectives"] == st["mixed_collectives"] == st["reads_of_inactive_lanes"] == 0, st
+
+
+def _emu_ran(lib, d, k, n_query, n, *, pruned, b3_env=None, expect_pruning=True):
+    import knn_shape_cases as S
+
+    assert lib.scamd_knn_last_select_engine() == S.expected_engine(d, k, b3_env)
+    pairs, pre = lib.scamd_knn_last_select_pairs(), lib.scamd_knn_last_select_prepass_pairs()
+    if not pruned:
+        assert pairs == float(n_query) * float(n) and pre == 0.0, (pairs, pre)
+    else:
+        assert pre > 0.0, "the call did not take the cell-pruned sweep"
+        assert not expect_pruning or pairs < float(n_query) * float(n), (pairs, n_query * n)
+
+
+def test_knn_shape_tables_cover_every_instantiation():
+    """no GPU, no emulator: every (H, KP) of the LDS-list kernel and every H of the register-list kernel x {brute force,
+    pruned} that the restated knn_plan() can produce has a case in the tables or in test_knn_vs_sklearn's list"""
+    import knn_shape_cases as S
+    import test_gpu_kernels
+
+    lds, reg = S.assert_every_instantiation_has_a_case(test_gpu_kernels.test_knn_vs_sklearn.pytestmark[0].args[1])
+    assert len(lds) == 18 and reg == [8, 16, 25, 32]
+
+
+def _lds_and_boundary_cases():
+    import knn_shape_cases as S
+
+    return sorted(S.LDS_LIST_CASES) + [c for c in S.BOUNDARY_CASES if c[0] != 256]  # (d = 256: test_knn_wide_rows_and_long_lists)
+
+
+@pytest.mark.parametrize(("d", "k"), _lds_and_boundary_cases())
+def test_knn_every_lds_list_instantiation_and_plan_boundary(emu, d, k):
+    import knn_shape_cases as S
+
+    H, lib = emu
+    n = 700
+    x = S.clustered(n, d, 1000 * d + k)
+    lib.emu_reset_stats()
+    idx, dist, n_scan = H.knn(lib, x, k)
+    _emu_ran(lib, d, k, n, n, pruned=False)
+    S.check_against_f64(x, k, np.arange(n), idx, dist, n_fallback=n_scan, label=f"emu d={d} k={k}")
+    # the float64 scan repairs whatever a select kernel gets wrong, so a wrong instantiation shows here and nowhere else.  The
+    # emulator's accumulation order is fixed: the bound of test_knn_wide_rows_and_long_lists holds on every machine (d <= 2:
+    # near-ties everywhere, a seventh of the queries is rescanned and rightly so)
+    assert d <= 2 or n_scan <= n // 10, n_scan
+    _no_partial_wave_collectives(H, lib)
+
+
+@pytest.mark.parametrize(("d", "k", "kind", "b3"), [(16, 2, "clustered", None), (8, 24, "clustered", None), (17, 2, "gaussian", None),
+                                                    (32, 24, "clustered", None), (33, 2, "clustered", None), (50, 24, "gaussian", None),
+                                                    (51, 2, "clustered", None), (64, 24, "clustered", None),
+                                                    (50, 24, "clustered", "0"), (40, 5, "clustered", "0")])
+def test_knn_pruned_sweep_off_k15(emu, monkeypatch, d, k, kind, b3):
+    """the cell-pruned sweep at every H with the smallest and the largest list threshold (k = 2: rank 8 / 10, k = 24: rank 30 /
+    the list's end), and the float32 engine's pruned H = 25 instantiation (SCAMD_KNN_B3=0); data without structure (every cell swept, slow
+    here) once per engine"""
+    import knn_shape_cases as S
+
+    H, lib = emu
+    monkeypatch.setenv("SCAMD_KNN_IVF", "1")
+    monkeypatch.setenv("SCAMD_KNN_CELL_ROWS", "512")
+    if b3 is not None:
+        monkeypatch.setenv("SCAMD_KNN_B3", b3)
+    n = 4300
+    x = S.clustered(n, d, 31 * d + k, S.PRUNED_SPREAD) if kind == "clustered" else S.gaussian(n, d, 31 * d + k)
+    lib.emu_reset_stats()
+    idx, dist, n_scan = H.knn(lib, x, k)
+    _emu_ran(lib, d, k, n, n, pruned=True, b3_env=b3, expect_pruning=kind == "clustered")
+    S.check_against_f64(x, k, np.arange(n), idx, dist, n_fallback=n_scan, label=f"emu pruned {kind} d={d} k={k} B3={b3}")
+    assert n_scan <= n // 10, n_scan  # (as above)
+    _no_partial_wave_collectives(H, lib)
+
+
+@pytest.mark.parametrize(("n", "d", "ivf"), [(700, 20, "0"), (700, 50, "0"), (700, 100, "0"), (4300, 50, "1")])
+def test_knn_row_stride(emu, monkeypatch, n, d, ivf):
+    """ld_x = d + 7 with NaN in the padding columns (any read of them poisons a distance or a norm): bitwise the
+    contiguous call"""
+    import knn_shape_cases as S
+
+    H, lib = emu
+    monkeypatch.setenv("SCAMD_KNN_IVF", ivf)
+    monkeypatch.setenv("SCAMD_KNN_CELL_ROWS", "512")
+    x = S.clustered(n, d, 9 * d, S.PRUNED_SPREAD)
+    i0, d0, _ = H.knn(lib, x, 15)
+    buf = np.full((n, d + 7), np.nan, dtype=np.float32)
+    buf[:, :d] = x
+    i1, d1, _ = H.knn(lib, buf, 15, d=d)
+    _emu_ran(lib, d, 15, n, n, pruned=ivf == "1")
+    assert np.array_equal(i0, i1) and np.array_equal(d0, d1)
+    S.check_against_f64(x, 15, np.arange(n), i0, d0, label=f"emu row stride d={d}")
+
+
+@pytest.mark.parametrize(("n", "d", "k", "ivf"), [(1500, 100, 15, "0"), (1500, 50, 30, "0"), (4300, 20, 15, "1")])
+def test_knn_duplicate_groups(emu, monkeypatch, n, d, k, ivf):
+    """groups of 10 .. 600 identical rows: self first, then the other members by row number (the share of rows using the
+    tie exemption is not bounded here: the ties are the data)"""
+    import knn_shape_cases as S
+
+    H, lib = emu
+    monkeypatch.setenv("SCAMD_KNN_IVF", ivf)
+    monkeypatch.setenv("SCAMD_KNN_CELL_ROWS", "512")
+    x, groups = S.with_duplicate_groups(S.clustered(n, d, 5 * d + k, S.PRUNED_SPREAD), S.DUPLICATE_GROUPS, seed=d)
+    lib.emu_reset_stats()
+    idx, dist, n_scan = H.knn(lib, x, k)
+    _emu_ran(lib, d, k, n, n, pruned=ivf == "1")
+    S.check_against_f64(x, k, np.arange(n), idx, dist, n_fallback=n_scan, tie_fraction=None, label=f"emu duplicates d={d} k={k}")
+    S.check_duplicate_groups(groups, k, idx, dist)
+    _no_partial_wave_collectives(H, lib)
+
+
+@pytest.mark.parametrize(("n", "d", "ivf"), [(2600, 20, "0"), (4300, 50, "1")])
+def test_knn_more_identical_rows_than_the_fallback_table_holds(emu, monkeypatch, n, d, ivf):
+    """2100 identical rows > FALLBACK_CAP: the float64 scan's bound is a (distance, index) key that keeps falling while the
+    table overflows (a distance bound alone stood still: the call gave up after eight rescans); the lists are the members
+    of lowest row number, the same on a second call.  Two query shards of 64 rows, four fifths of them members -- the rank
+    step is quadratic in the table and all 2100 members as queries take the emulator a minute and a half (the GPU suite
+    asks them all)"""
+    import knn_shape_cases as S
+
+    H, lib = emu
+    monkeypatch.setenv("SCAMD_KNN_IVF", ivf)
+    monkeypatch.setenv("SCAMD_KNN_CELL_ROWS", "512")
+    k = 15
+    x, groups = S.with_duplicate_groups(S.clustered(n, d, 3, S.PRUNED_SPREAD), (2100,), seed=4)
+    assert len(groups[0]) > S.FALLBACK_CAP
+    for qb in (0, n - 64):
+        rows = np.arange(qb, qb + 64)
+        assert np.isin(rows, groups[0]).sum() >= 32
+        lib.emu_reset_stats()
+        idx, dist, n_scan = H.knn(lib, x, k, q_begin=qb, n_query=64)
+        # (64 queries occupy whole blocks of 128 query slots: the pair count says nothing about pruning here)
+        _emu_ran(lib, d, k, 64, n, pruned=ivf == "1", expect_pruning=False)
+        S.check_against_f64(x, k, rows, idx, dist, n_fallback=n_scan, tie_fraction=None, label=f"emu 2100 identical rows, shard at {qb}")
+        S.check_duplicate_groups(groups, k, idx, dist, q_begin=qb)
+        _no_partial_wave_collectives(H, lib)
+        idx2, dist2, _ = H.knn(lib, x, k, q_begin=qb, n_query=64)
+        assert np.array_equal(idx, idx2) and np.array_equal(dist, dist2)
