@@ -22,6 +22,7 @@
 #include <algorithm>
 #include <cmath>
 #include <cstdlib>
+#include <memory>
 #include <type_traits>
 #include <vector>
 
@@ -2320,6 +2321,17 @@ __global__ void ivf_pack_image_kernel(const float* __restrict__ x, const float* 
 // ------------------------------------------------------------------------------------------------
 // host side
 // ------------------------------------------------------------------------------------------------
+// SCAMD_KNN_* switches, each read at the call that uses it: the tests flip them inside one process
+static int env_int(const char* name, int dflt, bool* is_set = nullptr) {
+  const char* e = getenv(name);
+  if (is_set) *is_set = e != nullptr;
+  return e ? atoi(e) : dflt;
+}
+static bool env_is(const char* name, char c) {  // the switch is set and starts with c ("0 turns off")
+  const char* e = getenv(name);
+  return e && e[0] == c;
+}
+
 struct KnnPlan {
   int H, TC, NW, KP;
   bool reg;       // register-list kernel (knn_select_reg_kernel) instead of the LDS-list kernel
@@ -2333,11 +2345,6 @@ struct KnnPlan {
   int n_cells;    // coarse cells
   int64_t n_img_max, n_slot_max;  // upper bounds of the padded image rows / query slots
 };
-
-template <int H>
-static void reg_plan(KnnPlan* p) {
-  p->row_dwords = RegCfg<H>::DPL;
-}
 
 static bool knn_plan(int64_t n, int d, int64_t n_query, int k, KnnPlan* p, int nprobe = 0) {
   p->nprobe = 0;
@@ -2360,53 +2367,35 @@ static bool knn_plan(int64_t n, int d, int64_t n_query, int k, KnnPlan* p, int n
     p->KP = std::max(p->KP, 128);
   }
   p->reg = (p->KP == 32 && p->H <= 32);
-  {
-    // k columns = self + k-1 others must be certified below the threshold: keep a margin of 6 ranks
-    static const int margin = [] {
-      const char* e = getenv("SCAMD_KNN_THR_MARGIN");
-      return e ? atoi(e) : 6;
-    }();
-    p->thr_rank = std::min(32, std::max(1, k + margin));
-    p->thr_margin_env = getenv("SCAMD_KNN_THR_MARGIN") != nullptr;
-  }
+  // k columns = self + k-1 others must be certified below the threshold: keep a margin of 6 ranks
+  const int margin = env_int("SCAMD_KNN_THR_MARGIN", 6, &p->thr_margin_env);
+  p->thr_rank = std::min(32, std::max(1, k + margin));
   p->row_dwords = 2 * p->H;
   if (p->reg) {
     p->NW = 4;
     p->TC = 128;
-    switch (p->H) {
-      case 8: reg_plan<8>(p); break;
-      case 16: reg_plan<16>(p); break;
-      case 25: reg_plan<25>(p); break;
-      default: reg_plan<32>(p); break;
-    }
+    p->row_dwords = p->H == 8 ? RegCfg<8>::DPL : p->H == 16 ? RegCfg<16>::DPL : p->H == 25 ? RegCfg<25>::DPL : RegCfg<32>::DPL;
   }
-  // 3 x bf16 engine: 32 < d <= 50 (the PCA embedding); SCAMD_KNN_B3=0 keeps the float32 MFMA engine (read per call)
-  p->b3 = false;
-  if (p->reg && p->H == 25) {
-    const char* e = getenv("SCAMD_KNN_B3");
-    p->b3 = !(e && e[0] == '0');
-    if (p->b3) {
-      p->row_dwords = B3_DPL;
-      // The engine's error bound is ~4x the float32 engine's (relative to ||q|| ||c||, which on clustered data is far
-      // larger than the neighbour distances): with the margin of 6 ranks, 508 queries of the planted 1M run failed the
-      // certificate under a bound that was still 2x too small, and the float64 scan of those cost 4.2 ms.  The failure
-      // probability falls like (bound / gap)^margin.  Measured with the correct bound, planted 1M: margin 8 -> select
-      // 16.5 ms + 200 fallbacks, 10 -> 17.0 ms + 5, 12 -> 18.0 ms + 1.  Round 4: the bound prices the norms a missed
-      // neighbour can have instead of the largest norm of the data set (knn_rerank_rows_kernel), which rejects fewer
-      // queries at every margin -- one box, planted 1M: margin 10 -> 16.97 ms + 1 float64 scan, 8 -> 16.30 ms + 58,
-      // 6 -> 15.89 ms + 1423 queries through the second tier (which costs what the margin saved), 4 -> 15.41 ms + 25764
-      // (profiles/r04e_knn_knobs.log): 8 ranks (threshold = the 23rd list entry at k = 15).
-      if (!p->thr_margin_env) p->thr_rank = std::min(32, std::max(1, k + 8));
-    }
+  // 3 x bf16 engine: 32 < d <= 50 (the PCA embedding); SCAMD_KNN_B3=0 keeps the float32 MFMA engine
+  p->b3 = p->reg && p->H == 25 && !env_is("SCAMD_KNN_B3", '0');
+  if (p->b3) {
+    p->row_dwords = B3_DPL;
+    // The engine's error bound is ~4x the float32 engine's (relative to ||q|| ||c||, which on clustered data is far
+    // larger than the neighbour distances): with the margin of 6 ranks, 508 queries of the planted 1M run failed the
+    // certificate under a bound that was still 2x too small, and the float64 scan of those cost 4.2 ms.  The failure
+    // probability falls like (bound / gap)^margin.  Measured with the correct bound, planted 1M: margin 8 -> select
+    // 16.5 ms + 200 fallbacks, 10 -> 17.0 ms + 5, 12 -> 18.0 ms + 1.  Round 4: the bound prices the norms a missed
+    // neighbour can have instead of the largest norm of the data set (knn_rerank_rows_kernel), which rejects fewer
+    // queries at every margin -- one box, planted 1M: margin 10 -> 16.97 ms + 1 float64 scan, 8 -> 16.30 ms + 58,
+    // 6 -> 15.89 ms + 1423 queries through the second tier (which costs what the margin saved), 4 -> 15.41 ms + 25764
+    // (profiles/r04e_knn_knobs.log): 8 ranks (threshold = the 23rd list entry at k = 15).
+    if (!p->thr_margin_env) p->thr_rank = std::min(32, std::max(1, k + 8));
   }
   const int QB = p->NW * 32;
   p->nq_pad = (n_query + QB - 1) / QB * QB;
   p->n_pad = (n + 255) / 256 * 256;
   // cell pruning pays once a sweep is long compared with the per-cell restarts; SCAMD_KNN_IVF=0 forces brute force
-  const int ivf_env = [] {  // read per call: the tests flip it inside one process
-    const char* e = getenv("SCAMD_KNN_IVF");
-    return e ? atoi(e) : -1;
-  }();
+  const int ivf_env = env_int("SCAMD_KNN_IVF", -1);
   p->ivf = p->reg && ivf_env != 0 && (n >= 65536 || ivf_env == 1) && n >= 4096;
   // approximate mode: always through the cell tables (register-list kernel: k <= 24, d <= 64, and n >= 4096 rows -- below
   // that, and for the other shapes, the call is answered exactly)
@@ -2417,10 +2406,7 @@ static bool knn_plan(int64_t n, int d, int64_t n_query, int k, KnnPlan* p, int n
   p->n_cells = 0;
   p->n_img_max = p->n_slot_max = 0;
   if (p->ivf) {
-    static const int cell_rows = [] {
-      const char* e = getenv("SCAMD_KNN_CELL_ROWS");
-      return e ? std::max(256, atoi(e)) : 2048;
-    }();
+    const int cell_rows = std::max(256, env_int("SCAMD_KNN_CELL_ROWS", 2048));
     int c = 16;
     while (c < IVF_MAX_CELLS && (int64_t)c * cell_rows < n) c <<= 1;  // ~cell_rows rows per cell
     while (c > 1 && (int64_t)c * 256 > n) c >>= 1;
@@ -2445,7 +2431,10 @@ struct KnnBuffers {
   int* qrow; float* xp2; int* flag_list2; int* t2_cell; int* t2_pos; int* t2_ints;
 };
 
+// launch slots of the pruned sweep: one per query block in block-id order; the XCD-aware order takes up to 8 x the longest queue
+static size_t block_perm_capacity(const KnnPlan& p) { return (size_t)(p.n_slot_max / 128 + 1) * 2 + 64; }
 static void knn_carve(Workspace& ws, const KnnPlan& p, int64_t n_query, KnnBuffers* b) {
+  *b = KnnBuffers{};  // (what a plan does not use stays null)
   b->xp = ws.take<float>((size_t)p.n_pad * p.row_dwords);
   b->cn = ws.take<float>((size_t)p.n_pad);
   b->mu = ws.take<float>(KNN_MAX_D);
@@ -2462,13 +2451,6 @@ static void knn_carve(Workspace& ws, const KnnPlan& p, int64_t n_query, KnnBuffe
   b->fb_retry[0] = ws.take<int>((size_t)n_query);
   b->fb_retry[1] = ws.take<int>((size_t)n_query);
   b->kth_idx = ws.take<int>((size_t)n_query);
-  b->labels = b->perm = b->qpos = b->block_cell = b->cell_ints = nullptr;
-  b->cent = b->centp = nullptr;
-  b->sums = nullptr;
-  b->radius_bits = nullptr;
-  b->cell_order = nullptr;
-  b->cell_lb2 = nullptr;
-  b->cell_aux = b->block_perm = b->qorder = nullptr;
   if (p.ivf) {
     b->labels = ws.take<int>((size_t)p.n_pad);  // sample labels, then labels of all rows
     b->perm = ws.take<int>((size_t)p.n_img_max);
@@ -2477,16 +2459,14 @@ static void knn_carve(Workspace& ws, const KnnPlan& p, int64_t n_query, KnnBuffe
     b->cent = ws.take<float>((size_t)p.n_cells * 128);
     b->centp = ws.take<float>((size_t)p.n_cells * 136);  // [n_cells][2H + norm column, padded to float4]
     b->sums = ws.take<long long>((size_t)p.n_cells * 128);
-    b->cell_ints = ws.take<int>((size_t)p.n_cells * 8);  // counts, qcounts, map, row_off, row_cur, slot_off, slot_cur, tile0/ntiles reuse
+    b->cell_ints = ws.take<int>((size_t)p.n_cells * 8);  // (sliced by cell_tables, as are sums, radius_bits and cell_aux)
     b->radius_bits = ws.take<unsigned int>((size_t)p.n_cells);
     b->cell_order = ws.take<int>((size_t)p.n_cells * p.n_cells);
     b->cell_lb2 = ws.take<float>((size_t)p.n_cells * p.n_cells);
-    b->cell_aux = ws.take<int>((size_t)p.n_cells * 3);  // expected work, first block, block count of every cell
-    b->block_perm = ws.take<int>((size_t)(p.n_slot_max / 128 + 1) * 2 + 64);  // (XCD-aware order: up to 8 x the longest queue)
+    b->cell_aux = ws.take<int>((size_t)p.n_cells * 3);
+    b->block_perm = ws.take<int>(block_perm_capacity(p));
     b->qorder = ws.take<int>((size_t)p.n_slot_max);
   }
-  b->qrow = b->flag_list2 = b->t2_cell = b->t2_pos = b->t2_ints = nullptr;
-  b->xp2 = nullptr;
   if (p.ivf && p.b3) {
     b->qrow = ws.take<int>((size_t)n_query);
     b->xp2 = ws.take<float>((size_t)p.n_img_max * RegCfg<25>::DPL);
@@ -2495,6 +2475,25 @@ static void knn_carve(Workspace& ws, const KnnPlan& p, int64_t n_query, KnnBuffe
     b->t2_pos = ws.take<int>((size_t)n_query);
     b->t2_ints = ws.take<int>((size_t)p.n_cells * 2 + 8);  // per-cell counts, slot offsets; [2 nc ..] counters
   }
+}
+
+// Typed views of the pruned search's per-cell tables ([n_cells] each): the one place that knows how cell_ints, cell_aux, the
+// recycled sums buffer and radius_bits are sliced.  Two pairs must stay adjacent and in this order: counts | qcounts are
+// cleared and read back as one block of 2 * n_cells, first_block | n_blocks are uploaded as one.
+struct CellTables {
+  int *counts, *qcounts;               // rows / rows of the query range the quantiser gave the cell
+  int* cell_map;                       // the cell it was folded into (itself unless it is small)
+  int *row_off, *row_cur;              // first image row; the scatter's cursor
+  int *slot_off, *slot_cur;            // first query slot; the scatter's cursor
+  int *tile0, *ntiles;                 // first tile of the image, tiles (ntiles: in the sums buffer, free once the quantiser is done)
+  const float* radius;                 // radius_bits as the floats they are (the pack kernel takes the maximum on the bits)
+  int *work, *first_block, *n_blocks;  // cell_aux: expected work of a sweep, first query block, query blocks
+};
+static CellTables cell_tables(const KnnBuffers& b, size_t nc) {
+  int* const ci = b.cell_ints;  // 8 * nc ints
+  int* const ca = b.cell_aux;   // 3 * nc ints
+  return {ci, ci + nc, ci + 2 * nc, ci + 3 * nc, ci + 4 * nc, ci + 5 * nc, ci + 6 * nc, ci + 7 * nc, reinterpret_cast<int*>(b.sums),
+          reinterpret_cast<const float*>(b.radius_bits), ca, ca + nc, ca + 2 * nc};
 }
 
 template <int H, int TC, int NW, int KP>
@@ -2572,96 +2571,61 @@ static int dispatch_select(const KnnPlan& p, const KnnBuffers& b, int64_t q_begi
 }
 
 // ---- cell-pruned search: quantiser, cell-sorted image, launch -------------------------------------------
-template <int H, bool B3 = false>
-static int run_ivf_select(const KnnPlan& p, const KnnBuffers& b, const float* x, int64_t n, int d, int64_t ld,
-                          int64_t q_begin, int64_t n_query, hipStream_t s, hipEvent_t ev0, hipEvent_t ev1,
-                          int64_t* rows_out) {
-  using C = RegCfg<H, 64, B3>;
+// the rows, the query range and the stream of one call
+struct KnnCall { const float* x; int64_t n; int d; int64_t ld, q_begin, n_query; hipStream_t s; };
+// owners: the events around the select launch and the trace buffer of the pruned sweep are released on every way out
+struct HipRelease {
+  void operator()(hipEvent_t e) const { (void)hipEventDestroy(e); }
+  void operator()(void* p) const { (void)hipFree(p); }
+};
+using EventOwner = std::unique_ptr<std::remove_pointer_t<hipEvent_t>, HipRelease>;
+
+// what every pruned sweep takes from the buffers and the cell tables; the caller adds pairs, qorder, prepass_*, trace, queue_ctr, n_slots
+static IvfArgs ivf_args(const KnnBuffers& b, const CellTables& t, int n_cells, int d) {
+  IvfArgs iv{};
+  iv.qpos = b.qpos;
+  iv.block_cell = b.block_cell;
+  iv.cell_tile0 = t.tile0;
+  iv.cell_ntiles = t.ntiles;
+  iv.centers = b.cent;
+  iv.radius = t.radius;
+  iv.order = b.cell_order;
+  iv.order_lb2 = b.cell_lb2;
+  iv.perm = b.perm;
+  iv.cmax_bits = b.cmax;
+  iv.n_cells = n_cells;
+  iv.dc = d;
+  iv.d = d;
+  iv.block_perm = b.block_perm;
+  return iv;
+}
+
+// query blocks of 128 slots, whole blocks per cell: the first slot of every cell and the cell of every block; returns the slots
+static int64_t layout_query_blocks(const std::vector<int>& n_queries, std::vector<int>* slot_off, std::vector<int>* block_cell) {
+  int64_t slots = 0;
+  for (size_t c = 0; c < n_queries.size(); ++c) {
+    slot_off->push_back((int)slots);
+    const int nb = (n_queries[c] + 127) / 128;
+    block_cell->insert(block_cell->end(), nb, (int)c);
+    slots += (int64_t)nb * 128;
+  }
+  return slots;
+}
+
+// host image of the cell tables, and the launch they lead to
+struct CellLayout {
+  std::vector<int> cell_map, row_off, slot_off, tile0, ntiles, block_cell;
+  std::vector<int> blocks;  // [first block | blocks] of every cell, 2 * nc
+  int64_t rows = 0, slots = 0;
+  int n_launch = 0, xcd_mode = 0;
+};
+
+// 3. host: fold small cells into their nearest big cell; padded layout of the image and of the query list
+static CellLayout ivf_cell_layout(const std::vector<int>& h_cnt, const std::vector<float>& h_cent, int nc, int d, size_t launch_cap) {
   constexpr int MIN_CELL = 128;
-  const int nc = p.n_cells;
-  int* counts = b.cell_ints;
-  int* qcounts = counts + nc;
-  int* cell_map = qcounts + nc;
-  int* row_off = cell_map + nc;
-  int* row_cur = row_off + nc;
-  int* slot_off = row_cur + nc;
-  int* slot_cur = slot_off + nc;
-  int* tile0 = slot_cur + nc;                     // cell_ints holds 8 * nc ints
-  int* ntiles = reinterpret_cast<int*>(b.sums);  // the sums buffer is free once the quantiser is done
-  // 1. quantiser: Lloyd on a strided sample
-  auto assign = ivf_assign_kernel<H>;
-  constexpr int DPA = (2 * H + 1 + 3) / 4 * 4;  // row length of the padded centroid table (ivf_assign_kernel)
-  // d <= 50: the assignments run on the bf16 matrix cores (any assignment gives a correct search; SCAMD_KNN_ASSIGN_MFMA=0
-  // keeps the float32 kernel, which at 32768 sampled rows x 512 centroids was 0.34 ms per Lloyd iteration -- a grid of
-  // 128 workgroups each looping over all centroids)
-  const int ncp = (nc + 31) / 32 * 32;
-  const size_t lds_a = (size_t)ncp * CENT_DPL * sizeof(unsigned int);
-  bool mfma_assign = false;
-  {
-    const char* e = getenv("SCAMD_KNN_ASSIGN_MFMA");
-    mfma_assign = H == 25 && !(e && e[0] == '0') && lds_a <= 150 * 1024;
-  }
-  unsigned int* centb = reinterpret_cast<unsigned int*>(b.centp);  // [ncp][32] dwords <= the float table's nc x 136 floats
-  if (mfma_assign)
-    SCAMD_HIP_CHECK(hipFuncSetAttribute(reinterpret_cast<const void*>(ivf_assign_mfma_kernel),
-                                        hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds_a));
-  auto run_assign = [&](int64_t a_start, int64_t a_step, int64_t a_count, int accumulate, int64_t aq0, int64_t aq1,
-                        int* a_qcounts, bool count_in_kernel = true) -> int {
-    if (mfma_assign) {
-      hipLaunchKernelGGL(ivf_centpad_bf16_kernel, dim3((unsigned)ceil_div((int64_t)ncp * 32, 256)), dim3(256), 0, s, b.cent, nc, ncp, d,
-                         centb);
-      SCAMD_LAUNCH_CHECK();
-      hipLaunchKernelGGL(ivf_assign_mfma_kernel, dim3((unsigned)ceil_div(a_count, ASSIGN_ROWS)), dim3(256), lds_a, s, x, d, ld, a_start,
-                         a_step, a_count, centb, ncp, nc, b.labels, count_in_kernel ? counts : (int*)nullptr, aq0, aq1, a_qcounts);
-      SCAMD_LAUNCH_CHECK();
-      if (accumulate) {
-        hipLaunchKernelGGL(ivf_sums_kernel, dim3((unsigned)ceil_div(a_count * d, 256)), dim3(256), 0, s, x, d, ld, a_start, a_step,
-                           a_count, b.labels, b.sums);
-        SCAMD_LAUNCH_CHECK();
-      }
-    } else {
-      hipLaunchKernelGGL(ivf_centpad_kernel, dim3((unsigned)ceil_div((int64_t)nc * DPA, 256)), dim3(256), 0, s, b.cent, nc, d,
-                         DPA, b.centp);
-      SCAMD_LAUNCH_CHECK();
-      hipLaunchKernelGGL(assign, dim3((unsigned)ceil_div(a_count, 256)), dim3(256), 0, s, x, d, ld, a_start, a_step, a_count,
-                         b.centp, nc, b.labels, accumulate, accumulate ? b.sums : (long long*)nullptr, counts, aq0, aq1,
-                         a_qcounts);
-      SCAMD_LAUNCH_CHECK();
-    }
-    return SCAMD_OK;
-  };
-  hipLaunchKernelGGL(ivf_init_kernel, dim3(nc), dim3(64), 0, s, x, n, d, ld, nc, b.cent);
-  SCAMD_LAUNCH_CHECK();
-  const int64_t n_sample = std::min<int64_t>(n, (int64_t)64 * nc);
-  const int64_t step = n / n_sample;
-  // (Lloyd iterations of the quantiser: 1 / 2 / 3 / 5 all leave the stage at 15.3-15.4 ms)
-  for (int it = 0; it < 3; ++it) {
-    SCAMD_HIP_CHECK(hipMemsetAsync(b.sums, 0, sizeof(long long) * nc * d, s));
-    SCAMD_HIP_CHECK(hipMemsetAsync(counts, 0, sizeof(int) * nc, s));
-    const int rca = run_assign(0, step, n_sample, 1, 0, 0, nullptr);
-    if (rca != SCAMD_OK) return rca;
-    hipLaunchKernelGGL(ivf_update_kernel, dim3((unsigned)ceil_div((int64_t)nc * d, 256)), dim3(256), 0, s, b.sums,
-                       counts, nc, d, b.cent);
-    SCAMD_LAUNCH_CHECK();
-  }
-  // 2. every row to its cell
-  SCAMD_HIP_CHECK(hipMemsetAsync(counts, 0, sizeof(int) * 2 * nc, s));
-  {
-    const int rca = run_assign(0, 1, n, 0, q_begin, q_begin + n_query, qcounts, !mfma_assign);
-    if (rca != SCAMD_OK) return rca;
-    if (mfma_assign) {
-      hipLaunchKernelGGL(ivf_count_kernel, dim3((unsigned)ceil_div(n, 4096)), dim3(1024), 0, s, b.labels, n, nc, q_begin, q_begin + n_query,
-                         counts, qcounts);
-      SCAMD_LAUNCH_CHECK();
-    }
-  }
-  std::vector<int> h_cnt(2 * nc);
-  std::vector<float> h_cent((size_t)nc * d);
-  SCAMD_HIP_CHECK(hipMemcpyAsync(h_cnt.data(), counts, sizeof(int) * 2 * nc, hipMemcpyDeviceToHost, s));
-  SCAMD_HIP_CHECK(hipMemcpyAsync(h_cent.data(), b.cent, sizeof(float) * nc * d, hipMemcpyDeviceToHost, s));
-  SCAMD_HIP_CHECK(hipStreamSynchronize(s));
-  // 3. host: fold small cells into their nearest big cell; padded layout of the image and of the query list
-  std::vector<int> h_map(nc), mc(nc, 0), mq(nc, 0);
+  CellLayout L;
+  L.cell_map.resize(nc);
+  std::vector<int> mc(nc, 0), mq(nc, 0);
   int biggest = 0;
   for (int c = 1; c < nc; ++c)
     if (h_cnt[c] > h_cnt[biggest]) biggest = c;
@@ -2683,195 +2647,275 @@ static int run_ivf_select(const KnnPlan& p, const KnnBuffers& b, const float* x,
         }
       }
     }
-    h_map[c] = tgt;
+    L.cell_map[c] = tgt;
     mc[tgt] += h_cnt[c];
     mq[tgt] += h_cnt[nc + c];
   }
-  std::vector<int> h_row_off(nc), h_slot_off(nc), h_tile0(nc), h_ntiles(nc), h_block_cell, h_blk(2 * nc);
-  int64_t rows = 0, slots = 0;
   for (int c = 0; c < nc; ++c) {
-    h_row_off[c] = (int)rows;
-    h_tile0[c] = (int)(rows / 64);
-    h_ntiles[c] = (mc[c] + 63) / 64;
-    rows += (int64_t)h_ntiles[c] * 64;
-    h_slot_off[c] = (int)slots;
-    const int nb = (mq[c] + 127) / 128;
-    h_blk[c] = (int)h_block_cell.size();  // first block of the cell
-    h_blk[nc + c] = nb;
-    for (int t = 0; t < nb; ++t) h_block_cell.push_back(c);
-    slots += (int64_t)nb * 128;
+    L.row_off.push_back((int)L.rows);
+    L.tile0.push_back((int)(L.rows / 64));
+    L.ntiles.push_back((mc[c] + 63) / 64);
+    L.rows += (int64_t)L.ntiles[c] * 64;
   }
-  const int n_blocks = (int)h_block_cell.size();
-  SCAMD_REQUIRE(rows <= p.n_img_max && slots <= p.n_slot_max, SCAMD_EWORKSPACE, "knn: cell layout exceeds its bound");
+  L.slots = layout_query_blocks(mq, &L.slot_off, &L.block_cell);
+  L.blocks.resize(2 * nc);
+  int maxb = 0;
+  for (int c = 0; c < nc; ++c) {
+    L.blocks[c] = L.slot_off[c] / 128;
+    L.blocks[nc + c] = (mq[c] + 127) / 128;
+    maxb = std::max(maxb, L.blocks[nc + c]);
+  }
   // launch slots: block-id order = n_blocks; XCD-aware order = 8 queues of at most
   // ceil(n_blocks / 8) + (blocks of the largest cell) slots, if the table has room
-  int n_launch = n_blocks, xcd_mode = 0;
-  {
-    // (the queues are built on the device from the device's work estimates; the host sizes the launch for queues of twice
-    // the mean length plus the largest cell -- slots beyond a queue's end hold -1 and exit at once, a queue that would
-    // not fit is cut off by `slot < n_slots` in ivf_block_order_kernel ... which must not happen: checked there)
-    int maxb = 0;
-    for (int c = 0; c < nc; ++c) maxb = std::max(maxb, h_blk[nc + c]);
-    const int64_t want = (int64_t)8 * (2 * ((n_blocks + 7) / 8) + maxb);
-    const int64_t cap = (int64_t)(p.n_slot_max / 128 + 1) * 2 + 64;
-    if (n_blocks >= 64 && want <= cap) {
-      xcd_mode = 1;
-      n_launch = (int)want;
+  // (the queues are built on the device from the device's work estimates; the host sizes the launch for queues of twice
+  // the mean length plus the largest cell -- slots beyond a queue's end hold -1 and exit at once, a queue that would
+  // not fit is cut off by `slot < n_slots` in ivf_block_order_kernel ... which must not happen: checked there)
+  const int n_blocks = (int)L.block_cell.size();
+  const int64_t want = (int64_t)8 * (2 * ((n_blocks + 7) / 8) + maxb);
+  L.n_launch = n_blocks;
+  if (n_blocks >= 64 && want <= (int64_t)launch_cap) {
+    L.xcd_mode = 1;
+    L.n_launch = (int)want;
+  }
+  return L;
+}
+
+// One pruned select: run_ivf_select<H, B3> gives the kernels of the instantiation, the stages compile once, in the order `run`
+// calls them.  The image geometry RegCfg<H, 64, B3> is the plan's: H, row_dwords, b3.
+struct IvfSelect {
+  const KnnPlan& p;
+  const KnnBuffers& b;
+  const KnnCall& c;
+  decltype(&ivf_assign_kernel<8>) assign_f32;
+  decltype(&knn_select_reg_kernel<8, 64, 3, true, false>) sweep[2];  // [0] plain, [1] with the coarse first stage
+  size_t sweep_lds;
+  const CellTables t = cell_tables(b, p.n_cells);
+  const int nc = p.n_cells;
+  // set by train_quantiser: how this call assigns rows to centroids
+  bool mfma_assign = false;
+  int ncp = 0;       // centroids, padded to whole MFMA operands
+  size_t lds_a = 0;  // the MFMA assignment's centroid table
+  // rows a_start + j * a_step (j < a_count) to their nearest centroid
+  int assign(int64_t a_start, int64_t a_step, int64_t a_count, int accumulate, int64_t aq0, int64_t aq1, int* a_qcounts,
+             bool count_in_kernel = true) const {
+    hipStream_t s = c.s;
+    if (mfma_assign) {
+      unsigned int* centb = reinterpret_cast<unsigned int*>(b.centp);  // [ncp][32] dwords <= the float table's nc x 136 floats
+      hipLaunchKernelGGL(ivf_centpad_bf16_kernel, dim3((unsigned)ceil_div((int64_t)ncp * 32, 256)), dim3(256), 0, s, b.cent, nc, ncp, c.d,
+                         centb);
+      SCAMD_LAUNCH_CHECK();
+      hipLaunchKernelGGL(ivf_assign_mfma_kernel, dim3((unsigned)ceil_div(a_count, ASSIGN_ROWS)), dim3(256), lds_a, s, c.x, c.d, c.ld, a_start,
+                         a_step, a_count, centb, ncp, nc, b.labels, count_in_kernel ? t.counts : (int*)nullptr, aq0, aq1, a_qcounts);
+      SCAMD_LAUNCH_CHECK();
+      if (accumulate) {
+        hipLaunchKernelGGL(ivf_sums_kernel, dim3((unsigned)ceil_div(a_count * c.d, 256)), dim3(256), 0, s, c.x, c.d, c.ld, a_start, a_step,
+                           a_count, b.labels, b.sums);
+        SCAMD_LAUNCH_CHECK();
+      }
+    } else {
+      const int dpa = (2 * p.H + 1 + 3) / 4 * 4;  // row length of the padded centroid table (ivf_assign_kernel)
+      hipLaunchKernelGGL(ivf_centpad_kernel, dim3((unsigned)ceil_div((int64_t)nc * dpa, 256)), dim3(256), 0, s, b.cent, nc, c.d, dpa,
+                         b.centp);
+      SCAMD_LAUNCH_CHECK();
+      hipLaunchKernelGGL(assign_f32, dim3((unsigned)ceil_div(a_count, 256)), dim3(256), 0, s, c.x, c.d, c.ld, a_start, a_step, a_count,
+                         b.centp, nc, b.labels, accumulate, accumulate ? b.sums : (long long*)nullptr, t.counts, aq0, aq1, a_qcounts);
+      SCAMD_LAUNCH_CHECK();
     }
+    return SCAMD_OK;
   }
-  rows_out[0] = rows;
-  rows_out[1] = slots;
-  if (n_blocks == 0) return SCAMD_OK;
-  SCAMD_HIP_CHECK(hipMemcpyAsync(cell_map, h_map.data(), sizeof(int) * nc, hipMemcpyHostToDevice, s));
-  SCAMD_HIP_CHECK(hipMemcpyAsync(row_off, h_row_off.data(), sizeof(int) * nc, hipMemcpyHostToDevice, s));
-  SCAMD_HIP_CHECK(hipMemcpyAsync(slot_off, h_slot_off.data(), sizeof(int) * nc, hipMemcpyHostToDevice, s));
-  SCAMD_HIP_CHECK(hipMemcpyAsync(tile0, h_tile0.data(), sizeof(int) * nc, hipMemcpyHostToDevice, s));
-  SCAMD_HIP_CHECK(hipMemcpyAsync(ntiles, h_ntiles.data(), sizeof(int) * nc, hipMemcpyHostToDevice, s));
-  SCAMD_HIP_CHECK(hipMemcpyAsync(b.block_cell, h_block_cell.data(), sizeof(int) * n_blocks, hipMemcpyHostToDevice, s));
-  SCAMD_HIP_CHECK(hipMemcpyAsync(b.cell_aux + nc, h_blk.data(), sizeof(int) * 2 * nc, hipMemcpyHostToDevice, s));
-  SCAMD_HIP_CHECK(hipMemsetAsync(row_cur, 0, sizeof(int) * nc, s));
-  SCAMD_HIP_CHECK(hipMemsetAsync(slot_cur, 0, sizeof(int) * nc, s));
-  SCAMD_HIP_CHECK(hipMemsetAsync(b.perm, 0xff, sizeof(int) * rows, s));
-  SCAMD_HIP_CHECK(hipMemsetAsync(b.qpos, 0xff, sizeof(int) * slots, s));
-  SCAMD_HIP_CHECK(hipMemsetAsync(b.radius_bits, 0, sizeof(unsigned int) * nc, s));
-  SCAMD_HIP_CHECK(hipMemsetAsync(b.counters + 2, 0, 16, s));
-  SCAMD_HIP_CHECK(hipStreamSynchronize(s));  // the host vectors above must outlive their copies
-  // 4. cell-sorted image
-  hipLaunchKernelGGL(ivf_scatter_kernel, dim3((unsigned)ceil_div(n, 1024 * SCATTER_ROWS)), dim3(1024), 0, s, b.labels, n, cell_map, row_off,
-                     row_cur, q_begin, q_begin + n_query, slot_off, slot_cur, b.perm, b.qpos, b.qrow, nc);
-  SCAMD_LAUNCH_CHECK();
-  {
-    // (a group of 16 lanes per image row, 16 groups per workgroup)
-    const int blocks = (int)std::min<int64_t>((rows + 15) / 16, 256 * 16);
-    hipLaunchKernelGGL(ivf_pack_image_kernel, dim3(blocks), dim3(256), 0, s, x, b.mu, d, ld, H, C::HP, C::DPL, rows, b.perm,
-                       b.labels, cell_map, b.cent, b.xp, b.cmax, b.radius_bits, B3 ? 1 : 0);
+  // 1. quantiser: Lloyd on a strided sample
+  int train_quantiser() {
+    // d <= 50: the assignments run on the bf16 matrix cores (any assignment gives a correct search; SCAMD_KNN_ASSIGN_MFMA=0
+    // keeps the float32 kernel, which at 32768 sampled rows x 512 centroids was 0.34 ms per Lloyd iteration -- a grid of
+    // 128 workgroups each looping over all centroids)
+    ncp = (nc + 31) / 32 * 32;
+    lds_a = (size_t)ncp * CENT_DPL * sizeof(unsigned int);
+    mfma_assign = p.H == 25 && !env_is("SCAMD_KNN_ASSIGN_MFMA", '0') && lds_a <= 150 * 1024;
+    if (mfma_assign)
+      SCAMD_HIP_CHECK(hipFuncSetAttribute(reinterpret_cast<const void*>(ivf_assign_mfma_kernel),
+                                          hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds_a));
+    hipLaunchKernelGGL(ivf_init_kernel, dim3(nc), dim3(64), 0, c.s, c.x, c.n, c.d, c.ld, nc, b.cent);
     SCAMD_LAUNCH_CHECK();
+    const int64_t n_sample = std::min<int64_t>(c.n, (int64_t)64 * nc);
+    const int64_t step = c.n / n_sample;
+    // (Lloyd iterations of the quantiser: 1 / 2 / 3 / 5 all leave the stage at 15.3-15.4 ms)
+    for (int it = 0; it < 3; ++it) {
+      SCAMD_HIP_CHECK(hipMemsetAsync(b.sums, 0, sizeof(long long) * nc * c.d, c.s));
+      SCAMD_HIP_CHECK(hipMemsetAsync(t.counts, 0, sizeof(int) * nc, c.s));
+      if (int rc = assign(0, step, n_sample, 1, 0, 0, nullptr)) return rc;
+      hipLaunchKernelGGL(ivf_update_kernel, dim3((unsigned)ceil_div((int64_t)nc * c.d, 256)), dim3(256), 0, c.s, b.sums, t.counts, nc,
+                         c.d, b.cent);
+      SCAMD_LAUNCH_CHECK();
+    }
+    return SCAMD_OK;
   }
-  // 5. sweep order of every cell (needs the radii the pack kernel just produced)
-  {
+  // 2. every row to its cell; h_cnt = [rows | rows of the query range] of every cell, h_cent = the centroids
+  int assign_rows(std::vector<int>* h_cnt, std::vector<float>* h_cent) const {
+    SCAMD_HIP_CHECK(hipMemsetAsync(t.counts, 0, sizeof(int) * 2 * nc, c.s));
+    if (int rc = assign(0, 1, c.n, 0, c.q_begin, c.q_begin + c.n_query, t.qcounts, !mfma_assign)) return rc;
+    if (mfma_assign) {
+      hipLaunchKernelGGL(ivf_count_kernel, dim3((unsigned)ceil_div(c.n, 4096)), dim3(1024), 0, c.s, b.labels, c.n, nc, c.q_begin,
+                         c.q_begin + c.n_query, t.counts, t.qcounts);
+      SCAMD_LAUNCH_CHECK();
+    }
+    SCAMD_HIP_CHECK(hipMemcpyAsync(h_cnt->data(), t.counts, sizeof(int) * 2 * nc, hipMemcpyDeviceToHost, c.s));
+    SCAMD_HIP_CHECK(hipMemcpyAsync(h_cent->data(), b.cent, sizeof(float) * nc * c.d, hipMemcpyDeviceToHost, c.s));
+    SCAMD_HIP_CHECK(hipStreamSynchronize(c.s));
+    return SCAMD_OK;
+  }
+  // 4. the tables to the device; cursors, image rows, query slots, radii and pair counters cleared
+  int upload_tables(const CellLayout& L) const {
+    hipStream_t s = c.s;
+    const size_t cell_bytes = sizeof(int) * nc;
+    const std::pair<int*, const std::vector<int>*> per_cell[] = {
+        {t.cell_map, &L.cell_map}, {t.row_off, &L.row_off}, {t.slot_off, &L.slot_off}, {t.tile0, &L.tile0}, {t.ntiles, &L.ntiles}};
+    for (const auto& [dst, src] : per_cell) SCAMD_HIP_CHECK(hipMemcpyAsync(dst, src->data(), cell_bytes, hipMemcpyHostToDevice, s));
+    SCAMD_HIP_CHECK(hipMemcpyAsync(b.block_cell, L.block_cell.data(), sizeof(int) * L.block_cell.size(), hipMemcpyHostToDevice, s));
+    SCAMD_HIP_CHECK(hipMemcpyAsync(t.first_block, L.blocks.data(), 2 * cell_bytes, hipMemcpyHostToDevice, s));
+    SCAMD_HIP_CHECK(hipMemsetAsync(t.row_cur, 0, cell_bytes, s));
+    SCAMD_HIP_CHECK(hipMemsetAsync(t.slot_cur, 0, cell_bytes, s));
+    SCAMD_HIP_CHECK(hipMemsetAsync(b.perm, 0xff, sizeof(int) * L.rows, s));
+    SCAMD_HIP_CHECK(hipMemsetAsync(b.qpos, 0xff, sizeof(int) * L.slots, s));
+    SCAMD_HIP_CHECK(hipMemsetAsync(b.radius_bits, 0, sizeof(unsigned int) * nc, s));
+    SCAMD_HIP_CHECK(hipMemsetAsync(b.counters + 2, 0, 16, s));
+    SCAMD_HIP_CHECK(hipStreamSynchronize(s));  // the host vectors of L must outlive their copies
+    return SCAMD_OK;
+  }
+  // 5. cell-sorted image; sweep order of every cell (needs the radii the pack kernel produces); launch order
+  int build_image_and_orders(const CellLayout& L) const {
+    hipStream_t s = c.s;
+    hipLaunchKernelGGL(ivf_scatter_kernel, dim3((unsigned)ceil_div(c.n, 1024 * SCATTER_ROWS)), dim3(1024), 0, s, b.labels, c.n, t.cell_map,
+                       t.row_off, t.row_cur, c.q_begin, c.q_begin + c.n_query, t.slot_off, t.slot_cur, b.perm, b.qpos, b.qrow, nc);
+    SCAMD_LAUNCH_CHECK();
+    // (a group of 16 lanes per image row, 16 groups per workgroup)
+    const int blocks = (int)std::min<int64_t>((L.rows + 15) / 16, 256 * 16);
+    hipLaunchKernelGGL(ivf_pack_image_kernel, dim3(blocks), dim3(256), 0, s, c.x, b.mu, c.d, c.ld, p.H, (p.H + 1 + 3) / 4 * 4, p.row_dwords, L.rows, b.perm, b.labels,
+                       t.cell_map, b.cent, b.xp, b.cmax, b.radius_bits, p.b3 ? 1 : 0);
+    SCAMD_LAUNCH_CHECK();
     int npow = 1;
     while (npow < nc) npow <<= 1;
     const size_t olds = (size_t)npow * 8;
     SCAMD_HIP_CHECK(hipFuncSetAttribute(reinterpret_cast<const void*>(ivf_cell_order_kernel),
                                         hipFuncAttributeMaxDynamicSharedMemorySize, (int)olds));
-    hipLaunchKernelGGL(ivf_cell_order_kernel, dim3(nc), dim3(256), olds, s, b.cent, d,
-                       reinterpret_cast<const float*>(b.radius_bits), ntiles, nc, b.cell_order, b.cell_lb2, b.cell_aux,
-                       p.nprobe);
+    hipLaunchKernelGGL(ivf_cell_order_kernel, dim3(nc), dim3(256), olds, s, b.cent, c.d, t.radius, t.ntiles, nc, b.cell_order, b.cell_lb2,
+                       t.work, p.nprobe);
     SCAMD_LAUNCH_CHECK();
     // launch order: longest expected sweeps first
-    hipLaunchKernelGGL(ivf_block_order_kernel, dim3(1), dim3(1024), 0, s, b.cell_aux, b.cell_aux + nc, b.cell_aux + 2 * nc,
-                       nc, b.block_perm, n_launch, xcd_mode, b.counters + 6);
+    hipLaunchKernelGGL(ivf_block_order_kernel, dim3(1), dim3(1024), 0, s, t.work, t.first_block, t.n_blocks, nc, b.block_perm, L.n_launch,
+                       L.xcd_mode, b.counters + 6);
     SCAMD_LAUNCH_CHECK();
+    return SCAMD_OK;
   }
-  // 6. pruned sweep
-  // register budget: cut for 3 resident blocks per CU (168 VGPRs; the H = 25 / 32 instantiations then spill 96 / 236
-  // bytes per lane to scratch, `-Rpass-analysis=kernel-resource-usage`; measured against the build cut for 2 blocks per
-  // CU, which does not spill).  (bf16 engine, round 4: with its tiles arriving by LDS-DMA the staging registers are gone --
-  // 175 VGPRs uncut, 5 of them spilled in the build cut for 3 blocks per CU (was 47), and 3 x 53 KB of LDS just fit the
-  // CU's 160: 13.31 ms against 16.11 with 2 blocks on one box, profiles/r04s_knn_lds_dma_ring_ab.log -- a third block
-  // covers the other two's insertion stalls)
-  auto kern = knn_select_reg_kernel<H, 64, 3, true, B3>;
-  // COARSE first stage (bf16 engine; knn_select_reg_block): pays when a query meets so many candidates that few 32 x 32
+  // 6. COARSE first stage (bf16 engine; knn_select_reg_block): pays when a query meets so many candidates that few 32 x 32
   // sub-tiles hold one below its threshold -- the sweeps in which the cell bounds prune little.  Decided from the device's own
   // work estimates (tiles within a cell's radius, ivf_cell_order_kernel), weighted by the cells' query blocks: expected
   // candidates per query >= 5e5 (1M cells: the planted matrix ~3e4 -> plain kernel, the weak / structure-less ones 1e6 -> coarse,
   // 317 -> 260 ms; 10M planted cells ~2.5e5 -> plain: 795 ms against 835 with the coarse stage, profiles/r06y2_ab.log).
   // SCAMD_KNN_COARSE=0 / 1 forces the choice (A/B, tests).
-  bool coarse = false;
-  if constexpr (B3) {
-    const char* ce = getenv("SCAMD_KNN_COARSE");
-    if (ce && (ce[0] == '0' || ce[0] == '1')) {
-      coarse = ce[0] == '1';
-    } else {
-      std::vector<int> h_work(nc);
-      SCAMD_HIP_CHECK(hipMemcpyAsync(h_work.data(), b.cell_aux, sizeof(int) * nc, hipMemcpyDeviceToHost, s));
-      SCAMD_HIP_CHECK(hipStreamSynchronize(s));
-      double num = 0.0, den = 0.0;
-      for (int c = 0; c < nc; ++c) {
-        num += (double)h_blk[nc + c] * (double)h_work[c] * 64.0;
-        den += (double)h_blk[nc + c];
-      }
-      coarse = den > 0.0 && num / den >= 5.0e5;
+  int choose_coarse(const CellLayout& L, bool* coarse) const {
+    *coarse = p.b3 && env_is("SCAMD_KNN_COARSE", '1');
+    if (!p.b3 || *coarse || env_is("SCAMD_KNN_COARSE", '0')) return SCAMD_OK;
+    std::vector<int> h_work(nc);
+    SCAMD_HIP_CHECK(hipMemcpyAsync(h_work.data(), t.work, sizeof(int) * nc, hipMemcpyDeviceToHost, c.s));
+    SCAMD_HIP_CHECK(hipStreamSynchronize(c.s));
+    double num = 0.0, den = 0.0;
+    for (int cell = 0; cell < nc; ++cell) {
+      num += (double)L.blocks[nc + cell] * (double)h_work[cell] * 64.0;
+      den += (double)L.blocks[nc + cell];
     }
-    if (coarse) kern = knn_select_reg_kernel<H, 64, 3, true, B3, B3>;  // (COARSE = B3: the float32 engine has no such instantiation)
+    *coarse = den > 0.0 && num / den >= 5.0e5;
+    return SCAMD_OK;
   }
-  g_last_coarse = coarse ? 1 : 0;
-  const size_t lds = C::LDS_BYTES + 64 + IVF_META_BYTES;
-  SCAMD_HIP_CHECK(hipFuncSetAttribute(reinterpret_cast<const void*>(kern), hipFuncAttributeMaxDynamicSharedMemorySize,
-                                      (int)lds));
-  IvfArgs iv;
-  iv.qpos = b.qpos;
-  iv.block_cell = b.block_cell;
-  iv.cell_tile0 = tile0;
-  iv.cell_ntiles = ntiles;
-  iv.centers = b.cent;
-  iv.radius = reinterpret_cast<const float*>(b.radius_bits);
-  iv.order = b.cell_order;
-  iv.order_lb2 = b.cell_lb2;
-  iv.perm = b.perm;
-  iv.cmax_bits = b.cmax;
-  iv.pairs = reinterpret_cast<unsigned long long*>(b.counters + 2);
-  iv.n_cells = nc;
-  iv.dc = d;
-  iv.d = d;
-  iv.block_perm = b.block_perm;
-  iv.qorder = b.qorder;
-  {
+  // 7. pruned sweep
+  int launch_sweep(const CellLayout& L, bool coarse, hipEvent_t ev0, hipEvent_t ev1) const {
+    hipStream_t s = c.s;
+    const size_t n_blocks = L.block_cell.size();
+    const auto kern = sweep[coarse];
+    const size_t lds = sweep_lds + 64 + IVF_META_BYTES;
+    SCAMD_HIP_CHECK(hipFuncSetAttribute(reinterpret_cast<const void*>(kern), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
+    IvfArgs iv = ivf_args(b, t, nc, c.d);
+    iv.pairs = reinterpret_cast<unsigned long long*>(b.counters + 2);
+    iv.qorder = b.qorder;
     // float32 engine, measured at 1M: 48 -> 29.3 ms, 24 / 12 -> 29.0, 6 -> 29.6, 2 -> 30.2; bf16 engine (the pre-pass
     // costs a quarter): 8 -> 17.1, 16 -> 16.8, 32 -> 16.15, 64 -> 16.1
-    iv.prepass_tiles = B3 ? 32 : 16;
-    const char* e3 = getenv("SCAMD_KNN_PREPASS_MIN2");
-    iv.prepass_min2 = (e3 && e3[0] == '0') ? 0 : 1;
-  }
-  iv.trace = nullptr;
-  const char* trace_path = getenv("SCAMD_KNN_TRACE");  // debug: per-block timeline of the sweep, dumped to this file
-  if (trace_path && trace_path[0]) {
-    SCAMD_HIP_CHECK(hipMalloc(reinterpret_cast<void**>(&iv.trace), sizeof(unsigned long long) * 8 * n_blocks));
-    SCAMD_HIP_CHECK(hipMemsetAsync(iv.trace, 0, sizeof(unsigned long long) * 8 * n_blocks, s));
-  }
-  // persistent launch (see knn_select_reg_kernel): 8 XCDs x 32 CUs x the resident blocks per CU; SCAMD_KNN_PERSISTENT=0 is the
-  // launch of one workgroup per slot, = N sets the number of workgroups (rounded up to a multiple of 8)
-  int n_groups = n_launch;
-  iv.queue_ctr = nullptr;
-  iv.n_slots = n_launch;
-  {
-    const char* e = getenv("SCAMD_KNN_PERSISTENT");
-    const int want = e ? atoi(e) : 768;
-    if (want > 0 && n_launch > want) {
+    iv.prepass_tiles = p.b3 ? 32 : 16;
+    iv.prepass_min2 = env_is("SCAMD_KNN_PREPASS_MIN2", '0') ? 0 : 1;
+    std::unique_ptr<void, HipRelease> trace;
+    const char* trace_path = getenv("SCAMD_KNN_TRACE");  // debug: per-block timeline of the sweep, dumped to this file
+    if (trace_path && trace_path[0]) {
+      SCAMD_HIP_CHECK(hipMalloc(reinterpret_cast<void**>(&iv.trace), sizeof(unsigned long long) * 8 * n_blocks));
+      trace.reset(iv.trace);
+      SCAMD_HIP_CHECK(hipMemsetAsync(iv.trace, 0, sizeof(unsigned long long) * 8 * n_blocks, s));
+    }
+    // persistent launch (see knn_select_reg_kernel): 8 XCDs x 32 CUs x the resident blocks per CU; SCAMD_KNN_PERSISTENT=0 is the
+    // launch of one workgroup per slot, = N sets the number of workgroups (rounded up to a multiple of 8)
+    int n_groups = L.n_launch;
+    iv.n_slots = L.n_launch;
+    const int want = env_int("SCAMD_KNN_PERSISTENT", 768);
+    if (want > 0 && L.n_launch > want) {
       n_groups = (want + 7) / 8 * 8;
       iv.queue_ctr = b.counters + 8;
       SCAMD_HIP_CHECK(hipMemsetAsync(b.counters + 8, 0, sizeof(int) * 8, s));
     }
-  }
-  SCAMD_HIP_CHECK(hipEventRecord(ev0, s));
-  hipLaunchKernelGGL(kern, dim3(n_groups), dim3(C::NT), lds, s, b.xp, (int)(rows / 64), rows, q_begin, p.thr_rank,
-                     b.cand_idx, b.cand_tau, iv);
-  SCAMD_LAUNCH_CHECK();
-  SCAMD_HIP_CHECK(hipEventRecord(ev1, s));
-  if (iv.trace) {
-    std::vector<unsigned long long> h((size_t)8 * n_blocks);
-    SCAMD_HIP_CHECK(hipMemcpyAsync(h.data(), iv.trace, sizeof(unsigned long long) * h.size(), hipMemcpyDeviceToHost, s));
-    SCAMD_HIP_CHECK(hipStreamSynchronize(s));
-    SCAMD_HIP_CHECK(hipFree(iv.trace));
-    if (FILE* f = fopen(trace_path, "wb")) {
-      fwrite(h.data(), sizeof(unsigned long long), h.size(), f);
-      fwrite(h_block_cell.data(), sizeof(int), h_block_cell.size(), f);
-      fclose(f);
+    SCAMD_HIP_CHECK(hipEventRecord(ev0, s));
+    hipLaunchKernelGGL(kern, dim3(n_groups), dim3(RegCfg<8>::NT), lds, s, b.xp, (int)(L.rows / 64), L.rows, c.q_begin, p.thr_rank,
+                       b.cand_idx, b.cand_tau, iv);
+    SCAMD_LAUNCH_CHECK();
+    SCAMD_HIP_CHECK(hipEventRecord(ev1, s));
+    if (iv.trace) {
+      std::vector<unsigned long long> h(8 * n_blocks);
+      SCAMD_HIP_CHECK(hipMemcpyAsync(h.data(), iv.trace, sizeof(unsigned long long) * h.size(), hipMemcpyDeviceToHost, s));
+      SCAMD_HIP_CHECK(hipStreamSynchronize(s));
+      SCAMD_HIP_CHECK(hipFree(trace.release()));
+      if (FILE* f = fopen(trace_path, "wb")) {
+        fwrite(h.data(), sizeof(unsigned long long), h.size(), f);
+        fwrite(L.block_cell.data(), sizeof(int), L.block_cell.size(), f);
+        fclose(f);
+      }
     }
+    return SCAMD_OK;
   }
-  return SCAMD_OK;
+  int run(hipEvent_t ev0, hipEvent_t ev1, int64_t* rows_out) {
+    std::vector<int> h_cnt(2 * nc);
+    std::vector<float> h_cent((size_t)nc * c.d);
+    if (int rc = train_quantiser()) return rc;
+    if (int rc = assign_rows(&h_cnt, &h_cent)) return rc;
+    const CellLayout L = ivf_cell_layout(h_cnt, h_cent, nc, c.d, block_perm_capacity(p));
+    SCAMD_REQUIRE(L.rows <= p.n_img_max && L.slots <= p.n_slot_max, SCAMD_EWORKSPACE, "knn: cell layout exceeds its bound");
+    rows_out[0] = L.rows;
+    rows_out[1] = L.slots;
+    if (L.block_cell.empty()) return SCAMD_OK;
+    if (int rc = upload_tables(L)) return rc;
+    if (int rc = build_image_and_orders(L)) return rc;
+    bool coarse = false;
+    if (int rc = choose_coarse(L, &coarse)) return rc;
+    g_last_coarse = coarse ? 1 : 0;
+    return launch_sweep(L, coarse, ev0, ev1);
+  }
+};
+
+template <int H, bool B3 = false>
+static int run_ivf_select(const KnnPlan& p, const KnnBuffers& b, const KnnCall& c, hipEvent_t ev0, hipEvent_t ev1, int64_t* rows_out) {
+  using C = RegCfg<H, 64, B3>;
+  // register budget of the sweep: cut for 3 resident blocks per CU (168 VGPRs; the H = 25 / 32 instantiations then spill 96 / 236
+  // bytes per lane to scratch, `-Rpass-analysis=kernel-resource-usage`; measured against the build cut for 2 blocks per
+  // CU, which does not spill).  (bf16 engine, round 4: with its tiles arriving by LDS-DMA the staging registers are gone --
+  // 175 VGPRs uncut, 5 of them spilled in the build cut for 3 blocks per CU (was 47), and 3 x 53 KB of LDS just fit the
+  // CU's 160: 13.31 ms against 16.11 with 2 blocks on one box, profiles/r04s_knn_lds_dma_ring_ab.log -- a third block
+  // covers the other two's insertion stalls)
+  // (the coarse sweep has COARSE = B3: the float32 engine has no such instantiation, and never chooses it)
+  static_assert(C::NT == RegCfg<8>::NT, "every instantiation is launched with the same block size");
+  IvfSelect sel{p, b, c, ivf_assign_kernel<H>,
+                {knn_select_reg_kernel<H, 64, 3, true, B3>, knn_select_reg_kernel<H, 64, 3, true, B3, B3>}, C::LDS_BYTES};
+  return sel.run(ev0, ev1, rows_out);
 }
 
-static int dispatch_ivf(const KnnPlan& p, const KnnBuffers& b, const float* x, int64_t n, int d, int64_t ld,
-                        int64_t q_begin, int64_t n_query, hipStream_t s, hipEvent_t ev0, hipEvent_t ev1,
-                        int64_t* rows_out) {
+static int dispatch_ivf(const KnnPlan& p, const KnnBuffers& b, const KnnCall& c, hipEvent_t ev0, hipEvent_t ev1, int64_t* rows_out) {
   switch (p.H) {
-    case 8: return run_ivf_select<8>(p, b, x, n, d, ld, q_begin, n_query, s, ev0, ev1, rows_out);
-    case 16: return run_ivf_select<16>(p, b, x, n, d, ld, q_begin, n_query, s, ev0, ev1, rows_out);
-    case 25:
-      if (p.b3) return run_ivf_select<25, true>(p, b, x, n, d, ld, q_begin, n_query, s, ev0, ev1, rows_out);
-      return run_ivf_select<25>(p, b, x, n, d, ld, q_begin, n_query, s, ev0, ev1, rows_out);
-    default: return run_ivf_select<32>(p, b, x, n, d, ld, q_begin, n_query, s, ev0, ev1, rows_out);
+    case 8: return run_ivf_select<8>(p, b, c, ev0, ev1, rows_out);
+    case 16: return run_ivf_select<16>(p, b, c, ev0, ev1, rows_out);
+    case 25: return p.b3 ? run_ivf_select<25, true>(p, b, c, ev0, ev1, rows_out) : run_ivf_select<25>(p, b, c, ev0, ev1, rows_out);
+    default: return run_ivf_select<32>(p, b, c, ev0, ev1, rows_out);
   }
 }
 
@@ -2881,41 +2925,30 @@ static int dispatch_ivf(const KnnPlan& p, const KnnBuffers& b, const float* x, i
 // blocks of their own -- are swept again by the FLOAT32 engine over a float32 image of the same cell-sorted rows (same
 // cell tables, same sweep orders), re-ranked and certified with the float32 bound; what fails that too goes to the
 // float64 scan as before.  Cost: one image (0.7 ms per million rows) + the float32 sweep of < 1 % of the queries.
-#define T2_DBG(line)                                                                 \
-  do {                                                                               \
-    if (getenv("SCAMD_KNN_T2_DEBUG")) {                                              \
-      hipError_t e_ = hipStreamSynchronize(s);                                       \
-      fprintf(stderr, "[knn tier2] line %d done (%s)\n", (int)(line), hipGetErrorString(e_)); \
-      fflush(stderr);                                                                \
-    }                                                                                \
-  } while (0)
-static int run_ivf_tier2(const KnnPlan& p, const KnnBuffers& b, const float* x, int64_t n, int d, int64_t ld,
-                         int64_t q_begin, int64_t n_query, int k, double cert_scale, int n_flag, int64_t rows,
-                         int32_t* out_idx, double* out_dist, hipStream_t s, int* n_flag2_host) {
+static void t2_dbg(hipStream_t s, int line) {
+  if (!getenv("SCAMD_KNN_T2_DEBUG")) return;
+  fprintf(stderr, "[knn tier2] line %d done (%s)\n", line, hipGetErrorString(hipStreamSynchronize(s)));
+  fflush(stderr);
+}
+static int run_ivf_tier2(const KnnPlan& p, const KnnBuffers& b, const KnnCall& c, int k, double cert_scale, int n_flag,
+                         int64_t rows, int32_t* out_idx, double* out_dist, int* n_flag2_host) {
   using C = RegCfg<25, 64, false>;
   const int nc = p.n_cells;
-  int* cell_map = b.cell_ints + 2 * nc;
-  int* tile0 = b.cell_ints + 7 * nc;
-  int* ntiles = reinterpret_cast<int*>(b.sums);
+  const CellTables t = cell_tables(b, nc);
+  hipStream_t s = c.s;
   int* cnt2 = b.t2_ints;
   int* slot_off2 = b.t2_ints + nc;
   int* ctr2 = b.t2_ints + 2 * nc;  // [0] still uncertified, [2..3] / [4..5] pair counters of the second sweep (not reported)
   *n_flag2_host = 0;
   SCAMD_HIP_CHECK(hipMemsetAsync(cnt2, 0, sizeof(int) * nc, s));
   SCAMD_HIP_CHECK(hipMemsetAsync(ctr2, 0, sizeof(int) * 8, s));
-  hipLaunchKernelGGL(ivf_t2_count_kernel, dim3((unsigned)ceil_div(n_flag, 256)), dim3(256), 0, s, b.flag_list, n_flag, q_begin,
-                     b.labels, cell_map, cnt2, b.t2_cell, b.t2_pos);
+  hipLaunchKernelGGL(ivf_t2_count_kernel, dim3((unsigned)ceil_div(n_flag, 256)), dim3(256), 0, s, b.flag_list, n_flag, c.q_begin,
+                     b.labels, t.cell_map, cnt2, b.t2_cell, b.t2_pos);
   SCAMD_LAUNCH_CHECK();
-  T2_DBG(__LINE__);
-  std::vector<int> h_cnt(nc), h_slot_off(nc), h_block_cell;
+  t2_dbg(s, __LINE__);
+  std::vector<int> h_cnt(nc), h_slot_off, h_block_cell;
   SCAMD_READBACK_NOW(h_cnt.data(), cnt2, sizeof(int) * nc, s);
-  int64_t slots = 0;
-  for (int c = 0; c < nc; ++c) {
-    h_slot_off[c] = (int)slots;
-    const int nb = (h_cnt[c] + 127) / 128;
-    for (int t = 0; t < nb; ++t) h_block_cell.push_back(c);
-    slots += (int64_t)nb * 128;
-  }
+  const int64_t slots = layout_query_blocks(h_cnt, &h_slot_off, &h_block_cell);
   const int n_blocks = (int)h_block_cell.size();
   if (n_blocks == 0) return SCAMD_OK;
   SCAMD_REQUIRE(slots <= p.n_slot_max, SCAMD_EWORKSPACE, "knn: second-tier query layout exceeds its bound");
@@ -2926,58 +2959,37 @@ static int run_ivf_tier2(const KnnPlan& p, const KnnBuffers& b, const float* x, 
   hipLaunchKernelGGL(ivf_t2_fill_kernel, dim3((unsigned)ceil_div(n_flag, 256)), dim3(256), 0, s, b.flag_list, n_flag, b.t2_cell,
                      b.t2_pos, slot_off2, b.qrow, b.qpos);
   SCAMD_LAUNCH_CHECK();
-  T2_DBG(__LINE__);
+  t2_dbg(s, __LINE__);
   hipLaunchKernelGGL(knn_iota_kernel, dim3((unsigned)ceil_div(n_blocks, 256)), dim3(256), 0, s, b.block_perm, n_blocks);
   SCAMD_LAUNCH_CHECK();
-  T2_DBG(__LINE__);
-  {
-    const int blocks = (int)std::min<int64_t>((rows + 3) / 4, 256 * 16);
-    hipLaunchKernelGGL(ivf_pack_image_kernel, dim3(blocks), dim3(256), 0, s, x, b.mu, d, ld, 25, C::HP, C::DPL, rows, b.perm,
-                       b.labels, cell_map, b.cent, b.xp2, b.cmax, b.radius_bits, 0);
-    SCAMD_LAUNCH_CHECK();
-  T2_DBG(__LINE__);
-  }
+  t2_dbg(s, __LINE__);
+  const int blocks = (int)std::min<int64_t>((rows + 3) / 4, 256 * 16);
+  hipLaunchKernelGGL(ivf_pack_image_kernel, dim3(blocks), dim3(256), 0, s, c.x, b.mu, c.d, c.ld, 25, C::HP, C::DPL, rows, b.perm,
+                     b.labels, t.cell_map, b.cent, b.xp2, b.cmax, b.radius_bits, 0);
+  SCAMD_LAUNCH_CHECK();
+  t2_dbg(s, __LINE__);
   auto kern = knn_select_reg_kernel<25, 64, 3, true, false>;
   const size_t lds = C::LDS_BYTES + 64 + IVF_META_BYTES;
   SCAMD_HIP_CHECK(hipFuncSetAttribute(reinterpret_cast<const void*>(kern), hipFuncAttributeMaxDynamicSharedMemorySize,
                                       (int)lds));
-  IvfArgs iv;
-  iv.qpos = b.qpos;
-  iv.block_cell = b.block_cell;
-  iv.cell_tile0 = tile0;
-  iv.cell_ntiles = ntiles;
-  iv.centers = b.cent;
-  iv.radius = reinterpret_cast<const float*>(b.radius_bits);
-  iv.order = b.cell_order;
-  iv.order_lb2 = b.cell_lb2;
-  iv.perm = b.perm;
-  iv.cmax_bits = b.cmax;
+  IvfArgs iv = ivf_args(b, t, nc, c.d);
   iv.pairs = reinterpret_cast<unsigned long long*>(ctr2 + 2);
-  iv.n_cells = nc;
-  iv.dc = d;
-  iv.d = d;
-  iv.block_perm = b.block_perm;
-  iv.qorder = nullptr;
   iv.prepass_tiles = 16;
   iv.prepass_min2 = 1;
-  iv.trace = nullptr;
-  iv.queue_ctr = nullptr;  // (a few hundred queries: one workgroup per block)
-  iv.n_slots = n_blocks;
+  iv.n_slots = n_blocks;  // (a few hundred queries: one workgroup per block, no queues)
   const int thr_rank = std::min(32, std::max(1, k + 6));
-  hipLaunchKernelGGL(kern, dim3(n_blocks), dim3(C::NT), lds, s, b.xp2, (int)(rows / 64), rows, q_begin, thr_rank, b.cand_idx,
+  hipLaunchKernelGGL(kern, dim3(n_blocks), dim3(C::NT), lds, s, b.xp2, (int)(rows / 64), rows, c.q_begin, thr_rank, b.cand_idx,
                      b.cand_tau, iv);
   SCAMD_LAUNCH_CHECK();
-  T2_DBG(__LINE__);
-  {
-    const size_t rlds = rerank_rows_lds_bytes(d, thr_rank - 1);
-    SCAMD_HIP_CHECK(hipFuncSetAttribute(reinterpret_cast<const void*>(knn_rerank_rows_kernel),
-                                        hipFuncAttributeMaxDynamicSharedMemorySize, (int)rlds));
-    hipLaunchKernelGGL(knn_rerank_rows_kernel, dim3((unsigned)ceil_div(n_flag, 8)), dim3(256), rlds, s, x, b.mu, n, d, ld,
-                       q_begin, n_query, k, std::max(1, thr_rank - 1), b.cand_idx, b.cand_tau, b.cmax, cert_scale, CERT_K_F32,
-                       0.0, out_idx, out_dist, b.kth_d2, b.flag_list2, ctr2, (const int*)b.flag_list, (int64_t)n_flag);
-  }
+  t2_dbg(s, __LINE__);
+  const size_t rlds = rerank_rows_lds_bytes(c.d, thr_rank - 1);
+  SCAMD_HIP_CHECK(hipFuncSetAttribute(reinterpret_cast<const void*>(knn_rerank_rows_kernel),
+                                      hipFuncAttributeMaxDynamicSharedMemorySize, (int)rlds));
+  hipLaunchKernelGGL(knn_rerank_rows_kernel, dim3((unsigned)ceil_div(n_flag, 8)), dim3(256), rlds, s, c.x, b.mu, c.n, c.d, c.ld,
+                     c.q_begin, c.n_query, k, std::max(1, thr_rank - 1), b.cand_idx, b.cand_tau, b.cmax, cert_scale, CERT_K_F32,
+                     0.0, out_idx, out_dist, b.kth_d2, b.flag_list2, ctr2, (const int*)b.flag_list, (int64_t)n_flag);
   SCAMD_LAUNCH_CHECK();
-  T2_DBG(__LINE__);
+  t2_dbg(s, __LINE__);
   SCAMD_READBACK_NOW(n_flag2_host, ctr2, sizeof(int), s);
   return SCAMD_OK;
 }
@@ -3078,23 +3090,23 @@ static int knn_l2_impl(const float* x, int64_t n, int d, int64_t ld_x, int64_t q
     }
     SCAMD_LAUNCH_CHECK();
   }
+  const KnnCall call{x, n, d, ld_x, q_begin, n_query, s};
   int64_t ivf_layout[2] = {0, 0};  // image rows, query slots of the pruned sweep
   hipEvent_t ev0 = nullptr, ev1 = nullptr;
   SCAMD_HIP_CHECK(hipEventCreate(&ev0));
+  const EventOwner own0(ev0);
   SCAMD_HIP_CHECK(hipEventCreate(&ev1));
-  int rc;
+  const EventOwner own1(ev1);
   if (p.ivf) {
-    rc = dispatch_ivf(p, b, x, n, d, ld_x, q_begin, n_query, s, ev0, ev1, ivf_layout);
+    if (int rc = dispatch_ivf(p, b, call, ev0, ev1, ivf_layout)) return rc;
   } else {
     SCAMD_HIP_CHECK(hipEventRecord(ev0, s));
-    rc = dispatch_select(p, b, q_begin, s);
-    if (rc == SCAMD_OK && hipEventRecord(ev1, s) != hipSuccess) rc = SCAMD_EHIP;
+    if (int rc = dispatch_select(p, b, q_begin, s)) return rc;
+    SCAMD_HIP_CHECK(hipEventRecord(ev1, s));
   }
-  if (rc != SCAMD_OK) {
-    (void)hipEventDestroy(ev0);
-    (void)hipEventDestroy(ev1);
-    return rc;
-  }
+  // certificate factors of the engine that swept (d > 128: 2 * (H - 64) more accumulated terms, float32 engine only)
+  const double cert_k = p.b3 ? CERT_K_B3 : CERT_K_F32 + (p.H > 64 ? 2.0 * (p.H - 64) : 0.0);
+  const double cert_k2 = p.b3 ? CERT_K2_B3 : 0.0;
   if (p.reg && p.KP == 32 && d <= 64) {
     // register-list kernels: sorted lists, row-wise re-rank of the entries below the threshold, in slot order when pruned
     const int n_rank = std::max(1, p.thr_rank - 1);
@@ -3103,21 +3115,17 @@ static int knn_l2_impl(const float* x, int64_t n, int d, int64_t ld_x, int64_t q
     SCAMD_HIP_CHECK(hipFuncSetAttribute(reinterpret_cast<const void*>(knn_rerank_rows_kernel),
                                         hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
     hipLaunchKernelGGL(knn_rerank_rows_kernel, dim3((unsigned)ceil_div(n_list, 8)), dim3(256), lds, s, x, b.mu, n, d, ld_x,
-                       q_begin, n_query, k, n_rank, b.cand_idx, b.cand_tau, b.cmax, cert_scale,
-                       p.b3 ? CERT_K_B3 : CERT_K_F32, p.b3 ? CERT_K2_B3 : 0.0, out_idx, out_dist, b.kth_d2, b.flag_list,
-                       b.counters, p.ivf ? (const int*)b.qorder : (const int*)nullptr, n_list);
+                       q_begin, n_query, k, n_rank, b.cand_idx, b.cand_tau, b.cmax, cert_scale, cert_k, cert_k2, out_idx,
+                       out_dist, b.kth_d2, b.flag_list, b.counters, p.ivf ? (const int*)b.qorder : (const int*)nullptr, n_list);
     SCAMD_LAUNCH_CHECK();
   } else {
-    int blocks = (int)((n_query + 3) / 4);
-#define RERANK(KP_)                                                                              \
-  hipLaunchKernelGGL(knn_rerank_kernel<KP_>, dim3(blocks), dim3(256), 0, s, x, b.mu, n, d, ld_x, q_begin, \
-                     n_query, k, b.cand_idx, b.cand_tau, b.cmax, cert_scale, p.b3 ? CERT_K_B3 : CERT_K_F32 + (p.H > 64 ? 2.0 * (p.H - 64) : 0.0), p.b3 ? CERT_K2_B3 : 0.0, out_idx, out_dist,  \
-                     b.kth_d2, b.flag_list, b.counters, (const int*)nullptr, 0)
-    if (p.KP == 32) RERANK(32);
-    else if (p.KP == 64) RERANK(64);
-    else if (p.KP == 128) RERANK(128);
-    else RERANK(288);
-#undef RERANK
+    auto rerank = knn_rerank_kernel<32>;
+    if (p.KP == 64) rerank = knn_rerank_kernel<64>;
+    else if (p.KP == 128) rerank = knn_rerank_kernel<128>;
+    else if (p.KP != 32) rerank = knn_rerank_kernel<288>;
+    hipLaunchKernelGGL(rerank, dim3((unsigned)((n_query + 3) / 4)), dim3(256), 0, s, x, b.mu, n, d, ld_x, q_begin, n_query, k,
+                       b.cand_idx, b.cand_tau, b.cmax, cert_scale, cert_k, cert_k2, out_idx, out_dist, b.kth_d2, b.flag_list,
+                       b.counters, (const int*)nullptr, 0);
     SCAMD_LAUNCH_CHECK();
   }
   int h_counters[8] = {0, 0, 0, 0, 0, 0, 0, 0};
@@ -3126,8 +3134,6 @@ static int knn_l2_impl(const float* x, int64_t n, int d, int64_t ld_x, int64_t q
     float ms = -1.f;
     if (hipEventElapsedTime(&ms, ev0, ev1) != hipSuccess) ms = -1.f;
     g_last_select_ms = ms;
-    (void)hipEventDestroy(ev0);
-    (void)hipEventDestroy(ev1);
     unsigned long long pairs = 0;
     memcpy(&pairs, &h_counters[2], 8);
     g_last_select_pairs = p.ivf ? (double)pairs : (double)n_query * (double)n;
@@ -3140,20 +3146,14 @@ static int knn_l2_impl(const float* x, int64_t n, int d, int64_t ld_x, int64_t q
   int n_flag = h_counters[0];
   const int* flag_list = b.flag_list;
   g_last_second_tier = 0;
-  if (p.ivf && p.b3) {
-    // second tier: the float32 engine on what the bf16 engine's certificate rejected (SCAMD_KNN_TIER2_MIN, default 256
-    // queries: below that the float64 scan of a few queries is cheaper than a second image)
-    const char* e = getenv("SCAMD_KNN_TIER2_MIN");
-    const int t2_min = e ? atoi(e) : 256;
-    if (n_flag > t2_min) {
-      int n_flag2 = 0;
-      rc = run_ivf_tier2(p, b, x, n, d, ld_x, q_begin, n_query, k, cert_scale, n_flag, ivf_layout[0], out_idx, out_dist, s,
-                         &n_flag2);
-      if (rc != SCAMD_OK) return rc;
-      g_last_second_tier = n_flag;
-      n_flag = n_flag2;
-      flag_list = b.flag_list2;
-    }
+  // second tier: the float32 engine on what the bf16 engine's certificate rejected (SCAMD_KNN_TIER2_MIN, default 256
+  // queries: below that the float64 scan of a few queries is cheaper than a second image)
+  if (p.ivf && p.b3 && n_flag > env_int("SCAMD_KNN_TIER2_MIN", 256)) {
+    int n_flag2 = 0;
+    if (int rc = run_ivf_tier2(p, b, call, k, cert_scale, n_flag, ivf_layout[0], out_idx, out_dist, &n_flag2)) return rc;
+    g_last_second_tier = n_flag;
+    n_flag = n_flag2;
+    flag_list = b.flag_list2;
   }
   if (n_fallback_host) *n_fallback_host = n_flag;
   // float64 scan of what is left; a query whose table overflowed comes back with a tighter bound (knn_fallback_rank_kernel)
@@ -3167,13 +3167,12 @@ static int knn_l2_impl(const float* x, int64_t n, int d, int64_t ld_x, int64_t q
       int count = std::min(FALLBACK_CHUNK, n_todo - begin);
       SCAMD_HIP_CHECK(hipMemsetAsync(b.fb_counts, 0, sizeof(int) * count, s));
       if (p.ivf) {
-        // cell tables of run_ivf_select (same carving): tile0 = cell_ints + 7 nc, ntiles = the recycled sums buffer
         const int nc = p.n_cells;
+        const CellTables t = cell_tables(b, nc);
         // (few queries: one workgroup per cell and query -- a launch lasts as long as its busiest workgroup)
         hipLaunchKernelGGL(knn_fallback_scan_cells_kernel, dim3(count <= 128 ? nc : std::min(nc, 64), count), dim3(256), 0, s, x, d, ld_x, q_begin,
                            todo, begin, b.kth_d2, b.kth_idx, b.scratch_d, b.scratch_i, b.fb_counts, b.cent,
-                           reinterpret_cast<const float*>(b.radius_bits), b.cell_ints + 7 * nc,
-                           reinterpret_cast<const int*>(b.sums), b.perm, nc);
+                           t.radius, t.tile0, t.ntiles, b.perm, nc);
       } else {
         const int chunks = (int)std::max<int64_t>(1, std::min<int64_t>(FALLBACK_ROW_CHUNKS, n / 2048));
         hipLaunchKernelGGL(knn_fallback_scan_kernel, dim3(chunks, count), dim3(256), 0, s, x, n, d, ld_x, q_begin,
