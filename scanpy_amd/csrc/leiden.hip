@@ -35,12 +35,14 @@ namespace scamd {
 // [8] local-moving sweeps of the levels that run as separate kernels (all iterations), [9] their algorithmic traffic in MB:
 //     active rows x (12 B per entry + 16 B per vertex), SURVEY.md 8(d)'s per-sweep figure restricted to the rows a sweep visits,
 // [10] communities the polish split off because a departure had cut them in two, [11] 1 if the iteration cap ended the run,
-// [12] 1 if a polish pass stopped at MAX_POLISH_ROUNDS (node optimality then NOT proven), [13] the iteration cap in force
+// [12] 1 if a polish pass stopped at MAX_POLISH_ROUNDS (node optimality then NOT proven), [13] the iteration cap in force,
+// [16] levels that took their coarse graph from the stored hierarchy instead of refining and aggregating (LevelStore),
+// [17] iterations that ran on the stored hierarchy to its end without a move at any level
 // table slots of a vertex of the sixteen-lanes-per-vertex kernels (the kNN graph itself); rows longer than 3/4 of them go to
 // the wave-per-vertex tier
 constexpr int G16_SLOTS = 128;
 constexpr int G16_MAX = G16_SLOTS * 3 / 4;
-constexpr int LD_NSTATS = 16;
+constexpr int LD_NSTATS = 18;
 static thread_local int g_ld_stats[LD_NSTATS] = {0};
 static thread_local double g_ld_sweep_bytes = 0.0;  // -> stats[9] (MB)
 #undef SCAMD_LAUNCH_CHECK
@@ -1520,6 +1522,43 @@ __global__ __launch_bounds__(1024) void ld_coarse_ids_kernel(int n, const int* _
   for (int i = threadIdx.x; i < BH_SLOTS; i += 1024)
     if (keys[i] != BH_EMPTY) atomicMin(&rep[keys[i]], mn[i]);
 }
+// the same representatives from a STORED vertex map (a level that reuses the stored hierarchy: no refinement has run, `cid` is
+// the map of the iteration that built the level)
+__global__ __launch_bounds__(1024) void ld_coarse_rep_kernel(int n, const int* __restrict__ cid, const int* __restrict__ comm,
+                                                             int* __restrict__ rep) {
+  __shared__ int keys[BH_SLOTS];
+  __shared__ int mn[BH_SLOTS];
+  for (int i = threadIdx.x; i < BH_SLOTS; i += 1024) {
+    keys[i] = BH_EMPTY;
+    mn[i] = 0x7fffffff;
+  }
+  __syncthreads();
+  const int v = blockIdx.x * 1024 + threadIdx.x;
+  if (v < n) {
+    const int c = cid[v];
+    const int cm = comm[v];
+    const int slot = bh_find_slot(keys, cm);
+    if (slot >= 0) atomicMin(&mn[slot], c);
+    else atomicMin(&rep[cm], c);
+  }
+  __syncthreads();
+  for (int i = threadIdx.x; i < BH_SLOTS; i += 1024)
+    if (keys[i] != BH_EMPTY) atomicMin(&rep[keys[i]], mn[i]);
+}
+// SCAMD_LEIDEN_DEBUG, before a level is reused: the stored groups must be nested in the current partition.  Pass 0 notes the
+// community of one member per group (whichever write lands), pass 1 compares every member against it.
+__global__ void ld_nest_check_kernel(int n, int nn, const int* __restrict__ cid, const int* __restrict__ comm,
+                                     int* __restrict__ group_comm, int pass, int* __restrict__ err) {
+  const int v = blockIdx.x * blockDim.x + threadIdx.x;
+  if (v >= n) return;
+  const int c = cid[v];
+  if (c < 0 || c >= nn) {
+    if (pass == 0) atomicOr(err, 2);
+    return;
+  }
+  if (pass == 0) group_comm[c] = comm[v];
+  else if (group_comm[c] != comm[v]) atomicOr(err, 1);
+}
 __global__ void ld_coarse_comm_kernel(int n, const int* __restrict__ cid, const int* __restrict__ comm,
                                       const int* __restrict__ rep, int* __restrict__ comm_new, int nn,
                                       int* __restrict__ cursor, int* __restrict__ counters) {
@@ -2515,9 +2554,22 @@ struct CoarseBuf {
   int64_t* indptr; int* indices; long long* wq; long long* k;
 };
 
+// The coarse levels of an iteration are built one behind the other into ONE pool (what used to be two ping-pong buffers
+// of E entries): the hierarchy of the best partition stays there, and a later iteration whose local moving moves nothing
+// takes its levels from it (leiden_iteration).  Level l >= 1 = the graph of the level + the vertex map (l - 1) -> l.
+struct StoredLevel {
+  LevelGraph g;
+  size_t e_off = 0, p_off = 0, c_off = 0;  // first entry / first row pointer and vertex weight / first map element
+  size_t c_n = 0;                          // map elements (vertices of the level below)
+  const int* cid = nullptr;                // the map (n of the level below elements): in the pool, or b.cid for a level off the store
+};
+constexpr size_t POOL_ALIGN = 64;  // (elements: levels start on 256-byte boundaries like the buffers they replaced)
+
 struct LeidenBuffers {
   long long* wq0; long long* k0;
-  CoarseBuf cb[2];
+  CoarseBuf pool;          // 2 (N + 1) row pointers and vertex weights, 2 E entries
+  int* cid_pool;           // 2 N map elements
+  int* sm_ix[2]; long long* sm_w[2];  // coarse levels of ld_small_levels_kernel (SMALL_NNZ entries each): it leaves the pool alone
   int* comm; int* csize; unsigned long long* Ktot;
   int* cls_lists; int* rlist; int* touched; int* hub_list;
   int* ref; int* target; int* target2; int* refsize; unsigned long long* Kref; unsigned long long* Eref; long long* a_in;
@@ -2546,11 +2598,14 @@ static void leiden_carve(Workspace& ws, int64_t n, int64_t nnz, LeidenBuffers* b
   const size_t N = (size_t)n, E = (size_t)std::max<int64_t>(nnz, 1);
   b->wq0 = ws.take<long long>(E);
   b->k0 = ws.take<long long>(N);
+  b->pool.indptr = ws.take<int64_t>(2 * (N + 1));
+  b->pool.indices = ws.take<int>(2 * E);
+  b->pool.wq = ws.take<long long>(2 * E);
+  b->pool.k = ws.take<long long>(2 * (N + 1));
+  b->cid_pool = ws.take<int>(2 * N);
   for (int i = 0; i < 2; ++i) {
-    b->cb[i].indptr = ws.take<int64_t>(N + 1);
-    b->cb[i].indices = ws.take<int>(E);
-    b->cb[i].wq = ws.take<long long>(E);
-    b->cb[i].k = ws.take<long long>(N);
+    b->sm_ix[i] = ws.take<int>(SMALL_NNZ);
+    b->sm_w[i] = ws.take<long long>(SMALL_NNZ);
   }
   b->comm = ws.take<int>(N);
   b->csize = ws.take<int>(N);
@@ -2656,6 +2711,18 @@ struct LeidenCtx {
   int agg_wave_work = 2048;
   int agg_mid_work = 65536;
   int hub_try_probes = HUB_TRY_PROBES;  // 0: no optimistic single pass over multi-pass rows (SCAMD_LEIDEN_HUB_TRY_PROBES; tests)
+  // ---- the stored hierarchy (StoredLevel) ----
+  size_t cap_e = 0, cap_p = 0, cap_c = 0;  // pool capacities: entries, row pointers / vertex weights, map elements
+  StoredLevel lv[MAX_LEVELS + 1];          // [l], l >= 1: level l as the running iteration sees it
+  bool reuse = true;      // SCAMD_LEIDEN_REUSE=0: every iteration refines and aggregates every level (test hook, A/B)
+  int depth = 0;          // levels 1 .. depth of the pool belong to the hierarchy that produced b.memb
+  int end_level = -1;     // that hierarchy ended at this level ...
+  int end_kind = 0;       // ... 1: its refinement merged nothing, 2: its aggregation merged nothing (0: otherwise)
+  // of the running iteration (leiden_run commits them when it accepts the iteration's partition)
+  int it_built = 0;       // its levels 1 .. it_built sit in the pool one behind the other (-1: a level did not fit)
+  int it_end_level = -1, it_end_kind = 0;
+  bool it_quiet = false;  // it ran on the stored hierarchy to its end and no separate-kernel level moved anything
+  int it_small_moves = 0; // moves inside ld_small_levels_kernel (fetched when it_quiet, handed out by quality()'s sync)
 };
 
 static bool g_leiden_debug = false;  // SCAMD_LEIDEN_DEBUG=1, read at every entry (tools switch it inside one process)
@@ -3160,9 +3227,50 @@ static int refinement(LeidenCtx& cx, const LevelGraph& g, int* n_merged) {
   return SCAMD_OK;
 }
 
-// builds the coarse graph of `g` under b.ref into cb[dst]; updates b.comm (coarse phase-1 partition)
-// and b.node_of.  Returns the new node count in *n_new (== g.n means nothing merged: no graph built).
-static int aggregate(LeidenCtx& cx, const LevelGraph& g, int n_orig, int dst, LevelGraph* out, int* n_new) {
+// Where level `level` + 1 (nn vertices, at most g.nnz entries, a map of g.n elements) goes: behind level `level` in the pool
+// while the iteration's levels sit there one behind the other and the next one fits.  The first that does not fit gives the
+// store up (depth 0: it is written over the lowest levels) and the rest of the iteration alternates between two places that
+// are free of its source, as the two buffers of E entries did.  Whatever is written over stops belonging to the stored
+// hierarchy HERE, before the first launch that writes.
+static int place_level(LeidenCtx& cx, const LevelGraph& g, int level, int nn, StoredLevel* out) {
+  LeidenBuffers& b = cx.b;
+  const bool ext = level == 0;  // (the level-0 graph is the caller's)
+  const StoredLevel& src = cx.lv[level];
+  const size_t need_e = (size_t)std::max<int64_t>(g.nnz, 1), need_p = (size_t)nn + 1, need_c = (size_t)g.n;
+  StoredLevel d;
+  d.c_n = need_c;
+  if (cx.it_built == level) {
+    d.e_off = ext ? 0 : align_up(src.e_off + (size_t)src.g.nnz, POOL_ALIGN);
+    d.p_off = ext ? 0 : align_up(src.p_off + (size_t)src.g.n + 1, POOL_ALIGN);
+    d.c_off = ext ? 0 : align_up(src.c_off + src.c_n, POOL_ALIGN);
+    if (d.e_off + need_e <= cx.cap_e && d.p_off + need_p <= cx.cap_p && d.c_off + need_c <= cx.cap_c) {
+      d.cid = b.cid_pool + d.c_off;
+      cx.it_built = level + 1;
+      cx.depth = std::min(cx.depth, level);
+      *out = d;
+      return SCAMD_OK;
+    }
+    cx.it_built = -1;
+    if (leiden_debug()) fprintf(stderr, "[leiden] level %d does not fit behind level %d in the pool: the hierarchy is not kept\n", level + 1, level);
+  }
+  cx.depth = 0;
+  d.e_off = (ext || src.e_off >= need_e) ? 0 : cx.cap_e / 2;
+  d.p_off = (ext || src.p_off >= need_p) ? 0 : cx.cap_p / 2;
+  d.c_off = 0;
+  d.cid = b.cid;
+  // (a source in the pool has every lower level before it, each at least its size; one off the pool sits at 0 or at half)
+  SCAMD_REQUIRE(d.e_off + need_e <= cx.cap_e && d.p_off + need_p <= cx.cap_p &&
+                    (ext || d.e_off + need_e <= src.e_off || d.e_off >= src.e_off + (size_t)src.g.nnz) &&
+                    (ext || d.p_off + need_p <= src.p_off || d.p_off >= src.p_off + (size_t)src.g.n + 1),
+                SCAMD_EINTERNAL, "leiden: no room for level %d beside its source", level + 1);
+  *out = d;
+  return SCAMD_OK;
+}
+
+// builds the coarse graph of `g` (level `level`) under b.ref into the pool (place_level) and records it as cx.lv[level + 1];
+// updates b.comm (coarse phase-1 partition) and b.node_of.  Returns the new node count in *n_new (== g.n means nothing
+// merged: no graph built).
+static int aggregate(LeidenCtx& cx, const LevelGraph& g, int n_orig, int level, LevelGraph* out, int* n_new) {
   LeidenBuffers& b = cx.b;
   hipLaunchKernelGGL(ld_flag_kernel, GRID1(g.n), 0, cx.s, g.n, b.refsize, b.flag, b.rep);  // (+ b.rep = the atomicMin sentinel)
   SCAMD_LAUNCH_CHECK();
@@ -3173,26 +3281,30 @@ static int aggregate(LeidenCtx& cx, const LevelGraph& g, int n_orig, int dst, Le
   LD_SYNC(cx.s);
   *n_new = (int)nn;
   if (nn == g.n) return SCAMD_OK;
-  hipLaunchKernelGGL(ld_coarse_ids_kernel, GRIDK(g.n), 0, cx.s, g.n, b.ref, b.newid, b.comm, b.cid, b.rep);
+  StoredLevel sl;
+  rc = place_level(cx, g, level, (int)nn, &sl);
+  if (rc != SCAMD_OK) return rc;
+  int* cid = const_cast<int*>(sl.cid);
+  hipLaunchKernelGGL(ld_coarse_ids_kernel, GRIDK(g.n), 0, cx.s, g.n, b.ref, b.newid, b.comm, cid, b.rep);
   SCAMD_LAUNCH_CHECK();
   // (+ the cursors of the member scatter and the phase counters cleared: two memsets until round 6)
-  hipLaunchKernelGGL(ld_coarse_comm_kernel, GRID1(g.n), 0, cx.s, g.n, b.cid, b.comm, b.rep, b.comm_tmp, (int)nn, b.cursor, b.counters);
+  hipLaunchKernelGGL(ld_coarse_comm_kernel, GRID1(g.n), 0, cx.s, g.n, cid, b.comm, b.rep, b.comm_tmp, (int)nn, b.cursor, b.counters);
   SCAMD_LAUNCH_CHECK();
-  hipLaunchKernelGGL(ld_remap_kernel, GRID1(n_orig), 0, cx.s, n_orig, b.cid, b.node_of);
+  hipLaunchKernelGGL(ld_remap_kernel, GRID1(n_orig), 0, cx.s, n_orig, cid, b.node_of);
   SCAMD_LAUNCH_CHECK();
   // group the members of every coarse node, then combine their rows per coarse node in LDS
   hipLaunchKernelGGL(ld_agg_mcount_kernel, GRID1(g.n), 0, cx.s, g.n, b.refsize, b.newid, b.mcount);
   SCAMD_LAUNCH_CHECK();
   rc = exclusive_scan_i32_i64(b.mcount, nn, b.moff, b.scan_tmp, cx.s);
   if (rc != SCAMD_OK) return rc;
-  hipLaunchKernelGGL(ld_agg_scatter_kernel, GRID1(g.n), 0, cx.s, g.n, b.cid, b.moff, b.cursor, g.indptr, b.members,
+  hipLaunchKernelGGL(ld_agg_scatter_kernel, GRID1(g.n), 0, cx.s, g.n, cid, b.moff, b.cursor, g.indptr, b.members,
                      b.mdeg);
   SCAMD_LAUNCH_CHECK();
   rc = exclusive_scan_i32_i64(b.mdeg, g.n, b.eoff, b.scan_tmp, cx.s);
   if (rc != SCAMD_OK) return rc;
   const int inn = (int)nn;
   hipLaunchKernelGGL(ld_agg_wave_kernel, GRIDW(inn), 0, cx.s, inn, b.moff, b.eoff, b.members, g.indptr, g.indices, g.wq,
-                     b.cid, b.agg_col, b.agg_w, b.rowcnt, b.mid_list, b.big_list, b.counters, cx.agg_wave_max,
+                     cid, b.agg_col, b.agg_w, b.rowcnt, b.mid_list, b.big_list, b.counters, cx.agg_wave_max,
                      cx.agg_mid_max, cx.agg_wave_work, cx.agg_mid_work, b.hub_list, agg_split_work());
   SCAMD_LAUNCH_CHECK();
   // workgroup tiers: 512 threads on the 48 KB tables (3 per CU), 1024 threads on the 96 KB table (1 per CU).  Their list
@@ -3207,13 +3319,13 @@ static int aggregate(LeidenCtx& cx, const LevelGraph& g, int n_orig, int dst, Le
   if (htier[0] > 0) {
     hipLaunchKernelGGL((ld_agg_block_kernel<AGG_MID_SLOTS, 512>), dim3((unsigned)std::min(AGG_MID_GRID, htier[0])), dim3(512),
                        (size_t)AGG_MID_SLOTS * 12, cx.s, b.mid_list, b.counters + 4, inn, b.moff, b.eoff, b.members, g.indptr,
-                       g.indices, g.wq, b.cid, b.agg_col, b.agg_w, b.rowcnt, b.counters + 7, AGG_MID_MAX, cx.hub_try_probes);
+                       g.indices, g.wq, cid, b.agg_col, b.agg_w, b.rowcnt, b.counters + 7, AGG_MID_MAX, cx.hub_try_probes);
     SCAMD_LAUNCH_CHECK();
   }
   if (htier[1] > 0) {
     hipLaunchKernelGGL((ld_agg_block_kernel<BHUB_SLOTS, 1024>), dim3((unsigned)std::min(HUB_GRID, htier[1])), dim3(1024),
                        HUB_LDS, cx.s, b.big_list, b.counters + 5, inn, b.moff, b.eoff, b.members, g.indptr, g.indices, g.wq,
-                       b.cid, b.agg_col, b.agg_w, b.rowcnt, b.counters + 7, cx.agg_pass_keys, cx.hub_try_probes);
+                       cid, b.agg_col, b.agg_w, b.rowcnt, b.counters + 7, cx.agg_pass_keys, cx.hub_try_probes);
     SCAMD_LAUNCH_CHECK();
   }
   if (htier[2] > 0) {
@@ -3227,7 +3339,7 @@ static int aggregate(LeidenCtx& cx, const LevelGraph& g, int n_orig, int dst, Le
     const int64_t parts_bound = (int64_t)htier[2] + g.nnz / chunk + 1;
     hipLaunchKernelGGL((ld_agg_block_kernel<BHUB_SLOTS, 1024>), dim3((unsigned)std::min<int64_t>(HUB_GRID, parts_bound)), dim3(1024),
                        HUB_LDS, cx.s, (const int*)b.part_list, (const int*)(b.counters + 3), inn, (const int64_t*)b.pmoff, b.eoff,
-                       b.members, g.indptr, g.indices, g.wq, b.cid, b.agg_col, b.agg_w, b.part_cnt, b.counters + 7,
+                       b.members, g.indptr, g.indices, g.wq, cid, b.agg_col, b.agg_w, b.part_cnt, b.counters + 7,
                        cx.agg_pass_keys, cx.hub_try_probes);
     SCAMD_LAUNCH_CHECK();
     hipLaunchKernelGGL(ld_agg_merge_kernel, dim3((unsigned)std::min(HUB_GRID, htier[2])), dim3(1024), HUB_LDS, cx.s,
@@ -3235,7 +3347,7 @@ static int aggregate(LeidenCtx& cx, const LevelGraph& g, int n_orig, int dst, Le
                        (const int*)b.rlist, (const int*)b.touched, b.agg_col, b.agg_w, b.rowcnt, b.counters + 7);
     SCAMD_LAUNCH_CHECK();
   }
-  CoarseBuf& cb = b.cb[dst];
+  const CoarseBuf cb{b.pool.indptr + sl.p_off, b.pool.indices + sl.e_off, b.pool.wq + sl.e_off, b.pool.k + sl.p_off};
   rc = exclusive_scan_i32_i64(b.rowcnt, nn, cb.indptr, b.scan_tmp, cx.s);
   if (rc != SCAMD_OK) return rc;
   // the order of a row's entries is arbitrary: nothing downstream depends on it (all sums are integer, every
@@ -3254,7 +3366,7 @@ static int aggregate(LeidenCtx& cx, const LevelGraph& g, int n_orig, int dst, Le
   if (cx.cpm) {  // sizes add up over the members; strengths are the row sums of the coarse graph
     rc = run_fill(cx, Filler().add(cb.k, sizeof(long long) * nn));
     if (rc != SCAMD_OK) return rc;
-    hipLaunchKernelGGL(ld_agg_nodeweight_kernel, GRID1(g.n), 0, cx.s, g.n, (const int*)b.cid, g.k, cb.k);
+    hipLaunchKernelGGL(ld_agg_nodeweight_kernel, GRID1(g.n), 0, cx.s, g.n, (const int*)cid, g.k, cb.k);
   } else {
     hipLaunchKernelGGL(ld_strength_kernel, GRIDW(nn), 0, cx.s, cb.indptr, cb.wq, (int)nn, cb.k);
   }
@@ -3272,6 +3384,41 @@ static int aggregate(LeidenCtx& cx, const LevelGraph& g, int n_orig, int dst, Le
   out->indices = cb.indices;
   out->wq = cb.wq;
   out->k = cb.k;
+  sl.g = *out;
+  cx.lv[level + 1] = sl;
+  return SCAMD_OK;
+}
+
+// Level `level` takes its coarse graph and its vertex map from the stored hierarchy (no refinement, no aggregation): the
+// coarse partition and node_of as aggregate() leaves them, from the CURRENT b.comm.
+static int reuse_level(LeidenCtx& cx, const LevelGraph& g, int n_orig, int level, LevelGraph* out) {
+  LeidenBuffers& b = cx.b;
+  const StoredLevel& sl = cx.lv[level + 1];
+  const int nn = sl.g.n;
+  SCAMD_REQUIRE(sl.c_n == (size_t)g.n && nn >= 1 && nn < g.n, SCAMD_EINTERNAL, "leiden: stored level %d does not belong to a level of %d vertices",
+                level + 1, g.n);
+  if (leiden_debug()) {
+    // every stored group lies inside one community of b.comm (nothing has moved below: b.comm is the projection of b.memb)
+    for (int pass = 0; pass < 2; ++pass) {
+      hipLaunchKernelGGL(ld_nest_check_kernel, GRID1(g.n), 0, cx.s, g.n, nn, sl.cid, (const int*)b.comm, b.comm_tmp, pass, b.counters + 7);
+      SCAMD_LAUNCH_CHECK();
+    }
+    int bad = 0;
+    LD_FETCH(&bad, b.counters + 7, sizeof(int), cx.s);
+    LD_SYNC(cx.s);
+    SCAMD_REQUIRE(bad == 0, SCAMD_EINTERNAL, "leiden: the stored level %d is not nested in the partition it is reused for (%d)", level + 1, bad);
+  }
+  int rc = run_fill(cx, Filler().add(b.rep, sizeof(int) * (size_t)g.n, 0x7f7f7f7fu));
+  if (rc != SCAMD_OK) return rc;
+  hipLaunchKernelGGL(ld_coarse_rep_kernel, GRIDK(g.n), 0, cx.s, g.n, sl.cid, (const int*)b.comm, b.rep);
+  SCAMD_LAUNCH_CHECK();
+  hipLaunchKernelGGL(ld_coarse_comm_kernel, GRID1(g.n), 0, cx.s, g.n, sl.cid, (const int*)b.comm, (const int*)b.rep, b.comm_tmp, nn, b.cursor, b.counters);
+  SCAMD_LAUNCH_CHECK();
+  hipLaunchKernelGGL(ld_remap_kernel, GRID1(n_orig), 0, cx.s, n_orig, sl.cid, b.node_of);
+  SCAMD_LAUNCH_CHECK();
+  std::swap(b.comm, b.comm_tmp);
+  *out = sl.g;
+  ++g_ld_stats[16];
   return SCAMD_OK;
 }
 
@@ -3293,10 +3440,10 @@ static int small_levels(LeidenCtx& cx, const LevelGraph& g, int level) {
   a.k = g.k;
   a.n = g.n;
   for (int i = 0; i < 2; ++i) {
-    a.ix[i] = b.cb[i].indices;
-    a.w[i] = b.cb[i].wq;
+    a.ix[i] = b.sm_ix[i];
+    a.w[i] = b.sm_w[i];
   }
-  a.first_dst = level & 1;  // level L >= 1 lives in cb[(L - 1) & 1]
+  a.first_dst = 0;  // (the entry level lives in the pool or is the caller's graph)
   a.comm = b.comm;
   a.gg = cx.gscale();
   a.inv_beta = cx.inv_beta;
@@ -3318,12 +3465,23 @@ static int small_levels(LeidenCtx& cx, const LevelGraph& g, int level) {
 }
 
 // (from the partition in b.memb; the result goes to b.memb_work)
+// Reuse of the stored hierarchy (iterations after the first): while no level of this iteration has moved a vertex, b.comm is
+// the projection of b.memb, and the groups of the hierarchy that produced b.memb are nested in it -- such a level takes the
+// stored coarse graph and vertex map instead of refining and aggregating (reuse_level).  The first level that moves
+// anything, and every level above it, is refined and aggregated as ever and replaces the stored levels from there up.
 static int leiden_iteration(LeidenCtx& cx, const LevelGraph& g0) {
   LeidenBuffers& b = cx.b;
   hipLaunchKernelGGL(ld_iter_init_kernel, GRID1(g0.n), 0, cx.s, g0.n, (const int*)b.memb, b.comm, b.node_of);
   SCAMD_LAUNCH_CHECK();
   LevelGraph g = g0;
   cx.l0_moves = -1;  // (a graph small enough to start in the one-workgroup kernel reports no level-0 count)
+  bool quiet = cx.reuse && cx.iter >= 1;  // no level so far has moved anything
+  int reused = 0;
+  cx.it_built = 0;
+  cx.it_end_level = -1;
+  cx.it_end_kind = 0;
+  cx.it_quiet = false;
+  cx.it_small_moves = 0;
   for (int level = 0; level < MAX_LEVELS; ++level) {
     int moves = 0;
     const bool dbg = leiden_debug();
@@ -3332,6 +3490,11 @@ static int leiden_iteration(LeidenCtx& cx, const LevelGraph& g0) {
       const int rcs = small_levels(cx, g, level);
       if (rcs != SCAMD_OK) return rcs;
       if (dbg) fprintf(stderr, "[leiden] small levels %.2f ms\n", dbg_now(cx) - t0);
+      cx.it_end_level = level;
+      if (quiet && level >= 1 && reused == level) {  // (its move count: handed out by the synchronisation of the quality that follows)
+        cx.it_quiet = true;
+        LD_FETCH(&cx.it_small_moves, b.counters + 13, sizeof(int), cx.s);
+      }
       break;
     }
     int rc = local_moving(cx, g, &moves);
@@ -3339,6 +3502,30 @@ static int leiden_iteration(LeidenCtx& cx, const LevelGraph& g0) {
     if (level == 0) cx.l0_moves = moves;
     cx.n_levels = level + 1;
     const double t1 = dbg ? dbg_now(cx) : 0.0;
+    if (moves != 0) quiet = false;
+    if (quiet && cx.it_built == level && cx.depth >= level + 1) {
+      LevelGraph gs;
+      rc = reuse_level(cx, g, g0.n, level, &gs);
+      if (rc != SCAMD_OK) return rc;
+      cx.it_built = level + 1;
+      ++reused;
+      if (dbg)
+        fprintf(stderr, "[leiden] level %d n=%d nnz=%lld maxdeg=%d: local moving %.2f ms (%d moves), reused %.2f ms -> n=%d\n",
+                level, g.n, (long long)g.nnz, g.max_deg, t1 - t0, moves, dbg_now(cx) - t1, gs.n);
+      g = gs;
+      continue;
+    }
+    if (quiet && level >= 1 && reused == level && cx.it_built == level && cx.depth == level && cx.end_level == level && cx.end_kind != 0) {
+      // the stored hierarchy ended here because nothing merged: so does this one
+      if (dbg)
+        fprintf(stderr, "[leiden] level %d n=%d nnz=%lld maxdeg=%d: local moving %.2f ms (%d moves), reused: the last level\n",
+                level, g.n, (long long)g.nnz, g.max_deg, t1 - t0, moves);
+      cx.it_end_level = level;
+      cx.it_end_kind = cx.end_kind;
+      cx.it_quiet = true;
+      ++g_ld_stats[16];
+      break;
+    }
     int merged = 0;
     rc = refinement(cx, g, &merged);
     if (rc != SCAMD_OK) return rc;
@@ -3346,18 +3533,33 @@ static int leiden_iteration(LeidenCtx& cx, const LevelGraph& g0) {
     if (dbg)
       fprintf(stderr, "[leiden] level %d n=%d nnz=%lld maxdeg=%d: local moving %.2f ms (%d moves), refinement %.2f ms (%d merged)\n",
               level, g.n, (long long)g.nnz, g.max_deg, t1 - t0, moves, t2 - t1, merged);
-    if (merged == 0) break;
+    cx.it_end_level = level;
+    if (merged == 0) {
+      cx.it_end_kind = 1;
+      break;
+    }
     LevelGraph gn;
     int n_new = 0;
-    rc = aggregate(cx, g, g0.n, level & 1, &gn, &n_new);
+    rc = aggregate(cx, g, g0.n, level, &gn, &n_new);
     if (rc != SCAMD_OK) return rc;
     if (dbg) fprintf(stderr, "[leiden] level %d aggregate %.2f ms -> n=%d\n", level, dbg_now(cx) - t2, n_new);
-    if (n_new == g.n) break;
+    if (n_new == g.n) {
+      cx.it_end_kind = 2;
+      break;
+    }
+    cx.it_end_level = -1;
     g = gn;
   }
   hipLaunchKernelGGL(ld_gather_kernel, GRID1(g0.n), 0, cx.s, g0.n, b.comm, b.node_of, b.memb_work);
   SCAMD_LAUNCH_CHECK();
   return SCAMD_OK;
+}
+
+// the iteration's partition was accepted as b.memb: what it built or reused is the stored hierarchy now
+static void own_hierarchy(LeidenCtx& cx) {
+  cx.depth = std::max(cx.it_built, 0);
+  cx.end_level = cx.it_end_level;
+  cx.end_kind = cx.it_end_kind;
 }
 
 // b.memb (values < n) relabelled to consecutive ids ordered by (size desc, first member asc) -> out (the caller's buffer)
@@ -3543,6 +3745,10 @@ static int leiden_run(const int64_t* indptr, const int32_t* indices, const float
   cx.seed = (unsigned int)(seed ^ (seed >> 32)) * 0x9E3779B1u + 0x632BE5ABu;
   if (const char* e = getenv("SCAMD_LEIDEN_SMALL")) cx.small_levels = e[0] != '0';
   if (const char* e = getenv("SCAMD_LEIDEN_POLISH")) cx.polish = e[0] != '0';
+  if (const char* e = getenv("SCAMD_LEIDEN_REUSE")) cx.reuse = e[0] != '0';
+  cx.cap_e = 2 * (size_t)std::max<int64_t>(nnz, 1);
+  cx.cap_p = 2 * ((size_t)n + 1);
+  cx.cap_c = 2 * (size_t)n;
   cx.cpm = objective == 1;
   cx.node_weights = node_weights;
   if (cx.cpm) cx.small_levels = false;  // (ld_small_levels_kernel derives its coarse vertex weights from row sums: strengths)
@@ -3618,11 +3824,13 @@ static int leiden_run(const int64_t* indptr, const int32_t* indices, const float
       const bool improved = q > q_best + 1e-12;
       const bool worse = q < q_best - 1e-12;
       if (leiden_debug()) fprintf(stderr, "[leiden] iteration %d: Q = %.10f (best before %.10f)\n", it, q, q_best);
+      if (cx.it_quiet && cx.it_small_moves == 0) ++g_ld_stats[17];
       if (improved) {
         q_best = q;
         bad_iters = 0;
         best_is_clean = false;
         std::swap(b.memb, b.memb_work);
+        own_hierarchy(cx);
       } else {
         if (cx.l0_moves == 0) best_is_clean = true;
         // synchronous moves and the randomised refinement are not monotone: the best partition seen stays in b.memb
@@ -3660,6 +3868,7 @@ static int leiden_run(const int64_t* indptr, const int32_t* indices, const float
       g_ld_stats[5] += ps[2];
       g_ld_stats[10] += ps[3];
       if (ps[2] == 0) break;  // the full sweep found no improving move: node optimal as it stands
+      cx.depth = 0;  // b.memb changed in place: the stored hierarchy is no longer its own, the iteration below runs in full
       double q = 0.0;
       rc = compute_totals(cx, g0, b.memb);
       if (rc == SCAMD_OK) rc = quality(cx, g0, b.memb, &q);
@@ -3680,9 +3889,11 @@ static int leiden_run(const int64_t* indptr, const int32_t* indices, const float
       if (rc == SCAMD_OK) rc = quality(cx, g0, b.memb_work, &q);
       if (rc != SCAMD_OK) return rc;
       if (leiden_debug()) fprintf(stderr, "[leiden] iteration after polish %d: Q = %.10f (polished %.10f), level-0 moves %d\n", pr, q, q_best, cx.l0_moves);
+      if (cx.it_quiet && cx.it_small_moves == 0) ++g_ld_stats[17];
       if (q > q_best + 1e-12) {
         q_best = q;
         std::swap(b.memb, b.memb_work);
+        own_hierarchy(cx);
       } else {
         break;  // stable: the polished partition (b.memb) stands
       }
