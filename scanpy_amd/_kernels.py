@@ -508,12 +508,13 @@ def leiden(indptr: torch.Tensor, indices: torch.Tensor, weights: torch.Tensor, n
 
 def leiden_last_stats() -> dict:
     """Diagnostics of this thread's last `leiden` call (scamd_leiden_last_stats)."""
-    out = (C.c_int32 * 16)()
-    _lib.load().scamd_leiden_last_stats(out, 16)
+    out = (C.c_int32 * 20)()
+    _lib.load().scamd_leiden_last_stats(out, 20)
     keys = ("iterations", "launches", "host_round_trips", "polish_full_sweeps", "polish_rounds", "polish_moves",
             "polish_skipped_proven", "levels_first_iteration", "lm_sweeps", "lm_sweep_algorithmic_MB", "polish_splits",
-            "ended_by_iteration_cap", "polish_ended_by_round_cap", "iteration_cap", "device_copies", "device_fills")
-    return dict(zip(keys, (int(v) for v in out)))
+            "ended_by_iteration_cap", "polish_ended_by_round_cap", "iteration_cap", None, "device_fills",
+            "levels_reused", "quiet_reuse_iterations", "overflow_pass_vertices", "hub_pass_vertices")  # (slot 14 is unused)
+    return {k: int(v) for k, v in zip(keys, out) if k is not None}
 
 
 def modularity(indptr: torch.Tensor, indices: torch.Tensor, weights: torch.Tensor, n: int, membership: torch.Tensor,

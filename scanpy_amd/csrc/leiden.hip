@@ -26,6 +26,7 @@
 #include <cmath>
 #include <cstdlib>
 #include <ctime>
+#include <type_traits>
 
 namespace scamd {
 
@@ -36,13 +37,16 @@ namespace scamd {
 //     active rows x (12 B per entry + 16 B per vertex), SURVEY.md 8(d)'s per-sweep figure restricted to the rows a sweep visits,
 // [10] communities the polish split off because a departure had cut them in two, [11] 1 if the iteration cap ended the run,
 // [12] 1 if a polish pass stopped at MAX_POLISH_ROUNDS (node optimality then NOT proven), [13] the iteration cap in force,
+// [14] unused, [15] ld_fill_kernel launches,
 // [16] levels that took their coarse graph from the stored hierarchy instead of refining and aggregating (LevelStore),
-// [17] iterations that ran on the stored hierarchy to its end without a move at any level
+// [17] iterations that ran on the stored hierarchy to its end without a move at any level,
+// [18] vertices the 64-lane overflow pass took over from a 16- / 32-lane decide launch, [19] vertices handed to the hub pass
+//     (decide_tiers: local moving, polish and refinement together; the list builders' counts, so no read-back of their own)
 // table slots of a vertex of the sixteen-lanes-per-vertex kernels (the kNN graph itself); rows longer than 3/4 of them go to
 // the wave-per-vertex tier
 constexpr int G16_SLOTS = 128;
 constexpr int G16_MAX = G16_SLOTS * 3 / 4;
-constexpr int LD_NSTATS = 18;
+constexpr int LD_NSTATS = 20;
 static thread_local int g_ld_stats[LD_NSTATS] = {0};
 static thread_local double g_ld_sweep_bytes = 0.0;  // -> stats[9] (MB)
 #undef SCAMD_LAUNCH_CHECK
@@ -70,7 +74,12 @@ constexpr int MAX_LM_SWEEPS = 96;
 constexpr int LM_DIR_AFTER = 32;  // sweeps after which the direction rule (termination guarantee) is switched on
 constexpr int MAX_CLASSES = 32;   // most class sub-rounds per sweep (local moving) / per refinement
 constexpr int DEF_CLASSES = 8;    // default
-constexpr int CTR_STRIDE = 16;    // ints per sub-round counter block
+constexpr int CTR_STRIDE = 16;    // ints per sub-round counter block:
+// [CTR_JOINED] joiners of the sub-round (refinement); filled by the decide kernels: [CTR_HUB] rows handed to the hub kernel,
+// [CTR_OVF] rows handed to the 64-lane overflow pass; counted while the class lists are built (count_long_rows): [CTR_N_MID] /
+// [CTR_N_HUB] rows of the class longer than the lanes-per-vertex table / than the wave table
+constexpr int CTR_JOINED = 0, CTR_HUB = 4, CTR_OVF = 5, CTR_N_MID = 8, CTR_N_HUB = 9;
+constexpr int PHASE_ERR = 7;      // slot of the phase counters (LeidenBuffers::counters) a kernel raises when a table overflows
 // counter area of a sweep / a refinement: MAX_CLASSES class-list lengths, then one CTR_STRIDE block per sub-round
 constexpr int CTR_AREA = MAX_CLASSES + CTR_STRIDE * MAX_CLASSES;
 constexpr int MAX_LEVELS = 64;
@@ -129,32 +138,19 @@ __global__ __launch_bounds__(256) void ld_sum_kernel(const long long* __restrict
   if ((threadIdx.x & 63) == 0 && s != 0) atomicAdd(total, (unsigned long long)s);
 }
 
-// row-length statistics of a level: out[0] = longest row, out[1 .. 3] = rows longer than 96 / 192 / 384 entries (the
-// bounds of the quarter- / half- / full-wave tables: levels without such rows skip the overflow / hub launches, the
-// others size those grids by the counts)
+// out[0] = max(out[0], longest row of the level): levels without hubs skip the block-per-vertex kernels
 __global__ __launch_bounds__(1024) void ld_degstats_kernel(const int64_t* __restrict__ indptr, int n, int* __restrict__ out) {
-  // (one set of atomics per 1024-row block: a million rows through four same-address atomics per WAVE took 0.3 ms)
-  __shared__ int sh[4];
-  if (threadIdx.x < 4) sh[threadIdx.x] = 0;
+  // (one atomic per 1024-row block: a million rows through same-address atomics per WAVE took 0.3 ms)
+  __shared__ int sh;
+  if (threadIdx.x == 0) sh = 0;
   __syncthreads();
   int v = blockIdx.x * blockDim.x + threadIdx.x;
   int d = (v < n) ? (int)(indptr[v + 1] - indptr[v]) : 0;
-  const unsigned long long m1 = __ballot(d > G16_MAX), m2 = __ballot(d > 192), m3 = __ballot(d > 384);
 #pragma unroll
   for (int o = 32; o > 0; o >>= 1) d = max(d, __shfl_xor(d, o));
-  if ((threadIdx.x & 63) == 0 && d > 0) {
-    atomicMax(&sh[0], d);
-    if (m1) atomicAdd(&sh[1], __popcll(m1));
-    if (m2) atomicAdd(&sh[2], __popcll(m2));
-    if (m3) atomicAdd(&sh[3], __popcll(m3));
-  }
+  if ((threadIdx.x & 63) == 0 && d > 0) atomicMax(&sh, d);
   __syncthreads();
-  if (threadIdx.x == 0 && sh[0] > 0) {
-    atomicMax(out, sh[0]);
-    if (sh[1]) atomicAdd(out + 1, sh[1]);
-    if (sh[2]) atomicAdd(out + 2, sh[2]);
-    if (sh[3]) atomicAdd(out + 3, sh[3]);
-  }
+  if (threadIdx.x == 0 && sh > 0) atomicMax(out, sh);
 }
 
 __global__ void ld_iota_kernel(int* __restrict__ a, int n) {
@@ -303,15 +299,25 @@ __device__ __forceinline__ bool cand_better(const Cand& a, const Cand& b) {  // 
   if (a.pr != b.pr) return a.pr < b.pr;
   return a.c < b.c;
 }
-__device__ __forceinline__ Cand wave_best(Cand x) {
+__device__ __forceinline__ Cand cand_none() { return Cand{0.0, -1, 0u}; }
+// best candidate of the G lanes that work on one vertex (G = 64: of the wave), in every one of them
+template <int G>
+__device__ __forceinline__ Cand group_best(Cand x) {
 #pragma unroll
-  for (int o = 32; o > 0; o >>= 1) {
+  for (int o = G / 2; o > 0; o >>= 1) {
     Cand y;
     y.val = __shfl_xor(x.val, o);
     y.c = __shfl_xor(x.c, o);
     y.pr = (unsigned int)__shfl_xor((int)x.pr, o);
     if (cand_better(y, x)) x = y;
   }
+  return x;
+}
+__device__ __forceinline__ Cand wave_best(Cand x) { return group_best<64>(x); }
+template <int G>
+__device__ __forceinline__ long long group_max(long long x) {
+#pragma unroll
+  for (int o = G / 2; o > 0; o >>= 1) x = max(x, __shfl_xor(x, o));
   return x;
 }
 
@@ -353,7 +359,7 @@ struct WaveHash {
 // ---- high-degree vertices: one workgroup per vertex, 8192-slot LDS table ---------------------------------
 // kNN graphs have hubs (in-degree in the thousands) and aggregated graphs are dense: the wave-per-vertex kernels
 // hand every vertex with more than WH_MAX_DEG neighbours to these block-per-vertex kernels (hub list filled
-// through counters[4]) instead of letting ONE wave grind through an O(deg^2) compare while the grid waits.
+// through counters[CTR_HUB]) instead of letting ONE wave grind through an O(deg^2) compare while the grid waits.
 constexpr int BHUB_SLOTS = 8192;
 constexpr int BHUB_MAX_DEG = 6000;  // longest row one pass of the table takes (load <= 0.73)
 // Longer rows (the coarse levels of a weakly clustered graph are nearly dense: 20k vertices with up to 18k
@@ -397,7 +403,7 @@ struct BlockHash {
     }
     atomicAdd(&vals[slot], (unsigned long long)w);
   }
-  // optimistic single pass over a long row (see hub_try_single_pass): gives up after max_probes occupied slots
+  // optimistic single pass over a long row (see hub_row): gives up after max_probes occupied slots
   __device__ __forceinline__ bool add_limited(int c, long long w, int max_probes) {
     unsigned int slot = hash32((unsigned int)c) & (nslots - 1);
     for (int probes = 0; probes < max_probes; ++probes) {
@@ -429,8 +435,7 @@ struct BlockHash {
 // block-wide argmax of candidates (+ max of w_own); result valid in thread 0
 __device__ __forceinline__ Cand block_best(Cand x, long long& w_own, Cand* sh_c, long long* sh_w) {
   x = wave_best(x);
-#pragma unroll
-  for (int o = 32; o > 0; o >>= 1) w_own = max(w_own, __shfl_xor(w_own, o));
+  w_own = group_max<64>(w_own);
   const int wv = threadIdx.x >> 6;
   if ((threadIdx.x & 63) == 0) {
     sh_c[wv] = x;
@@ -454,12 +459,40 @@ __device__ __forceinline__ Cand block_best(Cand x, long long& w_own, Cand* sh_c,
 
 // G lanes per ACTIVE vertex (list[0..n_act)): decision[w] = community to move to, -1 = stay,
 // -2 = wants to move but the direction rule forbids it this round (stays active).
-//   G = 64: one wave per vertex, table of up to 512 slots (deg <= 384); hubs go to hub_list (counters[4]).
+//   G = 64: one wave per vertex, table of up to 512 slots (deg <= 384); hubs go to hub_list (counters[CTR_HUB]).
 //   G = 16: FOUR vertices per wave, 128 slots each (deg <= 96) -- a kNN graph's rows are ~2k long, and the kernel
 //           is bound by its chain of dependent gathers (list -> indptr -> indices -> comm -> Ktot), so four
 //           vertices per wave put four times as many gathers in flight per wave slot.  Longer rows go to
-//           ovf_list (counters[5]) and are decided by the G = 64 instantiation in indirect mode
+//           ovf_list (counters[CTR_OVF]) and are decided by the G = 64 instantiation in indirect mode
 //           (sub_list / sub_count = positions in `list`, grid-strided).
+// THE move rule, shared by the wave and the hub kernel.  Score of moving v (weight kv) into community c, to which it has
+// weight `sum` and whose total is Kc:
+__device__ __forceinline__ Cand move_cand(int c, long long sum, unsigned long long Kc, double g, double kv, unsigned int seed) {
+  return Cand{(double)sum - g * kv * (double)(long long)Kc, c, prio(c, seed)};
+}
+// ... and the verdict on vertex v of community a (w_own: its weight to a, Ka_wo: a's total without v) given the best
+// candidate: the community to move to, -1 = stay, -2 = wants to move but the direction rule forbids it this round
+__device__ __forceinline__ int move_verdict(const Cand& best, long long w_own, double g, double kv, double Ka_wo, int a, int v,
+                                            int round, unsigned int seed, const int* __restrict__ csize) {
+  const double stay = (double)w_own - g * kv * Ka_wo;
+  int target = a;
+  bool wants = false, allowed = true;
+  if (best.c >= 0 && best.val > stay) {
+    wants = true;
+    target = best.c;
+    const unsigned int pa = prio(a, seed), pb = best.pr;
+    // direction rule (round >= 0 only: the termination guarantee of the late sweeps, see local_moving): moves towards
+    // lower / higher priority communities alternate, so that two communities cannot keep swapping members
+    if (round >= 0)
+      allowed = (round & 1) ? (pb > pa || (pb == pa && target > a)) : (pb < pa || (pb == pa && target < a));
+  } else if (stay < 0.0 && Ka_wo > 0.0 && csize[v] == 0) {
+    // leaving for an empty community (id = own vertex id, free at the snapshot) beats staying
+    wants = true;
+    target = v;
+  }
+  return (wants && allowed) ? target : (wants ? -2 : -1);
+}
+
 struct MoveArgs {
   int n_act;
   const int* list;
@@ -537,19 +570,16 @@ __device__ __forceinline__ void ld_move_body(int bid, int nblk, const MoveArgs& 
     for (int t = 0; t < 2; ++t) c_pre[t] = comm[u_pre[t]];
     if (G < 64) {
       if (deg > GMAX) {  // decided by the wave-per-vertex instantiation
-        if (sub == 0) ovf_list[atomicAdd(&counters[5], 1)] = w;
+        if (sub == 0) ovf_list[atomicAdd(&counters[CTR_OVF], 1)] = w;
         continue;
       }
     } else if (deg > WH_MAX_DEG) {  // hub: decided by ld_move_hub_kernel (any length: multi-pass table)
-      if (sub == 0) hub_list[atomicAdd(&counters[4], 1)] = w;
+      if (sub == 0) hub_list[atomicAdd(&counters[CTR_HUB], 1)] = w;
       continue;
     }
     const double kv = (double)kq;
     const double Ka_wo = (double)(long long)(Ka - (unsigned long long)kq);  // own community without v
-    Cand best;
-    best.val = 0.0;
-    best.c = -1;
-    best.pr = 0;
+    Cand best = cand_none();
     long long w_own = 0;
     if (deg <= GMAX) {
       int* keys = hkeys[grp];
@@ -601,149 +631,111 @@ __device__ __forceinline__ void ld_move_body(int bid, int nblk, const MoveArgs& 
           if (c == a) {
             w_own = sum;
           } else {
-            Cand x;
-            x.val = (double)sum - g * kv * (double)(long long)kt[t];
-            x.c = c;
-            x.pr = prio(c, seed);
+            const Cand x = move_cand(c, sum, kt[t], g, kv, seed);
             if (cand_better(x, best)) best = x;
           }
         }
       }
     }
-#pragma unroll
-    for (int o = G / 2; o > 0; o >>= 1) {
-      Cand y;
-      y.val = __shfl_xor(best.val, o);
-      y.c = __shfl_xor(best.c, o);
-      y.pr = (unsigned int)__shfl_xor((int)best.pr, o);
-      if (cand_better(y, best)) best = y;
-      w_own = max(w_own, __shfl_xor(w_own, o));
-    }
-    const double stay = (double)w_own - g * kv * Ka_wo;
-    int target = a;
-    bool wants = false, allowed = true;
-    if (best.c >= 0 && best.val > stay) {
-      wants = true;
-      target = best.c;
-      const unsigned int pa = prio(a, seed), pb = best.pr;
-      // direction rule (round >= 0 only: the termination guarantee of the late sweeps, see local_moving): moves towards
-      // lower / higher priority communities alternate, so that two communities cannot keep swapping members
-      if (round >= 0)
-        allowed = (round & 1) ? (pb > pa || (pb == pa && target > a)) : (pb < pa || (pb == pa && target < a));
-    } else if (stay < 0.0 && Ka_wo > 0.0 && csize[v] == 0) {
-      // leaving for an empty community (id = own vertex id, free at the snapshot) beats staying
-      wants = true;
-      target = v;
-    }
-    if (sub == 0) decision[w] = (wants && allowed) ? target : (wants ? -2 : -1);
+    best = group_best<G>(best);
+    w_own = group_max<G>(w_own);
+    const int verdict = move_verdict(best, w_own, g, kv, Ka_wo, a, v, round, seed, csize);
+    if (sub == 0) decision[w] = verdict;
   }
 }
 template <int G>
-__global__ __launch_bounds__(256) void ld_move_kernel(
-    int n_act, const int* __restrict__ list, const int* __restrict__ sub_list, const int* __restrict__ sub_count,
-    const int64_t* __restrict__ indptr, const int* __restrict__ indices, const long long* __restrict__ wq,
-    const long long* __restrict__ k, const int* __restrict__ comm, const unsigned long long* __restrict__ Ktot,
-    const int* __restrict__ csize, double g /* gamma / 2m */, int round, unsigned int seed,
-    int* __restrict__ decision, int* __restrict__ ovf_list, int* __restrict__ hub_list, int* __restrict__ counters) {
-  const MoveArgs ma{n_act, list, sub_list, sub_count, indptr, indices, wq, k, comm, Ktot, csize, g, round, seed,
-                    decision, ovf_list, hub_list, counters};
+__global__ __launch_bounds__(256) void ld_move_kernel(MoveArgs ma) {
   ld_move_body<G>((int)blockIdx.x, (int)gridDim.x, ma);
 }
 
-// Hub vertices of the active list (positions in hub_list[0 .. counters[4])): one workgroup each.
 // HUB_THREADS = 1024 (round 3; 256 before): a launch lasts as long as its longest row -- up to 20k entries on the coarse
 // levels of unstructured graphs, swept in 7 hash-class passes -- and the row is walked blockDim entries at a time.
 constexpr int HUB_THREADS = 1024;
-__global__ __launch_bounds__(HUB_THREADS) void ld_move_hub_kernel(
-    const int* __restrict__ hub_list, int* __restrict__ counters, const int* __restrict__ list,
-    const int64_t* __restrict__ indptr, const int* __restrict__ indices, const long long* __restrict__ wq,
-    const long long* __restrict__ k, const int* __restrict__ comm, const unsigned long long* __restrict__ Ktot,
-    const int* __restrict__ csize, double g, int round, unsigned int seed, int* __restrict__ decision,
-    int* __restrict__ err, int try_probes) {
+struct HubTry {
+  int* err;        // raised when a class pass finds its table full (the host turns it into SCAMD_EINTERNAL)
+  int try_probes;  // probe bound of the optimistic single pass over a multi-pass row (0: straight to the class passes)
+};
+// One long row through the workgroup's table: the weight of the row towards every distinct key, handed to visit(key, sum)
+// once per key, by whichever thread scans the key's slot.  key_of(e) = the key of entry e of the row, or WH_EMPTY to
+// leave the entry out; its weight is wrow[e] (read only for the entries that are inserted).  A row of more than
+// BHUB_MAX_DEG entries first tries ONE pass with bounded probing (the comment at HUB_TRY_PROBES) and falls back to its
+// bhub_passes(deg) hash-class passes.  Called by every thread of the workgroup; ends with a barrier.
+template <typename KeyOf, typename Visit>
+__device__ __forceinline__ void hub_row(BlockHash& bh, int deg, const long long* __restrict__ wrow, const HubTry& ht,
+                                        int* sh_fail, KeyOf key_of, Visit visit) {
+  const int n_pass = bhub_passes(deg);
+  bh.size_for(n_pass > 1 ? BHUB_SLOTS : deg);
+  bool filled = false;  // the table already holds the whole row (a successful optimistic pass)
+  if (n_pass > 1 && ht.try_probes > 0) {
+    if (threadIdx.x == 0) *sh_fail = 0;
+    bh.clear();
+    __syncthreads();
+    for (int e = threadIdx.x; e < deg; e += blockDim.x) {
+      if (__hip_atomic_load(sh_fail, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WORKGROUP)) break;
+      const int c = key_of(e);
+      if (c == WH_EMPTY) continue;
+      if (!bh.add_limited(c, wrow[e], ht.try_probes)) __hip_atomic_store(sh_fail, 1, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WORKGROUP);
+    }
+    __syncthreads();
+    filled = *sh_fail == 0;
+    __syncthreads();  // (sh_fail is rewritten for the next row)
+  }
+  const int n_sweep = filled ? 1 : n_pass;
+  for (int pass = 0; pass < n_sweep; ++pass) {
+    if (!filled) {
+      bh.clear();
+      __syncthreads();
+      for (int e = threadIdx.x; e < deg; e += blockDim.x) {
+        const int c = key_of(e);
+        if (c == WH_EMPTY) continue;
+        if (n_pass == 1) bh.add(c, wrow[e]);
+        else if (bhub_class(c, n_pass) == pass && !bh.add_bounded(c, wrow[e])) *ht.err = 1;
+      }
+      __syncthreads();
+    }
+    for (int sl = threadIdx.x; sl < bh.nslots; sl += blockDim.x) {
+      const int c = bh.keys[sl];
+      if (c != WH_EMPTY) visit(c, (long long)bh.vals[sl]);
+    }
+    __syncthreads();  // the scan of this pass is done before the next pass clears the table
+  }
+}
+
+// Hub vertices of the active list (positions in hub_list[0 .. counters[CTR_HUB])): one workgroup each.
+__global__ __launch_bounds__(HUB_THREADS) void ld_move_hub_kernel(MoveArgs ma, HubTry ht) {
   extern __shared__ __attribute__((aligned(16))) unsigned long long hub_smem[];
   BlockHash bh{reinterpret_cast<int*>(hub_smem + BHUB_SLOTS), hub_smem, BHUB_SLOTS};
   __shared__ Cand sh_c[HUB_THREADS / 64];
   __shared__ long long sh_w[HUB_THREADS / 64];
   __shared__ int sh_fail;
-  const int n_hub = counters[4];
+  const int n_hub = ma.counters[CTR_HUB];
   for (int i = blockIdx.x; i < n_hub; i += gridDim.x) {
-    const int w = hub_list[i];
-    const int v = list[w];
-    const int a = comm[v];
-    const double kv = (double)k[v];
-    const int64_t beg = indptr[v];
-    const int deg = (int)(indptr[v + 1] - beg);
-    const double Ka_wo = (double)(long long)(Ktot[a] - (unsigned long long)k[v]);
-    const int n_pass = bhub_passes(deg);
-    bh.size_for(n_pass > 1 ? BHUB_SLOTS : deg);
-    Cand best;
-    best.val = 0.0;
-    best.c = -1;
-    best.pr = 0;
+    const int w = ma.hub_list[i];
+    const int v = ma.list[w];
+    const int a = ma.comm[v];
+    const double kv = (double)ma.k[v];
+    const int64_t beg = ma.indptr[v];
+    const int deg = (int)(ma.indptr[v + 1] - beg);
+    const double Ka_wo = (double)(long long)(ma.Ktot[a] - (unsigned long long)ma.k[v]);
+    const int* __restrict__ urow = ma.indices + beg;
+    Cand best = cand_none();
     long long w_own = 0;
-    bool filled = false;  // the table already holds the whole row (a successful optimistic pass)
-    if (n_pass > 1 && try_probes > 0) {
-      if (threadIdx.x == 0) sh_fail = 0;
-      bh.clear();
-      __syncthreads();
-      for (int e = threadIdx.x; e < deg; e += blockDim.x) {
-        if (__hip_atomic_load(&sh_fail, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WORKGROUP)) break;
-        const int u = indices[beg + e];
-        if (u == v) continue;
-        if (!bh.add_limited(comm[u], wq[beg + e], try_probes)) __hip_atomic_store(&sh_fail, 1, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WORKGROUP);
-      }
-      __syncthreads();
-      filled = sh_fail == 0;
-      __syncthreads();  // (sh_fail is rewritten for the next row)
-    }
-    const int n_sweep = filled ? 1 : n_pass;
-    for (int pass = 0; pass < n_sweep; ++pass) {
-      if (!filled) {
-        bh.clear();
-        __syncthreads();
-        for (int e = threadIdx.x; e < deg; e += blockDim.x) {
-          const int u = indices[beg + e];
-          if (u == v) continue;
-          const int c = comm[u];
-          if (n_pass == 1) bh.add(c, wq[beg + e]);
-          else if (bhub_class(c, n_pass) == pass && !bh.add_bounded(c, wq[beg + e])) *err = 1;
-        }
-        __syncthreads();
-      }
-      for (int sl = threadIdx.x; sl < bh.nslots; sl += blockDim.x) {
-        const int c = bh.keys[sl];
-        if (c != WH_EMPTY) {
-          const long long sum = (long long)bh.vals[sl];
+    hub_row(
+        bh, deg, ma.wq + beg, ht, &sh_fail,
+        [&](int e) {
+          const int u = urow[e];
+          return u == v ? WH_EMPTY : ma.comm[u];
+        },
+        [&](int c, long long sum) {
           if (c == a) {
             w_own = sum;
           } else {
-            Cand x;
-            x.val = (double)sum - g * kv * (double)(long long)Ktot[c];
-            x.c = c;
-            x.pr = prio(c, seed);
+            const Cand x = move_cand(c, sum, ma.Ktot[c], ma.g, kv, ma.seed);
             if (cand_better(x, best)) best = x;
           }
-        }
-      }
-      __syncthreads();  // the scan of this pass is done before the next pass clears the table
-    }
+        });
     best = block_best(best, w_own, sh_c, sh_w);
-    if (threadIdx.x == 0) {
-      const double stay = (double)w_own - g * kv * Ka_wo;
-      int target = a;
-      bool wants = false, allowed = true;
-      if (best.c >= 0 && best.val > stay) {
-        wants = true;
-        target = best.c;
-        const unsigned int pa = prio(a, seed), pb = best.pr;
-        if (round >= 0)
-          allowed = (round & 1) ? (pb > pa || (pb == pa && target > a)) : (pb < pa || (pb == pa && target < a));
-      } else if (stay < 0.0 && Ka_wo > 0.0 && csize[v] == 0) {
-        wants = true;
-        target = v;
-      }
-      decision[w] = (wants && allowed) ? target : (wants ? -2 : -1);
-    }
+    if (threadIdx.x == 0) ma.decision[w] = move_verdict(best, w_own, ma.g, kv, Ka_wo, a, v, ma.round, ma.seed, ma.csize);
     __syncthreads();
   }
 }
@@ -969,7 +961,6 @@ __device__ __forceinline__ int lm_class(int v, unsigned int salt, int n_cls) {
 // vertices whose rows the main decision kernel hands on -- longer than thr_mid (the lanes-per-vertex table) / longer than
 // thr_hub (the wave table) -- so that the host launches the overflow / hub kernels of a sub-round only when it has any
 // (they were launched blind: ~300 near-empty launches of ~10 us per call at 1M cells).  thr_mid < 0: no such tier.
-constexpr int CTR_N_MID = 8, CTR_N_HUB = 9;
 // tier of a vertex's row: bit 0 = longer than thr_mid, bit 1 = longer than thr_hub (0 for inactive vertices)
 __device__ __forceinline__ int long_row_tier(int cls, int v, const int64_t* __restrict__ indptr, int thr_mid, int thr_hub) {
   if (cls < 0 || !indptr) return 0;
@@ -1191,20 +1182,73 @@ __device__ __forceinline__ double refine_noise(int v, int c, int round, unsigned
   return -log(-log(u));
 }
 
+struct RefineRule {
+  double g;         // gamma / 2m
+  double inv_beta;  // 1 / (beta * 2^32); 0 = greedy
+  int round;        // the sub-round = the class that proposes
+  int n_cls;
+  unsigned int salt, seed;
+};
+// THE merge rule, shared by the wave and the hub kernel.  Candidate v (weight kv, in a phase-1 community of total KC) and
+// the refined community c (record t) to which it has weight `sum`: if c is an admissible target -- grown, or a singleton of
+// another class; well connected -- of non-negative gain, its value in the draw goes into *x
+__device__ __forceinline__ bool refine_cand(const RefineRule& r, int v, double kv, double KC, int c, long long sum,
+                                            unsigned long long Kref, int refsize, unsigned long long Eref, Cand* x) {
+  const double Kr = (double)(long long)Kref;
+  const bool single = refsize == 1;
+  const bool ok_target = (!single || lm_class(c, r.salt, r.n_cls) != r.round) &&
+                         ((double)(long long)Eref >= r.g * Kr * (KC - Kr));  // target well connected
+  const double gain = (double)sum - r.g * kv * Kr;
+  if (!(ok_target && gain >= 0.0)) return false;
+  *x = Cand{r.inv_beta > 0.0 ? gain * r.inv_beta + refine_noise(v, c, r.round, r.seed) : gain, c, prio(c, r.seed)};
+  return true;
+}
+// ... and what v does given the best of them: the refined community to join, -1 = no admissible target, -2 = "stay" was
+// drawn against the best candidate (a singleton that stays is done; it may still be joined)
+__device__ __forceinline__ int refine_verdict(const RefineRule& r, int v, const Cand& best) {
+  return (r.inv_beta > 0.0 && best.c >= 0 && !(best.val > refine_noise(v, v, r.round, r.seed))) ? -2 : best.c;
+}
+
+struct ProposeArgs {
+  int n_act;        // length of ...
+  const int* list;  // ... the candidates of class rule.round
+  const int* sub_list;
+  const int* sub_count;
+  const int64_t* indptr;
+  const int* indices;
+  const long long* wq;
+  const long long* k;
+  const int* comm;
+  const unsigned long long* Ktot;
+  const int* ref;
+  const int* refsize;
+  const VertRec* vr;
+  const TargRec* tr;
+  RefineRule rule;
+  int* target;
+  int* ovf_list;
+  int* hub_list;
+  int* counters;
+};
 // G lanes per candidate (see ld_move_kernel: G = 16 puts four candidates in a wave on short-rowed levels, rows longer
-// than the 128-slot table go to ovf_list / counters[5] and are proposed by the G = 64 instantiation in indirect mode).
-// `list` holds the candidates of class `round` (the sub-round's number).  target[v] = refined community to join,
-// -1 = no admissible target, -2 = no longer a singleton (somebody joined it) or "stay" was drawn.
+// than the 128-slot table go to ovf_list / counters[CTR_OVF] and are proposed by the G = 64 instantiation in indirect
+// mode).  target[v] = refined community to join, -1 = no admissible target, -2 = no longer a singleton (somebody joined
+// it) or "stay" was drawn.
 template <int G>
-__global__ __launch_bounds__(256) void ld_refine_propose_kernel(
-    const int* __restrict__ list, const int* __restrict__ sub_list, const int* __restrict__ sub_count,
-    const int64_t* __restrict__ indptr, const int* __restrict__ indices, const long long* __restrict__ wq,
-    const long long* __restrict__ k, const int* __restrict__ comm, const unsigned long long* __restrict__ Ktot,
-    const int* __restrict__ ref, const int* __restrict__ refsize, const unsigned long long* __restrict__ Kref,
-    const unsigned long long* __restrict__ Eref, double g, double inv_beta /* 1 / (beta * 2^32); 0 = greedy */,
-    int round, int n_cls, unsigned int salt, unsigned int seed, int* __restrict__ target,
-    int* __restrict__ ovf_list, int* __restrict__ hub_list, int* __restrict__ counters, int n_cand,
-    const VertRec* __restrict__ vr, const TargRec* __restrict__ tr) {
+__global__ __launch_bounds__(256) void ld_refine_propose_kernel(ProposeArgs pa) {
+  const int* __restrict__ list = pa.list;
+  const int* __restrict__ sub_list = pa.sub_list;
+  const int64_t* __restrict__ indptr = pa.indptr;
+  const int* __restrict__ indices = pa.indices;
+  const long long* __restrict__ wq = pa.wq;
+  const long long* __restrict__ k = pa.k;
+  const int* __restrict__ comm = pa.comm;
+  const unsigned long long* __restrict__ Ktot = pa.Ktot;
+  const int* __restrict__ ref = pa.ref;
+  const int* __restrict__ refsize = pa.refsize;
+  const VertRec* __restrict__ vr = pa.vr;
+  const TargRec* __restrict__ tr = pa.tr;
+  const RefineRule rule = pa.rule;
   constexpr int GROUPS = 256 / G;
   constexpr int GSLOTS = G == 16 ? G16_SLOTS : WH_SLOTS * G / 64;
   constexpr int GMAX = GSLOTS * 3 / 4;
@@ -1212,7 +1256,7 @@ __global__ __launch_bounds__(256) void ld_refine_propose_kernel(
   __shared__ unsigned long long hvals[GROUPS][GSLOTS];
   const int sub = threadIdx.x % G;
   const int grp = threadIdx.x / G;
-  const int n_items = sub_list ? *sub_count : n_cand;
+  const int n_items = sub_list ? *pa.sub_count : pa.n_act;
   for (int item = blockIdx.x * GROUPS + grp; item < n_items; item += gridDim.x * GROUPS) {
     // (gathers grouped by what they depend on, as in ld_move_kernel: list -> {refsize, ref, k, comm, indptr}[v] ->
     // {Ktot[a], indices, wq} -> {comm, ref}[u] -> {Kref, refsize, Eref}[c]; most launches of a refinement are short
@@ -1248,17 +1292,14 @@ __global__ __launch_bounds__(256) void ld_refine_propose_kernel(
       const double kv = (double)kq;
       if (G < 64) {
         if (deg > GMAX) {  // proposed by the wave-per-candidate instantiation
-          if (sub == 0) ovf_list[atomicAdd(&counters[5], 1)] = w;
+          if (sub == 0) pa.ovf_list[atomicAdd(&pa.counters[CTR_OVF], 1)] = w;
           continue;
         }
       } else if (deg > WH_MAX_DEG) {  // hub: proposed by ld_refine_propose_hub_kernel (any length)
-        if (sub == 0) hub_list[atomicAdd(&counters[4], 1)] = v;
+        if (sub == 0) pa.hub_list[atomicAdd(&pa.counters[CTR_HUB], 1)] = v;
         continue;
       }
-      Cand best;
-      best.val = 0.0;
-      best.c = -1;
-      best.pr = 0;
+      Cand best = cand_none();
       if (deg <= GMAX) {
         int* keys = hkeys[grp];
         unsigned long long* vals = hvals[grp];
@@ -1309,121 +1350,51 @@ __global__ __launch_bounds__(256) void ld_refine_propose_kernel(
           if (c != WH_EMPTY) {
             const long long sum =
                 (long long)__hip_atomic_load(&vals[sub + t * G], __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WORKGROUP);
-            const double Kr = (double)(long long)kr[t];
-            const bool single = rsz[t] == 1;
-            const bool ok_target = (!single || lm_class(c, salt, n_cls) != round) &&
-                                   ((double)(long long)er[t] >= g * Kr * (KC - Kr));  // target well connected
-            const double gain = (double)sum - g * kv * Kr;
-            if (ok_target && gain >= 0.0) {
-              Cand x;
-              x.val = inv_beta > 0.0 ? gain * inv_beta + refine_noise(v, c, round, seed) : gain;
-              x.c = c;
-              x.pr = prio(c, seed);
-              if (cand_better(x, best)) best = x;
-            }
+            Cand x;
+            if (refine_cand(rule, v, kv, KC, c, sum, kr[t], rsz[t], er[t], &x) && cand_better(x, best)) best = x;
           }
         }
       }
-#pragma unroll
-      for (int o = G / 2; o > 0; o >>= 1) {
-        Cand y;
-        y.val = __shfl_xor(best.val, o);
-        y.c = __shfl_xor(best.c, o);
-        y.pr = (unsigned int)__shfl_xor((int)best.pr, o);
-        if (cand_better(y, best)) best = y;
-      }
-      tgt = best.c;
-      // "stay" drawn against the best candidate: a singleton that stays is done (it may still be joined)
-      if (inv_beta > 0.0 && tgt >= 0 && !(best.val > refine_noise(v, v, round, seed))) tgt = -2;
+      best = group_best<G>(best);
+      tgt = refine_verdict(rule, v, best);
     }
-    if (sub == 0) target[v] = tgt;
+    if (sub == 0) pa.target[v] = tgt;
   }
 }
 
-// Hub candidates (vertex ids in hub_list[0 .. counters[4])): one workgroup each; same rule as the wave kernel.
-__global__ __launch_bounds__(HUB_THREADS) void ld_refine_propose_hub_kernel(
-    const int* __restrict__ hub_list, int* __restrict__ counters, const int64_t* __restrict__ indptr,
-    const int* __restrict__ indices, const long long* __restrict__ wq, const long long* __restrict__ k,
-    const int* __restrict__ comm, const unsigned long long* __restrict__ Ktot, const int* __restrict__ ref,
-    const int* __restrict__ refsize, const unsigned long long* __restrict__ Kref,
-    const unsigned long long* __restrict__ Eref, double g, double inv_beta, int round, int n_cls, unsigned int salt,
-    unsigned int seed, int* __restrict__ target, int* __restrict__ err, const VertRec* __restrict__ vr,
-    const TargRec* __restrict__ tr, int try_probes) {
+// Hub candidates (vertex ids in hub_list[0 .. counters[CTR_HUB])): one workgroup each.
+__global__ __launch_bounds__(HUB_THREADS) void ld_refine_propose_hub_kernel(ProposeArgs pa, HubTry ht) {
   extern __shared__ __attribute__((aligned(16))) unsigned long long hub_smem[];
   BlockHash bh{reinterpret_cast<int*>(hub_smem + BHUB_SLOTS), hub_smem, BHUB_SLOTS};
   __shared__ Cand sh_c[HUB_THREADS / 64];
   __shared__ long long sh_w[HUB_THREADS / 64];
   __shared__ int sh_fail;
-  const int n_hub = counters[4];
+  const int n_hub = pa.counters[CTR_HUB];
   for (int i = blockIdx.x; i < n_hub; i += gridDim.x) {
-    const int v = hub_list[i];
-    const double kv = (double)k[v];
-    const int a = comm[v];
-    const double KC = (double)(long long)Ktot[a];
-    const int64_t beg = indptr[v];
-    const int deg = (int)(indptr[v + 1] - beg);
-    const int n_pass = bhub_passes(deg);
-    bh.size_for(n_pass > 1 ? BHUB_SLOTS : deg);
-    Cand best;
-    best.val = 0.0;
-    best.c = -1;
-    best.pr = 0;
+    const int v = pa.hub_list[i];
+    const double kv = (double)pa.k[v];
+    const int a = pa.comm[v];
+    const double KC = (double)(long long)pa.Ktot[a];
+    const int64_t beg = pa.indptr[v];
+    const int deg = (int)(pa.indptr[v + 1] - beg);
+    const int* __restrict__ urow = pa.indices + beg;
+    Cand best = cand_none();
     long long dummy = 0;
-    bool filled = false;  // (hub_try_single_pass: the comment at HUB_TRY_PROBES)
-    if (n_pass > 1 && try_probes > 0) {
-      if (threadIdx.x == 0) sh_fail = 0;
-      bh.clear();
-      __syncthreads();
-      for (int e = threadIdx.x; e < deg; e += blockDim.x) {
-        if (__hip_atomic_load(&sh_fail, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WORKGROUP)) break;
-        const int u = indices[beg + e];
-        const VertRec r = vr[u];
-        if (u == v || r.comm != a) continue;
-        if (!bh.add_limited(r.ref, wq[beg + e], try_probes)) __hip_atomic_store(&sh_fail, 1, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WORKGROUP);
-      }
-      __syncthreads();
-      filled = sh_fail == 0;
-      __syncthreads();
-    }
-    const int n_sweep = filled ? 1 : n_pass;
-    for (int pass = 0; pass < n_sweep; ++pass) {
-      if (!filled) {
-        bh.clear();
-        __syncthreads();
-        for (int e = threadIdx.x; e < deg; e += blockDim.x) {
-          const int u = indices[beg + e];
-          const VertRec r = vr[u];
-          if (u == v || r.comm != a) continue;
-          const int c = r.ref;
-          if (n_pass == 1) bh.add(c, wq[beg + e]);
-          else if (bhub_class(c, n_pass) == pass && !bh.add_bounded(c, wq[beg + e])) *err = 1;
-        }
-        __syncthreads();
-      }
-      for (int sl = threadIdx.x; sl < bh.nslots; sl += blockDim.x) {
-        const int c = bh.keys[sl];
-        if (c != WH_EMPTY && c != v) {
-          const long long sum = (long long)bh.vals[sl];
-          const TargRec x = tr[c];
-          const double Kr = (double)(long long)x.Kref;
-          const bool single = x.refsize == 1;
-          const bool ok_target = (!single || lm_class(c, salt, n_cls) != round) &&
-                                 ((double)(long long)x.Eref >= g * Kr * (KC - Kr));
-          const double gain = (double)sum - g * kv * Kr;
-          if (ok_target && gain >= 0.0) {
-            Cand x;
-            x.val = inv_beta > 0.0 ? gain * inv_beta + refine_noise(v, c, round, seed) : gain;
-            x.c = c;
-            x.pr = prio(c, seed);
-            if (cand_better(x, best)) best = x;
-          }
-        }
-      }
-      __syncthreads();
-    }
+    hub_row(
+        bh, deg, pa.wq + beg, ht, &sh_fail,
+        [&](int e) {
+          const int u = urow[e];
+          const VertRec r = pa.vr[u];
+          return (u == v || r.comm != a) ? WH_EMPTY : r.ref;
+        },
+        [&](int c, long long sum) {
+          if (c == v) return;
+          const TargRec t = pa.tr[c];
+          Cand x;
+          if (refine_cand(pa.rule, v, kv, KC, c, sum, t.Kref, t.refsize, t.Eref, &x) && cand_better(x, best)) best = x;
+        });
     best = block_best(best, dummy, sh_c, sh_w);
-    if (threadIdx.x == 0)
-      target[v] = (inv_beta > 0.0 && best.c >= 0 && !(best.val > refine_noise(v, v, round, seed))) ? -2 : best.c;
+    if (threadIdx.x == 0) pa.target[v] = refine_verdict(pa.rule, v, best);
     __syncthreads();
   }
 }
@@ -1904,7 +1875,7 @@ __global__ __launch_bounds__(256) void ld_agg_compact_kernel(int nn, const int64
                                                              int* __restrict__ dstat) {
   const int lane = threadIdx.x & 63;
   const int c = blockIdx.x * 4 + (threadIdx.x >> 6);
-  if (blockIdx.x == 0 && threadIdx.x < 4) dstat[threadIdx.x] = 0;  // (row-length statistics of the level being built: ld_degstats_kernel follows)
+  if (blockIdx.x == 0 && threadIdx.x == 0) dstat[0] = 0;  // (longest row of the level being built: ld_degstats_kernel follows)
   if (c >= nn) return;
   const int64_t u0 = eoff[moff[c]];
   const int64_t p0 = indptr_new[c];
@@ -2541,8 +2512,7 @@ __global__ void ld_gather_kernel(int n, const int* __restrict__ comm, const int*
 // ---- host orchestration --------------------------------------------------------------------------
 struct LevelGraph {
   int n = 0;
-  int max_deg = 0;  // largest row length: levels without hubs skip the block-per-vertex kernels
-  int n_gt96 = 0, n_gt192 = 0, n_gt384 = 0;  // rows beyond the quarter- / half- / full-wave tables
+  int max_deg = 0;  // largest row length (debug trace)
   int64_t nnz = 0;
   const int64_t* indptr = nullptr;
   const int* indices = nullptr;
@@ -2652,7 +2622,7 @@ static void leiden_carve(Workspace& ws, int64_t n, int64_t nnz, LeidenBuffers* b
   }
   b->rowcnt = ws.take<int>(N);
   b->cursor = ws.take<int>(N);
-  b->counters = ws.take<int>(16);  // [0..7] phase counters, [8..11] row-length statistics of the level being built
+  b->counters = ws.take<int>(16);  // [0..7] phase counters, [8] longest row of the level being built
   b->rcounters = ws.take<int>(2 * CTR_AREA);  // two counter areas: the sweeps of the local moving alternate between them
   b->total = ws.take<unsigned long long>(4);
   b->dscratch = ws.take<double>(4 + SUMSQ_BLOCKS);
@@ -2771,6 +2741,19 @@ static int read_counters(LeidenCtx& cx, int* h, int cnt) {
   return SCAMD_OK;
 }
 
+// lanes per vertex -> the template instantiation: f(std::integral_constant<int, lanes>()).  WITH_32 = false for the kernels
+// that exist for 16 and 64 lanes only.
+template <bool WITH_32, typename F>
+static void with_lanes(int lanes, F&& f) {
+  if (lanes == 16) return f(std::integral_constant<int, 16>());
+  if constexpr (WITH_32) {
+    if (lanes == 32) return f(std::integral_constant<int, 32>());
+  }
+  return f(std::integral_constant<int, 64>());
+}
+// 256-thread workgroups that give `cnt` vertices `lanes` lanes each
+static int blocks_for(int lanes, int cnt) { return ceil_div(cnt, 256 / lanes); }
+
 // Ktot / csize of `comm`; `extra`: further regions the caller wants cleared by the same launch
 static int compute_totals(LeidenCtx& cx, const LevelGraph& g, const int* comm, Filler extra = Filler()) {
   extra.add(cx.b.Ktot, sizeof(unsigned long long) * g.n).add(cx.b.csize, sizeof(int) * g.n);
@@ -2788,12 +2771,11 @@ static int quality(LeidenCtx& cx, const LevelGraph& g, const int* comm, double* 
   // (a group walks its vertices one after the other, three dependent loads each: the more groups, the fewer steps of that
   // walk -- and one same-word atomic per workgroup at the end)
   constexpr int qgrid = 2048;
-  if (g.nnz <= (int64_t)48 * g.n)
-    hipLaunchKernelGGL(ld_internal_kernel<16>, dim3((unsigned)std::min(qgrid, ceil_div(g.n, 16))), dim3(256), 0, cx.s, g.n,
+  with_lanes<false>(g.nnz <= (int64_t)48 * g.n ? 16 : 64, [&](auto G) {
+    constexpr int L = decltype(G)::value;
+    hipLaunchKernelGGL(ld_internal_kernel<L>, dim3((unsigned)std::min(qgrid, blocks_for(L, g.n))), dim3(256), 0, cx.s, g.n,
                        g.indptr, g.indices, g.wq, comm, cx.b.total + 1);
-  else
-    hipLaunchKernelGGL(ld_internal_kernel<64>, dim3((unsigned)std::min(qgrid, ceil_div(g.n, 4))), dim3(256), 0, cx.s, g.n,
-                       g.indptr, g.indices, g.wq, comm, cx.b.total + 1);
+  });
   SCAMD_LAUNCH_CHECK();
   // (CPM: sum of squared community SIZES, unnormalised)
   hipLaunchKernelGGL(ld_sumsq_kernel, dim3(SUMSQ_BLOCKS), dim3(1024), 0, cx.s, g.n, cx.b.Ktot, cx.cpm ? cx.nw_scale : cx.m2, cx.b.dscratch + 4);
@@ -2812,7 +2794,7 @@ static int quality(LeidenCtx& cx, const LevelGraph& g, const int* comm, double* 
 
 // levels whose rows are short on average (the kNN graph itself) take the four-vertices-per-wave kernels
 static_assert(WH_SLOTS / 2 * 3 / 4 == 192 && WH_MAX_DEG == 384,
-              "ld_degstats_kernel counts the rows beyond the 128- / 256- / 512-slot tables");
+              "the table ladders of the decide kernels (rows <= 96 / 192 / 384) are written out in their nslots expressions");
 // lanes per vertex of the decision kernels for this level: 16 (four vertices per wave, rows <= 96), 32 (two per wave,
 // rows <= 192: the first coarse levels, ~64 entries per row) or 64.  SCAMD_LEIDEN_QUAD = 0 / 1 / 2 forces 64 / 16 / 32.
 static int level_lanes(const LevelGraph& g) {
@@ -2824,7 +2806,67 @@ static int level_lanes(const LevelGraph& g) {
   const int64_t avg = g.nnz / g.n;
   return avg <= 40 ? 16 : (avg <= 110 ? 32 : 64);
 }
-static bool level_is_short_rowed(const LevelGraph& g) { return level_lanes(g) == 16; }
+// ... of the refinement's kernels, which exist for 16 and 64 lanes
+static int refine_lanes(const LevelGraph& g) { return level_lanes(g) == 16 ? 16 : 64; }
+// longest row the table of a `lanes`-lane decide kernel takes: longer rows of such a launch overflow to the 64-lane pass
+// (-1: no such tier, the launch is the 64-lane one)
+static int lanes_thr_mid(int lanes) { return lanes == 16 ? (int)G16_MAX : (lanes == 32 ? (int)(WH_SLOTS / 2 * 3 / 4) : -1); }
+
+// One decide step of a class sub-round, in its three tiers: the main launch (`lanes` lanes per vertex, the whole list), the
+// 64-lane pass over the rows the main launch handed on (indirect mode: positions in ovf_list, their number in the counter
+// block), the workgroup-per-row pass over the hubs.  hctr: the host's copy of the sub-round's counter block as the list
+// builder left it -- a tier without rows is not launched.  main = false: the main launch has been made already (by
+// ld_requeue_move_kernel).  The two flavours, by the argument struct: MoveArgs (local moving, polish) and ProposeArgs
+// (refinement).
+static void launch_main_tier(LeidenCtx& cx, int lanes, const MoveArgs& a) {
+  with_lanes<true>(lanes, [&](auto G) {
+    constexpr int L = decltype(G)::value;
+    hipLaunchKernelGGL(ld_move_kernel<L>, dim3((unsigned)blocks_for(L, a.n_act)), dim3(256), 0, cx.s, a);
+  });
+}
+static void launch_main_tier(LeidenCtx& cx, int lanes, const ProposeArgs& a) {
+  with_lanes<false>(lanes, [&](auto G) {
+    constexpr int L = decltype(G)::value;
+    hipLaunchKernelGGL(ld_refine_propose_kernel<L>, dim3((unsigned)std::min(32768, blocks_for(L, a.n_act))), dim3(256), 0, cx.s, a);
+  });
+}
+static void launch_overflow_tier(LeidenCtx& cx, unsigned grid, const MoveArgs& a) {
+  hipLaunchKernelGGL(ld_move_kernel<64>, dim3(grid), dim3(256), 0, cx.s, a);
+}
+static void launch_overflow_tier(LeidenCtx& cx, unsigned grid, const ProposeArgs& a) {
+  hipLaunchKernelGGL(ld_refine_propose_kernel<64>, dim3(grid), dim3(256), 0, cx.s, a);
+}
+static void launch_hub_tier(LeidenCtx& cx, unsigned grid, const MoveArgs& a, HubTry ht) {
+  hipLaunchKernelGGL(ld_move_hub_kernel, dim3(grid), dim3(HUB_THREADS), HUB_LDS, cx.s, a, ht);
+}
+static void launch_hub_tier(LeidenCtx& cx, unsigned grid, const ProposeArgs& a, HubTry ht) {
+  hipLaunchKernelGGL(ld_refine_propose_hub_kernel, dim3(grid), dim3(HUB_THREADS), HUB_LDS, cx.s, a, ht);
+}
+template <typename Args>
+static int decide_tiers(LeidenCtx& cx, const char* what, int n, int cls, int lanes, bool main, const int* hctr, const Args& a) {
+  const int n_mid = lanes != 64 ? hctr[CTR_N_MID] : 0, n_hub = hctr[CTR_N_HUB];
+  if (main) {
+    launch_main_tier(cx, lanes, a);
+    SCAMD_LAUNCH_CHECK();
+    LD_DBG_SYNC(cx, "%s<%d> n=%d class=%d cnt=%d", what, lanes, n, cls, a.n_act);
+  }
+  if (n_mid > 0) {
+    Args ovf = a;
+    ovf.sub_list = a.ovf_list;
+    ovf.sub_count = a.counters + CTR_OVF;
+    launch_overflow_tier(cx, (unsigned)std::min(2048, blocks_for(64, n_mid)), ovf);
+    SCAMD_LAUNCH_CHECK();
+    LD_DBG_SYNC(cx, "%s<64> overflow n=%d class=%d", what, n, cls);
+    g_ld_stats[18] += n_mid;
+  }
+  if (n_hub > 0) {
+    launch_hub_tier(cx, (unsigned)std::min(HUB_GRID, n_hub), a, HubTry{cx.b.counters + PHASE_ERR, cx.hub_try_probes});
+    SCAMD_LAUNCH_CHECK();
+    LD_DBG_SYNC(cx, "%s hub n=%d class=%d", what, n, cls);
+    g_ld_stats[19] += n_hub;
+  }
+  return SCAMD_OK;
+}
 
 // class sub-rounds per sweep: 8 everywhere.  (4 / 2 on levels below 16384 / 1024 vertices saved ~1 ms of launch latency
 // per call, but the fewer the classes the more neighbours move at once: on the 700-cell fixture one seed in ten then
@@ -2852,12 +2894,12 @@ static int local_moving(LeidenCtx& cx, const LevelGraph& g, int* total_moves) {
   const double gg = cx.gscale();
   *total_moves = 0;
   const size_t n = (size_t)g.n;
-  // (one clear launch: totals, re-queue flags, phase counters ([0] moved, [1] blocked (cumulative), [7] error), the counter
+  // (one clear launch: totals, re-queue flags, phase counters ([0] moved, [1] blocked (cumulative), [PHASE_ERR] error), the counter
   // area of sweep 0 -- every later sweep's area is cleared by the ld_compact_cls_kernel launch of the sweep before it)
   int rc = compute_totals(cx, g, b.comm, Filler().add(b.flag, sizeof(int) * n).add(b.counters, sizeof(int) * 8).add(b.rcounters, sizeof(int) * CTR_AREA));
   if (rc != SCAMD_OK) return rc;
   const int lanes = level_lanes(g);
-  const int thr_mid = lanes == 16 ? (int)G16_MAX : (lanes == 32 ? (int)(WH_SLOTS / 2 * 3 / 4) : -1);
+  const int thr_mid = lanes_thr_mid(lanes);
   const int n_cls = lm_classes(cx, g.n);
   int moved_before = 0, quiet = 0, moved_prev2 = 0;
   for (int sweep = 0; sweep < MAX_LM_SWEEPS; ++sweep) {
@@ -2872,7 +2914,7 @@ static int local_moving(LeidenCtx& cx, const LevelGraph& g, int* total_moves) {
     LD_FETCH(hc, sw, sizeof(int) * (MAX_CLASSES + CTR_STRIDE * n_cls), cx.s);
     LD_FETCH(ht, b.counters, sizeof(int) * 8, cx.s);
     LD_SYNC(cx.s);
-    SCAMD_REQUIRE(ht[7] == 0, SCAMD_EINTERNAL, "leiden: hub table overflow (local moving)");
+    SCAMD_REQUIRE(ht[PHASE_ERR] == 0, SCAMD_EINTERNAL, "leiden: hub table overflow (local moving)");
     int n_act = 0;
     for (int c = 0; c < n_cls; ++c) n_act += hc[c];
     const int moved_last = ht[0] - moved_before;  // moves of the previous sweep
@@ -2918,43 +2960,14 @@ static int local_moving(LeidenCtx& cx, const LevelGraph& g, int* total_moves) {
       return MoveArgs{hc[c], b.cls_lists + (size_t)c * n, nullptr, nullptr, g.indptr, g.indices, g.wq, g.k, b.comm, b.Ktot,
                       b.csize, gg, dir_round, cx.seed, decision, b.mid_list, b.hub_list, sw + MAX_CLASSES + CTR_STRIDE * c};
     };
-    auto move_blocks = [&](int cnt) { return lanes == 16 ? ceil_div(cnt, 16) : (lanes == 32 ? ceil_div(cnt, 8) : ceil_div(cnt, 4)); };
     for (int i = 0; i < ncl; ++i) {
       const int c = cls[i];
       const int cnt = hc[c];
       const int* list = b.cls_lists + (size_t)c * n;
-      int* ctr = sw + MAX_CLASSES + CTR_STRIDE * c;
       int* tg = tgt[i & 1];
-      // long rows among THIS sub-round's vertices (counted by ld_compact_cls_kernel): no launch for an empty tier
-      const int n_mid = hc[MAX_CLASSES + CTR_STRIDE * c + CTR_N_MID], n_hub = hc[MAX_CLASSES + CTR_STRIDE * c + CTR_N_HUB];
-      if (i == 0) {  // (later sub-rounds: decided in the launch that re-queued the sub-round before)
-        const MoveArgs ma = move_args(c, tg);
-        if (lanes == 32)
-          hipLaunchKernelGGL(ld_move_kernel<32>, dim3((unsigned)move_blocks(cnt)), dim3(256), 0, cx.s, ma.n_act, ma.list, ma.sub_list,
-                             ma.sub_count, ma.indptr, ma.indices, ma.wq, ma.k, ma.comm, ma.Ktot, ma.csize, ma.g, ma.round, ma.seed,
-                             ma.decision, ma.ovf_list, ma.hub_list, ma.counters);
-        else if (lanes == 16)
-          hipLaunchKernelGGL(ld_move_kernel<16>, dim3((unsigned)move_blocks(cnt)), dim3(256), 0, cx.s, ma.n_act, ma.list, ma.sub_list,
-                             ma.sub_count, ma.indptr, ma.indices, ma.wq, ma.k, ma.comm, ma.Ktot, ma.csize, ma.g, ma.round, ma.seed,
-                             ma.decision, ma.ovf_list, ma.hub_list, ma.counters);
-        else
-          hipLaunchKernelGGL(ld_move_kernel<64>, dim3((unsigned)move_blocks(cnt)), dim3(256), 0, cx.s, ma.n_act, ma.list, ma.sub_list,
-                             ma.sub_count, ma.indptr, ma.indices, ma.wq, ma.k, ma.comm, ma.Ktot, ma.csize, ma.g, ma.round, ma.seed,
-                             ma.decision, ma.ovf_list, ma.hub_list, ma.counters);
-        SCAMD_LAUNCH_CHECK();
-      }
-      if (lanes != 64 && n_mid > 0) {
-        hipLaunchKernelGGL(ld_move_kernel<64>, dim3((unsigned)std::min(2048, ceil_div(n_mid, 4))), dim3(256), 0, cx.s,
-                           cnt, list, (const int*)b.mid_list, (const int*)(ctr + 5), g.indptr, g.indices, g.wq, g.k,
-                           b.comm, b.Ktot, b.csize, gg, dir_round, cx.seed, tg, b.mid_list, b.hub_list, ctr);
-        SCAMD_LAUNCH_CHECK();
-      }
-      if (n_hub > 0) {
-        hipLaunchKernelGGL(ld_move_hub_kernel, dim3((unsigned)std::min(HUB_GRID, n_hub)), dim3(HUB_THREADS), HUB_LDS, cx.s, b.hub_list,
-                           ctr, list, g.indptr, g.indices, g.wq, g.k, b.comm, b.Ktot, b.csize, gg, dir_round, cx.seed,
-                           tg, b.counters + 7, cx.hub_try_probes);
-        SCAMD_LAUNCH_CHECK();
-      }
+      // (sub-rounds after the first: their main launch was the one that re-queued the sub-round before)
+      rc = decide_tiers(cx, "lm move", g.n, c, lanes, i == 0, hc + MAX_CLASSES + CTR_STRIDE * c, move_args(c, tg));
+      if (rc != SCAMD_OK) return rc;
       hipLaunchKernelGGL(ld_apply_kernel, GRID1(cnt), 0, cx.s, cnt, list, tg, g.k, b.comm, b.Ktot, b.csize, b.flag,
                          b.counters);
       SCAMD_LAUNCH_CHECK();
@@ -2962,16 +2975,11 @@ static int local_moving(LeidenCtx& cx, const LevelGraph& g, int* total_moves) {
         const int cn = cls[i + 1];
         const MoveArgs ma = move_args(cn, tgt[(i + 1) & 1]);
         const int nb_rq = ceil_div(cnt, 256);
-        const dim3 grid((unsigned)(nb_rq + move_blocks(hc[cn])));
-        if (lanes == 32)
-          hipLaunchKernelGGL(ld_requeue_move_kernel<32>, grid, dim3(256), 0, cx.s, nb_rq, cnt, list, (const int*)tg, g.indptr,
-                             g.indices, (const int*)b.comm, b.flag, ma);
-        else if (lanes == 16)
-          hipLaunchKernelGGL(ld_requeue_move_kernel<16>, grid, dim3(256), 0, cx.s, nb_rq, cnt, list, (const int*)tg, g.indptr,
-                             g.indices, (const int*)b.comm, b.flag, ma);
-        else
-          hipLaunchKernelGGL(ld_requeue_move_kernel<64>, grid, dim3(256), 0, cx.s, nb_rq, cnt, list, (const int*)tg, g.indptr,
-                             g.indices, (const int*)b.comm, b.flag, ma);
+        const dim3 grid((unsigned)(nb_rq + blocks_for(lanes, hc[cn])));
+        with_lanes<true>(lanes, [&](auto G) {
+          hipLaunchKernelGGL(ld_requeue_move_kernel<decltype(G)::value>, grid, dim3(256), 0, cx.s, nb_rq, cnt, list, (const int*)tg,
+                             g.indptr, g.indices, (const int*)b.comm, b.flag, ma);
+        });
         SCAMD_LAUNCH_CHECK();
       } else {
         hipLaunchKernelGGL(ld_requeue_kernel, GRID1(cnt), 0, cx.s, cnt, list, tg, g.indptr, g.indices, b.comm, b.flag);
@@ -3038,7 +3046,7 @@ static int polish_level0(LeidenCtx& cx, const LevelGraph& g, int* stats) {
                                               .add(b.rcounters, sizeof(int) * CTR_AREA));
   if (rc != SCAMD_OK) return rc;  // (cx.b lives for this call only: an error return need not swap back)
   const int lanes = level_lanes(g);
-  const int thr_mid = lanes == 16 ? (int)G16_MAX : (lanes == 32 ? (int)(WH_SLOTS / 2 * 3 / 4) : -1);
+  const int thr_mid = lanes_thr_mid(lanes);
   unsigned int round = 0, area = 0;  // (the rounds alternate between the two counter areas, as the sweeps of the local moving do)
   int moved_before = 0, moved_at_full = 0;
   int checked_at = 0;  // moves + splits when the communities were last known to be connected (the input is: an iteration's result)
@@ -3055,7 +3063,7 @@ static int polish_level0(LeidenCtx& cx, const LevelGraph& g, int* stats) {
     LD_FETCH(hc, sw, sizeof(hc), cx.s);
     LD_FETCH(ht, b.counters, sizeof(ht), cx.s);
     LD_SYNC(cx.s);
-    SCAMD_REQUIRE(ht[7] == 0, SCAMD_EINTERNAL, "leiden: hub table overflow (polish)");
+    SCAMD_REQUIRE(ht[PHASE_ERR] == 0, SCAMD_EINTERNAL, "leiden: hub table overflow (polish)");
     const int cnt = hc[0];
     const int moved_last = ht[0] - moved_before;  // moves of the previous round
     moved_before = ht[0];
@@ -3092,30 +3100,10 @@ static int polish_level0(LeidenCtx& cx, const LevelGraph& g, int* stats) {
     ++round;
     ++stats[1];
     const int* list = b.cls_lists;
-    const int n_mid = hc[MAX_CLASSES + CTR_N_MID], n_hub = hc[MAX_CLASSES + CTR_N_HUB];
-    const unsigned nbm = (unsigned)(lanes == 16 ? ceil_div(cnt, 16) : (lanes == 32 ? ceil_div(cnt, 8) : ceil_div(cnt, 4)));
-    if (lanes == 32)
-      hipLaunchKernelGGL(ld_move_kernel<32>, dim3(nbm), dim3(256), 0, cx.s, cnt, list, (const int*)nullptr, (const int*)nullptr,
-                         g.indptr, g.indices, g.wq, g.k, b.comm, b.Ktot, b.csize, gg, -1, cx.seed, b.target, b.mid_list, b.hub_list, ctr);
-    else if (lanes == 16)
-      hipLaunchKernelGGL(ld_move_kernel<16>, dim3(nbm), dim3(256), 0, cx.s, cnt, list, (const int*)nullptr, (const int*)nullptr,
-                         g.indptr, g.indices, g.wq, g.k, b.comm, b.Ktot, b.csize, gg, -1, cx.seed, b.target, b.mid_list, b.hub_list, ctr);
-    else
-      hipLaunchKernelGGL(ld_move_kernel<64>, dim3(nbm), dim3(256), 0, cx.s, cnt, list, (const int*)nullptr, (const int*)nullptr,
-                         g.indptr, g.indices, g.wq, g.k, b.comm, b.Ktot, b.csize, gg, -1, cx.seed, b.target, b.mid_list, b.hub_list, ctr);
-    SCAMD_LAUNCH_CHECK();
-    if (lanes != 64 && n_mid > 0) {
-      hipLaunchKernelGGL(ld_move_kernel<64>, dim3((unsigned)std::min(2048, ceil_div(n_mid, 4))), dim3(256), 0, cx.s, cnt, list,
-                         (const int*)b.mid_list, (const int*)(ctr + 5), g.indptr, g.indices, g.wq, g.k, b.comm, b.Ktot, b.csize, gg,
-                         -1, cx.seed, b.target, b.mid_list, b.hub_list, ctr);
-      SCAMD_LAUNCH_CHECK();
-    }
-    if (n_hub > 0) {
-      hipLaunchKernelGGL(ld_move_hub_kernel, dim3((unsigned)std::min(HUB_GRID, n_hub)), dim3(HUB_THREADS), HUB_LDS, cx.s, b.hub_list,
-                         ctr, list, g.indptr, g.indices, g.wq, g.k, b.comm, b.Ktot, b.csize, gg, -1, cx.seed, b.target,
-                         b.counters + 7, cx.hub_try_probes);
-      SCAMD_LAUNCH_CHECK();
-    }
+    rc = decide_tiers(cx, "polish move", g.n, 0, lanes, true, hc + MAX_CLASSES,
+                      MoveArgs{cnt, list, nullptr, nullptr, g.indptr, g.indices, g.wq, g.k, b.comm, b.Ktot, b.csize, gg, -1, cx.seed,
+                               b.target, b.mid_list, b.hub_list, ctr});
+    if (rc != SCAMD_OK) return rc;
     hipLaunchKernelGGL(ld_polish_lock_kernel, GRID1(cnt), 0, cx.s, cnt, list, (const int*)b.target, (const int*)b.comm, lock, round);
     SCAMD_LAUNCH_CHECK();
     hipLaunchKernelGGL(ld_polish_apply_kernel, GRID1(cnt), 0, cx.s, cnt, list, b.target, g.k, b.comm, b.Ktot, b.csize,
@@ -3136,22 +3124,22 @@ static int refinement(LeidenCtx& cx, const LevelGraph& g, int* n_merged) {
   const unsigned int rseed = cx.seed + 0x9E3779B9u * (unsigned int)cx.iter;
   const unsigned int salt = hash32(rseed ^ 0x5bd1e995u);
   const size_t n = (size_t)g.n;
-  const bool quad = level_is_short_rowed(g);
-  if (quad)
-    hipLaunchKernelGGL(ld_within_kernel<16>, dim3((unsigned)ceil_div(g.n, 16)), dim3(256), 0, cx.s, g.n, g.indptr,
-                       g.indices, g.wq, b.comm, b.a_in);
-  else
-    hipLaunchKernelGGL(ld_within_kernel<64>, GRIDW(g.n), 0, cx.s, g.n, g.indptr, g.indices, g.wq, b.comm, b.a_in);
+  const int lanes = refine_lanes(g);
+  with_lanes<false>(lanes, [&](auto G) {
+    constexpr int L = decltype(G)::value;
+    hipLaunchKernelGGL(ld_within_kernel<L>, dim3((unsigned)blocks_for(L, g.n)), dim3(256), 0, cx.s, g.n, g.indptr, g.indices, g.wq,
+                       b.comm, b.a_in);
+  });
   SCAMD_LAUNCH_CHECK();
   const int n_cls = rf_classes(g.n);
-  int* rc0 = b.rcounters;  // [0, MAX_CLASSES): class list lengths; then per sub-round c: [0] joiners, [4] hubs, [5] overflow
+  int* rc0 = b.rcounters;  // [0, MAX_CLASSES): class list lengths; then per sub-round c: [CTR_JOINED], [CTR_HUB], [CTR_OVF]
   // (also clears rc0, the phase counters and the join stamps b.touched: three memsets until round 6)
   hipLaunchKernelGGL(ld_refine_init_kernel, GRID1(g.n), 0, cx.s, g.n, g.k, b.a_in, b.comm, b.ref, b.refsize, b.Kref,
                      b.Eref, b.vrec, b.trec, b.touched, rc0, (int)(MAX_CLASSES + CTR_STRIDE * n_cls), b.counters);
   SCAMD_LAUNCH_CHECK();
   hipLaunchKernelGGL(ld_refine_candidates_kernel, dim3((unsigned)ceil_div(g.n, 1024)), dim3(1024), 0, cx.s, g.n, g.k,
                      b.comm, b.Ktot, b.a_in, gg, b.cls_lists, rc0, n_cls, salt, g.indptr,
-                     quad ? (int)G16_MAX : -1, (int)WH_MAX_DEG);
+                     lanes_thr_mid(lanes), (int)WH_MAX_DEG);
   SCAMD_LAUNCH_CHECK();
   LD_DBG_SYNC(cx, "rf candidates n=%d classes=%d", g.n, n_cls);
   int hc[CTR_AREA];  // class list lengths, then per sub-round [CTR_N_MID] / [CTR_N_HUB] (ld_refine_candidates_kernel)
@@ -3165,64 +3153,33 @@ static int refinement(LeidenCtx& cx, const LevelGraph& g, int* n_merged) {
     if (cnt == 0) continue;
     const int* list = b.cls_lists + (size_t)c * n;
     int* ctr = rc0 + MAX_CLASSES + CTR_STRIDE * c;
-    const int n_mid = hc[MAX_CLASSES + CTR_STRIDE * c + CTR_N_MID], n_hub = hc[MAX_CLASSES + CTR_STRIDE * c + CTR_N_HUB];
-    const unsigned wgrid = (unsigned)std::min(32768, ceil_div(cnt, 4));
     const unsigned tgrid = (unsigned)std::min(32768, ceil_div(cnt, 256));
-    const unsigned qgrid = (unsigned)std::min(32768, ceil_div(cnt, 16));
-    if (quad) {
-      hipLaunchKernelGGL(ld_refine_propose_kernel<16>, dim3(qgrid), dim3(256), 0, cx.s, list, (const int*)nullptr,
-                         (const int*)nullptr, g.indptr, g.indices, g.wq, g.k, b.comm, b.Ktot, b.ref, b.refsize, b.Kref,
-                         b.Eref, gg, cx.inv_beta, c, n_cls, salt, rseed, b.target, b.mid_list, b.hub_list, ctr, cnt,
-                         b.vrec, b.trec);
-      SCAMD_LAUNCH_CHECK();
-      LD_DBG_SYNC(cx, "rf propose<16> n=%d class=%d cnt=%d", g.n, c, cnt);
-      if (n_mid > 0) {
-        hipLaunchKernelGGL(ld_refine_propose_kernel<64>, dim3((unsigned)std::min(2048, ceil_div(n_mid, 4))), dim3(256), 0, cx.s, list,
-                           (const int*)b.mid_list, (const int*)(ctr + 5), g.indptr, g.indices, g.wq, g.k, b.comm, b.Ktot,
-                           b.ref, b.refsize, b.Kref, b.Eref, gg, cx.inv_beta, c, n_cls, salt, rseed, b.target, b.mid_list,
-                           b.hub_list, ctr, cnt, b.vrec, b.trec);
-        SCAMD_LAUNCH_CHECK();
-        LD_DBG_SYNC(cx, "rf propose<64> overflow n=%d class=%d", g.n, c);
-      }
-    } else {
-      hipLaunchKernelGGL(ld_refine_propose_kernel<64>, dim3(wgrid), dim3(256), 0, cx.s, list, (const int*)nullptr,
-                         (const int*)nullptr, g.indptr, g.indices, g.wq, g.k, b.comm, b.Ktot, b.ref, b.refsize, b.Kref,
-                         b.Eref, gg, cx.inv_beta, c, n_cls, salt, rseed, b.target, b.mid_list, b.hub_list, ctr, cnt,
-                         b.vrec, b.trec);
-      SCAMD_LAUNCH_CHECK();
-      LD_DBG_SYNC(cx, "rf propose<64> n=%d class=%d cnt=%d", g.n, c, cnt);
-    }
-    if (n_hub > 0) {
-      hipLaunchKernelGGL(ld_refine_propose_hub_kernel, dim3((unsigned)std::min(HUB_GRID, n_hub)), dim3(HUB_THREADS), HUB_LDS, cx.s,
-                         b.hub_list, ctr, g.indptr, g.indices, g.wq, g.k, b.comm, b.Ktot, b.ref, b.refsize, b.Kref, b.Eref,
-                         gg, cx.inv_beta, c, n_cls, salt, rseed, b.target, b.counters + 7, b.vrec, b.trec, cx.hub_try_probes);
-      SCAMD_LAUNCH_CHECK();
-      LD_DBG_SYNC(cx, "rf propose hub n=%d class=%d", g.n, c);
-    }
+    const unsigned lgrid = (unsigned)std::min(32768, blocks_for(lanes, cnt));
+    int rc = decide_tiers(cx, "rf propose", g.n, c, lanes, true, hc + MAX_CLASSES + CTR_STRIDE * c,
+                          ProposeArgs{cnt, list, nullptr, nullptr, g.indptr, g.indices, g.wq, g.k, b.comm, b.Ktot, b.ref, b.refsize,
+                                      b.vrec, b.trec, RefineRule{gg, cx.inv_beta, c, n_cls, salt, rseed}, b.target, b.mid_list,
+                                      b.hub_list, ctr});
+    if (rc != SCAMD_OK) return rc;
     hipLaunchKernelGGL(ld_refine_apply_kernel, dim3(tgrid), dim3(256), 0, cx.s, cnt, list, b.target, g.k, b.ref,
                        b.refsize, b.Kref, b.Eref, b.touched, c, b.rlist, ctr, b.vrec, b.trec);
     SCAMD_LAUNCH_CHECK();
     LD_DBG_SYNC(cx, "rf apply n=%d class=%d", g.n, c);
-    if (quad)
-      hipLaunchKernelGGL(ld_refine_cut_update_kernel<16>, dim3(qgrid), dim3(256), 0, cx.s, cnt, b.rlist, g.indptr,
-                         g.indices, g.wq, b.comm, b.ref, b.touched, b.a_in, c, b.Eref, (const int*)ctr,
-                         b.vrec, b.trec);
-    else
-      hipLaunchKernelGGL(ld_refine_cut_update_kernel<64>, dim3(wgrid), dim3(256), 0, cx.s, cnt, b.rlist, g.indptr,
-                         g.indices, g.wq, b.comm, b.ref, b.touched, b.a_in, c, b.Eref, (const int*)ctr,
-                         b.vrec, b.trec);
+    with_lanes<false>(lanes, [&](auto G) {
+      hipLaunchKernelGGL(ld_refine_cut_update_kernel<decltype(G)::value>, dim3(lgrid), dim3(256), 0, cx.s, cnt, b.rlist, g.indptr,
+                         g.indices, g.wq, b.comm, b.ref, b.touched, b.a_in, c, b.Eref, (const int*)(ctr + CTR_JOINED), b.vrec, b.trec);
+    });
     SCAMD_LAUNCH_CHECK();
     LD_DBG_SYNC(cx, "rf cut update n=%d class=%d", g.n, c);
   }
   int hr[CTR_AREA], herr = 0;
   LD_FETCH(hr, rc0, sizeof(int) * (MAX_CLASSES + CTR_STRIDE * n_cls), cx.s);
-  LD_FETCH(&herr, b.counters + 7, sizeof(int), cx.s);
+  LD_FETCH(&herr, b.counters + PHASE_ERR, sizeof(int), cx.s);
   LD_SYNC(cx.s);
   SCAMD_REQUIRE(herr == 0, SCAMD_EINTERNAL, "leiden: hub table overflow (refinement)");
   for (int c = 0; c < n_cls; ++c) {
-    *n_merged += hr[MAX_CLASSES + CTR_STRIDE * c];
+    *n_merged += hr[MAX_CLASSES + CTR_STRIDE * c + CTR_JOINED];
     if (leiden_debug())
-      fprintf(stderr, "[leiden] rf n=%d class=%d/%d cand=%d merges=%d\n", g.n, c, n_cls, hc[c], hr[MAX_CLASSES + CTR_STRIDE * c]);
+      fprintf(stderr, "[leiden] rf n=%d class=%d/%d cand=%d merges=%d\n", g.n, c, n_cls, hc[c], hr[MAX_CLASSES + CTR_STRIDE * c + CTR_JOINED]);
   }
   return SCAMD_OK;
 }
@@ -3319,13 +3276,13 @@ static int aggregate(LeidenCtx& cx, const LevelGraph& g, int n_orig, int level, 
   if (htier[0] > 0) {
     hipLaunchKernelGGL((ld_agg_block_kernel<AGG_MID_SLOTS, 512>), dim3((unsigned)std::min(AGG_MID_GRID, htier[0])), dim3(512),
                        (size_t)AGG_MID_SLOTS * 12, cx.s, b.mid_list, b.counters + 4, inn, b.moff, b.eoff, b.members, g.indptr,
-                       g.indices, g.wq, cid, b.agg_col, b.agg_w, b.rowcnt, b.counters + 7, AGG_MID_MAX, cx.hub_try_probes);
+                       g.indices, g.wq, cid, b.agg_col, b.agg_w, b.rowcnt, b.counters + PHASE_ERR, AGG_MID_MAX, cx.hub_try_probes);
     SCAMD_LAUNCH_CHECK();
   }
   if (htier[1] > 0) {
     hipLaunchKernelGGL((ld_agg_block_kernel<BHUB_SLOTS, 1024>), dim3((unsigned)std::min(HUB_GRID, htier[1])), dim3(1024),
                        HUB_LDS, cx.s, b.big_list, b.counters + 5, inn, b.moff, b.eoff, b.members, g.indptr, g.indices, g.wq,
-                       cid, b.agg_col, b.agg_w, b.rowcnt, b.counters + 7, cx.agg_pass_keys, cx.hub_try_probes);
+                       cid, b.agg_col, b.agg_w, b.rowcnt, b.counters + PHASE_ERR, cx.agg_pass_keys, cx.hub_try_probes);
     SCAMD_LAUNCH_CHECK();
   }
   if (htier[2] > 0) {
@@ -3339,12 +3296,12 @@ static int aggregate(LeidenCtx& cx, const LevelGraph& g, int n_orig, int level, 
     const int64_t parts_bound = (int64_t)htier[2] + g.nnz / chunk + 1;
     hipLaunchKernelGGL((ld_agg_block_kernel<BHUB_SLOTS, 1024>), dim3((unsigned)std::min<int64_t>(HUB_GRID, parts_bound)), dim3(1024),
                        HUB_LDS, cx.s, (const int*)b.part_list, (const int*)(b.counters + 3), inn, (const int64_t*)b.pmoff, b.eoff,
-                       b.members, g.indptr, g.indices, g.wq, cid, b.agg_col, b.agg_w, b.part_cnt, b.counters + 7,
+                       b.members, g.indptr, g.indices, g.wq, cid, b.agg_col, b.agg_w, b.part_cnt, b.counters + PHASE_ERR,
                        cx.agg_pass_keys, cx.hub_try_probes);
     SCAMD_LAUNCH_CHECK();
     hipLaunchKernelGGL(ld_agg_merge_kernel, dim3((unsigned)std::min(HUB_GRID, htier[2])), dim3(1024), HUB_LDS, cx.s,
                        (const int*)b.hub_list, (const int*)b.counters, b.moff, b.eoff, (const int64_t*)b.pmoff, (const int*)b.part_cnt,
-                       (const int*)b.rlist, (const int*)b.touched, b.agg_col, b.agg_w, b.rowcnt, b.counters + 7);
+                       (const int*)b.rlist, (const int*)b.touched, b.agg_col, b.agg_w, b.rowcnt, b.counters + PHASE_ERR);
     SCAMD_LAUNCH_CHECK();
   }
   const CoarseBuf cb{b.pool.indptr + sl.p_off, b.pool.indices + sl.e_off, b.pool.wq + sl.e_off, b.pool.k + sl.p_off};
@@ -3356,12 +3313,12 @@ static int aggregate(LeidenCtx& cx, const LevelGraph& g, int n_orig, int level, 
                      cb.indices, cb.wq, b.counters + 8);  // (+ clears the row-length statistics ld_degstats_kernel adds to)
   SCAMD_LAUNCH_CHECK();
   int64_t nnz_new = 0;
-  int dstat[4] = {0, 0, 0, 0};
+  int max_deg = 0;
   int agg_err = 0;
-  LD_FETCH(&agg_err, b.counters + 7, sizeof(int), cx.s);
+  LD_FETCH(&agg_err, b.counters + PHASE_ERR, sizeof(int), cx.s);
   hipLaunchKernelGGL(ld_degstats_kernel, GRIDK(nn), 0, cx.s, cb.indptr, (int)nn, b.counters + 8);
   SCAMD_LAUNCH_CHECK();
-  LD_FETCH(dstat, b.counters + 8, sizeof(int) * 4, cx.s);
+  LD_FETCH(&max_deg, b.counters + 8, sizeof(int), cx.s);
   LD_FETCH(&nnz_new, cb.indptr + nn, sizeof(int64_t), cx.s);
   if (cx.cpm) {  // sizes add up over the members; strengths are the row sums of the coarse graph
     rc = run_fill(cx, Filler().add(cb.k, sizeof(long long) * nn));
@@ -3375,10 +3332,7 @@ static int aggregate(LeidenCtx& cx, const LevelGraph& g, int n_orig, int level, 
   LD_SYNC(cx.s);
   SCAMD_REQUIRE(agg_err == 0, SCAMD_EINTERNAL, "leiden: coarse-row table overflow");
   out->n = (int)nn;
-  out->max_deg = dstat[0];
-  out->n_gt96 = dstat[1];
-  out->n_gt192 = dstat[2];
-  out->n_gt384 = dstat[3];
+  out->max_deg = max_deg;
   out->nnz = nnz_new;
   out->indptr = cb.indptr;
   out->indices = cb.indices;
@@ -3400,11 +3354,11 @@ static int reuse_level(LeidenCtx& cx, const LevelGraph& g, int n_orig, int level
   if (leiden_debug()) {
     // every stored group lies inside one community of b.comm (nothing has moved below: b.comm is the projection of b.memb)
     for (int pass = 0; pass < 2; ++pass) {
-      hipLaunchKernelGGL(ld_nest_check_kernel, GRID1(g.n), 0, cx.s, g.n, nn, sl.cid, (const int*)b.comm, b.comm_tmp, pass, b.counters + 7);
+      hipLaunchKernelGGL(ld_nest_check_kernel, GRID1(g.n), 0, cx.s, g.n, nn, sl.cid, (const int*)b.comm, b.comm_tmp, pass, b.counters + PHASE_ERR);
       SCAMD_LAUNCH_CHECK();
     }
     int bad = 0;
-    LD_FETCH(&bad, b.counters + 7, sizeof(int), cx.s);
+    LD_FETCH(&bad, b.counters + PHASE_ERR, sizeof(int), cx.s);
     LD_SYNC(cx.s);
     SCAMD_REQUIRE(bad == 0, SCAMD_EINTERNAL, "leiden: the stored level %d is not nested in the partition it is reused for (%d)", level + 1, bad);
   }
@@ -3611,15 +3565,12 @@ static int setup_level0(LeidenCtx& cx, const int64_t* indptr, const int32_t* ind
   hipLaunchKernelGGL(ld_degstats_kernel, GRIDK(n), 0, cx.s, indptr, (int)n, b.counters + 8);
   SCAMD_LAUNCH_CHECK();
   unsigned long long tot = 0;
-  int dstat[4] = {0, 0, 0, 0};
+  int max_deg = 0;
   LD_FETCH(&tot, b.total, sizeof(tot), cx.s);
-  LD_FETCH(dstat, b.counters + 8, sizeof(int) * 4, cx.s);
+  LD_FETCH(&max_deg, b.counters + 8, sizeof(int), cx.s);
   LD_SYNC(cx.s);
   cx.m2 = (double)tot;
-  g0->max_deg = dstat[0];
-  g0->n_gt96 = dstat[1];
-  g0->n_gt192 = dstat[2];
-  g0->n_gt384 = dstat[3];
+  g0->max_deg = max_deg;
   g0->n = (int)n;
   g0->nnz = nnz;
   g0->indptr = indptr;
@@ -3627,11 +3578,11 @@ static int setup_level0(LeidenCtx& cx, const int64_t* indptr, const int32_t* ind
   g0->wq = b.wq0;
   g0->k = b.k0;
   if (cx.cpm && cx.node_weights) {
-    // (b.counters[7] is zero: cleared above, nothing has raised it since)
-    hipLaunchKernelGGL(ld_nodeweight_quantize_kernel, GRID1(n), 0, cx.s, cx.node_weights, (int)n, b.k0, b.counters + 7);
+    // (b.counters[PHASE_ERR] is zero: cleared above, nothing has raised it since)
+    hipLaunchKernelGGL(ld_nodeweight_quantize_kernel, GRID1(n), 0, cx.s, cx.node_weights, (int)n, b.k0, b.counters + PHASE_ERR);
     SCAMD_LAUNCH_CHECK();
     int bad = 0;
-    LD_FETCH(&bad, b.counters + 7, sizeof(int), cx.s);
+    LD_FETCH(&bad, b.counters + PHASE_ERR, sizeof(int), cx.s);
     LD_SYNC(cx.s);
     SCAMD_REQUIRE(bad == 0, SCAMD_EINVAL, "leiden: node weights must lie in [0, 1e6]");
     cx.nw_scale = NODE_WEIGHT_SCALE;
@@ -3780,11 +3731,11 @@ static int leiden_run(const int64_t* indptr, const int32_t* indices, const float
   if (rc != SCAMD_OK) return rc;
   LeidenBuffers& b = cx.b;
   if (initial_membership) {
-    // (b.counters[7] is zero: setup_level0 cleared the counters and checked whatever it raised)
-    hipLaunchKernelGGL(ld_copy_membership_kernel, GRID1(n), 0, cx.s, (int)n, initial_membership, b.memb, b.counters + 7);
+    // (b.counters[PHASE_ERR] is zero: setup_level0 cleared the counters and checked whatever it raised)
+    hipLaunchKernelGGL(ld_copy_membership_kernel, GRID1(n), 0, cx.s, (int)n, initial_membership, b.memb, b.counters + PHASE_ERR);
     SCAMD_LAUNCH_CHECK();
     int bad = 0;
-    LD_FETCH(&bad, b.counters + 7, sizeof(int), cx.s);
+    LD_FETCH(&bad, b.counters + PHASE_ERR, sizeof(int), cx.s);
     LD_SYNC(cx.s);
     SCAMD_REQUIRE(bad == 0, SCAMD_EINVAL, "leiden: initial membership ids must lie in [0, n)");
   } else {

@@ -30,3 +30,21 @@ def csr_from_parts(indptr, indices, data, n):
     from scipy import sparse
 
     return sparse.csr_matrix((np.asarray(data), np.asarray(indices), np.asarray(indptr)), shape=(n, n))
+
+
+def long_rows_graph():
+    """3000 vertices with eight random neighbours each, five of them given 150, 250, 500, 1200 and 2500 more; symmetrised,
+    float32.  The smallest rows in every bucket of the Leiden decide kernels: 97-192 entries overflow from the 16-lane table
+    only, 193-384 from the 16- and the 32-lane tables, longer ones are hub rows (2500: still one pass of the hub table)."""
+    from scipy import sparse
+
+    rng = np.random.default_rng(2)
+    n, deg = 3000, 8
+    m = sparse.coo_matrix((rng.random(n * deg).astype(np.float32) * 0.9 + 0.1, (np.repeat(np.arange(n), deg), rng.integers(0, n, n * deg))),
+                          shape=(n, n)).tocsr()
+    for h, dh in ((0, 150), (1, 250), (2, 500), (3, 1200), (4, 2500)):
+        t = rng.choice(n, dh, replace=False)
+        m = m + sparse.coo_matrix((rng.random(dh).astype(np.float32) * 0.5 + 0.1, (np.full(dh, h), t)), shape=(n, n)).tocsr()
+    m.setdiag(0)
+    m.eliminate_zeros()
+    return m.maximum(m.T).tocsr().astype(np.float32)

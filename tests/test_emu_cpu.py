@@ -447,24 +447,40 @@ def test_leiden_cpm_node_weights(emu):
 
 def test_leiden_hub_rows(emu):
     """a vertex with 2500 neighbours (multi-pass hub tables) and vertices of 150 .. 1200 (overflow list, hub list tiers)"""
-    from scipy import sparse
-
+    from helpers import long_rows_graph
     from oracle import leiden as ol
 
     H, lib = emu
-    rng = np.random.default_rng(2)
-    n, deg = 3000, 8
-    m = sparse.coo_matrix((rng.random(n * deg).astype(np.float32) * 0.9 + 0.1, (np.repeat(np.arange(n), deg), rng.integers(0, n, n * deg))),
-                          shape=(n, n)).tocsr()
-    for h, dh in ((0, 150), (1, 250), (2, 500), (3, 1200), (4, 2500)):
-        t = rng.choice(n, dh, replace=False)
-        m = m + sparse.coo_matrix((rng.random(dh).astype(np.float32) * 0.5 + 0.1, (np.full(dh, h), t)), shape=(n, n)).tocsr()
-    m.setdiag(0)
-    m.eliminate_zeros()
-    m = m.maximum(m.T).tocsr().astype(np.float32)
+    m = long_rows_graph()
     memb, q, _ = H.leiden(lib, m, seed=0)
     assert abs(q - ol.modularity(m, memb)) < 1e-9
     assert q > ol.leiden(m, seed=0)[1] - 0.01
+
+
+def test_leiden_long_row_tiers_agree(emu, monkeypatch):
+    """the decide step of a row is the same rule in every tier: with 64, 16 and 32 lanes per vertex (SCAMD_LEIDEN_QUAD = 0 /
+    1 / 2) the rows of 150 .. 2500 entries are decided by the main launch, the 64-lane overflow pass or the hub pass, and the
+    partition must not depend on which.  Slots 18 / 19 of scamd_leiden_last_stats (vertices taken over by the overflow pass /
+    handed to the hub pass) show that the tiers were reached: with 64 lanes there is no overflow tier."""
+    from helpers import long_rows_graph
+    from oracle import leiden as ol
+
+    H, lib = emu
+    m = long_rows_graph()
+    monkeypatch.setenv("SCAMD_LEIDEN_SMALL", "0")
+    out = {}
+    for quad in ("0", "1", "2"):
+        monkeypatch.setenv("SCAMD_LEIDEN_QUAD", quad)
+        memb, q, nc = H.leiden(lib, m, seed=0, n_iterations=2)
+        st = (C.c_int32 * 20)()
+        lib.scamd_leiden_last_stats(st, 20)
+        print(f"QUAD={quad}: Q={q!r} communities={nc} overflow pass={st[18]} hub pass={st[19]}")
+        out[quad] = (memb, q, nc, st[18], st[19])
+        assert abs(q - ol.modularity(m, memb)) < 1e-8
+        assert st[19] > 0
+        assert (st[18] == 0) if quad == "0" else (st[18] > 0)
+    for quad in ("1", "2"):
+        assert out[quad][1] == out["0"][1] and out[quad][2] == out["0"][2] and np.array_equal(out[quad][0], out["0"][0])
 
 
 def test_pca_chain(emu):

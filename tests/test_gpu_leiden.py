@@ -241,3 +241,27 @@ def test_leiden_quarter_wave_kernels_agree(K, monkeypatch):
         m1, q1, nc1 = K.leiden(ip, ix, w, n, seed=7)
         assert nc0 == nc1 and q0 == q1
         assert np.array_equal(m0.cpu().numpy(), m1.cpu().numpy())
+
+
+def test_leiden_long_row_tiers_agree(K, monkeypatch):
+    """the decide step of a row is the same rule in every tier: with 64, 16 and 32 lanes per vertex (SCAMD_LEIDEN_QUAD = 0 /
+    1 / 2) the rows of 150 .. 2500 entries are decided by the main launch, the 64-lane overflow pass or the hub pass, and the
+    partition must not depend on which.  Slots 18 / 19 of scamd_leiden_last_stats (vertices taken over by the overflow pass /
+    handed to the hub pass) show that the tiers were reached: with 64 lanes there is no overflow tier."""
+    from helpers import long_rows_graph
+
+    m = long_rows_graph()
+    ip, ix, w, n = _graph_dev(m)
+    monkeypatch.setenv("SCAMD_LEIDEN_SMALL", "0")
+    out = {}
+    for quad in ("0", "1", "2"):
+        monkeypatch.setenv("SCAMD_LEIDEN_QUAD", quad)
+        memb, q, nc = K.leiden(ip, ix, w, n, seed=0)
+        st = K.leiden_last_stats()
+        print(f"QUAD={quad}: Q={q!r} communities={nc} overflow pass={st['overflow_pass_vertices']} hub pass={st['hub_pass_vertices']}")
+        out[quad] = (memb.cpu().numpy(), q, nc)
+        assert abs(q - ol.modularity(m, out[quad][0])) < 1e-8
+        assert st["hub_pass_vertices"] > 0
+        assert (st["overflow_pass_vertices"] == 0) if quad == "0" else (st["overflow_pass_vertices"] > 0)
+    for quad in ("1", "2"):
+        assert out[quad][1] == out["0"][1] and out[quad][2] == out["0"][2] and np.array_equal(out[quad][0], out["0"][0])
