@@ -332,22 +332,27 @@ int scamd_leiden_csr_nw_f32(const int64_t* indptr, const int32_t* indices, const
                             const int32_t* initial_membership, int32_t* membership, double* modularity_host,
                             int32_t* n_communities_host, void* workspace, size_t workspace_bytes,
                             scamd_stream_t stream);
-/* Statistics of the last scamd_leiden_csr_f32 call on this thread:
- *   [0] outer iterations run, [1] kernel launches, [2] blocking host round trips,
- *   [3] full sweeps / [4] rounds / [5] vertices moved by the final polish (n_iterations < 0: strictly monotone
- *       single-vertex moves until a sweep over ALL vertices finds no improving one -- the node optimality a stable
- *       partition of leidenalg / igraph has, src/scanpy/tools/_leiden.py:166-196 with n_iterations=-1),
- *   [6] 1 if the polish was skipped because the last iteration itself had proven node optimality,
- *   [7] levels of the first iteration,
- *   [8] local-moving sweeps of the levels that run as separate kernels, [9] their algorithmic traffic in MB (active rows
- *       x (12 B per entry + 16 B per vertex): SURVEY.md 8(d)'s per-sweep figure over the rows a sweep visits),
- *   [10] communities the polish split off (a departing vertex had cut them in two), [11] 1 if the cap on the outer iterations
- *        ([13]; 32 unless SCAMD_LEIDEN_ITER_CAP says otherwise) ended an n_iterations < 0 run instead of convergence --
- *        `tl.leiden` turns it into a UserWarning, [12] 1 if a polish pass stopped at its round cap (node optimality then
- *        unproven; warned about as well), [14] device-to-device copies (0 since round 6: partitions change buffers by
- *        pointer), [15] launches of the multi-region clear kernel (all that is left of the hipMemsetAsync calls).
- * out[0 .. min(n, 16)).  Diagnostics only (bench.py, tools/, the two warnings). */
+/* Statistics of the last scamd_leiden_csr_* call on this thread, out[0 .. min(n, 20)); scamd_leiden_stat_name gives the key of
+ * every slot.  Diagnostics only (bench.py, tools/, the two warnings).
+ *   iterations, launches, host_round_trips: outer iterations run, kernel launches, blocking host round trips;
+ *   polish_full_sweeps / polish_rounds / polish_moves: of the final polish (n_iterations < 0: strictly monotone single-vertex
+ *       moves until a sweep over ALL vertices finds no improving one -- the node optimality a stable partition of leidenalg /
+ *       igraph has, src/scanpy/tools/_leiden.py:166-196 with n_iterations=-1); polish_skipped_proven: 1 if the last iteration
+ *       itself had proven node optimality; polish_splits: communities the polish split off (a departing vertex had cut them in
+ *       two); polish_ended_by_round_cap: 1 if a polish pass stopped at its round cap (node optimality then unproven;
+ *       `tl.leiden` warns);
+ *   levels_first_iteration; lm_sweeps: local-moving sweeps of the levels that run as separate kernels,
+ *       lm_sweep_algorithmic_MB: their algorithmic traffic (active rows x (12 B per entry + 16 B per vertex): SURVEY.md 8(d)'s
+ *       per-sweep figure over the rows a sweep visits);
+ *   ended_by_iteration_cap: 1 if the cap on the outer iterations (iteration_cap; 32 unless SCAMD_LEIDEN_ITER_CAP says
+ *       otherwise) ended an n_iterations < 0 run instead of convergence -- `tl.leiden` turns it into a UserWarning;
+ *   device_fills: launches of the multi-region clear kernel;
+ *   levels_reused / quiet_reuse_iterations: levels that took their coarse graph from the stored hierarchy / iterations that
+ *       ran on it to its end without a move; overflow_pass_vertices / hub_pass_vertices: vertices the 64-lane overflow pass
+ *       took over from a 16- / 32-lane decide launch / handed to the hub pass. */
 void scamd_leiden_last_stats(int32_t* out, int n);
+/* Key of statistics slot `slot` (a static string); NULL for the unused slot 14 and outside [0, 20). */
+const char* scamd_leiden_stat_name(int slot);
 /* Test entry: the component split the polish applies after its moves -- every connected component (over the stored
  * entries) of a community of `membership` (ids in [0, n), device, rewritten in place) becomes a community of its own, id =
  * its smallest vertex; *n_split_host = components - communities (0: membership untouched).  Workspace:

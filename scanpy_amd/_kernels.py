@@ -476,44 +476,27 @@ def leiden(indptr: torch.Tensor, indices: torch.Tensor, weights: torch.Tensor, n
             raise ValueError(f"initial_membership has {init.numel()} entries for {n} vertices")
     if objective.lower() not in ("modularity", "cpm"):
         raise ValueError(f"objective={objective!r}: 'modularity' or 'cpm'")
+    nw = None
     if node_weights is not None:
         if objective.lower() != "cpm":
             raise NotImplementedError("node_weights with the modularity objective (its vertex weights are the strengths)")
         nw = node_weights.to(device=dev, dtype=torch.float32).contiguous()
         if nw.numel() != n:
             raise ValueError(f"node_weights has {nw.numel()} entries for {n} vertices")
-        rc = lib.scamd_leiden_csr_nw_f32(ptr(indptr), ptr(indices), ptr(weights), n, nnz, float(resolution),
-                                         int(n_iterations), float(beta), int(seed) & (2**64 - 1), 1, ptr(nw), ptr(init),
-                                         ptr(memb), C.byref(q), C.byref(nc), ptr(ws), wsz, stream_ptr())
-        _check(rc, "scamd_leiden_csr_nw_f32")
-        return memb, float(q.value), int(nc.value)
-    if objective.lower() == "cpm":
-        rc = lib.scamd_leiden_csr_ex_f32(ptr(indptr), ptr(indices), ptr(weights), n, nnz, float(resolution),
-                                         int(n_iterations), float(beta), int(seed) & (2**64 - 1), 1, ptr(init), ptr(memb),
-                                         C.byref(q), C.byref(nc), ptr(ws), wsz, stream_ptr())
-        _check(rc, "scamd_leiden_csr_ex_f32")
-        return memb, float(q.value), int(nc.value)
-    if init is not None:
-        rc = lib.scamd_leiden_csr_init_f32(ptr(indptr), ptr(indices), ptr(weights), n, nnz, float(resolution),
-                                           int(n_iterations), float(beta), int(seed) & (2**64 - 1), ptr(init), ptr(memb),
-                                           C.byref(q), C.byref(nc), ptr(ws), wsz, stream_ptr())
-        _check(rc, "scamd_leiden_csr_init_f32")
-        return memb, float(q.value), int(nc.value)
-    rc = lib.scamd_leiden_csr_f32(ptr(indptr), ptr(indices), ptr(weights), n, nnz, float(resolution),
-                                  int(n_iterations), float(beta), int(seed) & (2**64 - 1), ptr(memb), C.byref(q),
-                                  C.byref(nc), ptr(ws), wsz, stream_ptr())
-    _check(rc, "scamd_leiden_csr_f32")
+    # (the entry that takes everything: NULL node weights / initial membership are the other three)
+    rc = lib.scamd_leiden_csr_nw_f32(ptr(indptr), ptr(indices), ptr(weights), n, nnz, float(resolution),
+                                     int(n_iterations), float(beta), int(seed) & (2**64 - 1), int(objective.lower() == "cpm"),
+                                     ptr(nw), ptr(init), ptr(memb), C.byref(q), C.byref(nc), ptr(ws), wsz, stream_ptr())
+    _check(rc, "scamd_leiden_csr_nw_f32")
     return memb, float(q.value), int(nc.value)
 
 
 def leiden_last_stats() -> dict:
     """Diagnostics of this thread's last `leiden` call (scamd_leiden_last_stats)."""
-    out = (C.c_int32 * 20)()
-    _lib.load().scamd_leiden_last_stats(out, 20)
-    keys = ("iterations", "launches", "host_round_trips", "polish_full_sweeps", "polish_rounds", "polish_moves",
-            "polish_skipped_proven", "levels_first_iteration", "lm_sweeps", "lm_sweep_algorithmic_MB", "polish_splits",
-            "ended_by_iteration_cap", "polish_ended_by_round_cap", "iteration_cap", None, "device_fills",
-            "levels_reused", "quiet_reuse_iterations", "overflow_pass_vertices", "hub_pass_vertices")  # (slot 14 is unused)
+    lib = _lib.load()
+    keys = _lib.leiden_stat_names(lib)
+    out = (C.c_int32 * len(keys))()
+    lib.scamd_leiden_last_stats(out, len(keys))
     return {k: int(v) for k, v in zip(keys, out) if k is not None}
 
 

@@ -63,6 +63,7 @@ SIGNATURES = {
     "scamd_leiden_csr_ex_f32": (_i32, [_vp, _vp, _vp, _i64, _i64, _f64, _i32, _f64, _u64, _i32, _vp, _vp, C.POINTER(_f64), C.POINTER(_i32), _vp, _sz, _vp]),
     "scamd_leiden_csr_nw_f32": (_i32, [_vp, _vp, _vp, _i64, _i64, _f64, _i32, _f64, _u64, _i32, _vp, _vp, _vp, C.POINTER(_f64), C.POINTER(_i32), _vp, _sz, _vp]),
     "scamd_leiden_last_stats": (None, [C.POINTER(_i32), _i32]),
+    "scamd_leiden_stat_name": (C.c_char_p, [_i32]),
     "scamd_leiden_debug_split_f32": (_i32, [_vp, _vp, _vp, _i64, _i64, _vp, C.POINTER(_i32), _vp, _sz, _vp]),
     "scamd_modularity_csr_f32": (_i32, [_vp, _vp, _vp, _i64, _i64, _vp, _f64, C.POINTER(_f64), _vp, _sz, _vp]),
     "scamd_pp_row_sums_f32": (_i32, [_vp, _vp, _vp, _i64, _i64, _vp, _vp, _vp]),
@@ -101,6 +102,14 @@ def load() -> C.CDLL:
     if lib.scamd_abi_version() != 1:
         raise ScamdError("libscanpy_amd.so ABI version mismatch; rebuild")
     return lib
+
+
+def leiden_stat_names(lib: C.CDLL) -> list:
+    """Key of every slot of scamd_leiden_last_stats (None: unused), from the library's own table."""
+    names = [lib.scamd_leiden_stat_name(i) for i in range(64)]
+    while names and names[-1] is None:
+        names.pop()
+    return [None if k is None else k.decode() for k in names]
 
 
 def check(rc: int, what: str = "") -> None:

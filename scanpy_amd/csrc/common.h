@@ -5,6 +5,7 @@
 #include <cstdarg>
 #include <cstdint>
 #include <cstdio>
+#include <cstdlib>
 #include <cstring>
 
 #include "../../include/scanpy_amd.h"
@@ -55,6 +56,18 @@ struct Workspace {
 };
 
 inline int ceil_div(int64_t a, int64_t b) { return static_cast<int>((a + b - 1) / b); }
+
+// SCAMD_* environment switches.  Read where a call uses them, never cached across calls: tools
+// and tests flip them inside one process.
+inline int env_int(const char* name, int dflt, bool* is_set = nullptr) {
+  const char* e = getenv(name);
+  if (is_set) *is_set = e != nullptr;
+  return e ? atoi(e) : dflt;
+}
+inline bool env_is(const char* name, char c) {  // the switch is set and starts with c ("0 turns off")
+  const char* e = getenv(name);
+  return e && e[0] == c;
+}
 
 // ---- small device -> host read-backs (counters, sizes) between the launches of a host-driven loop ------------------------
 // hipMemcpyAsync into PAGEABLE host memory is a blocking round trip of its own (the runtime stages it): a kernel + two such

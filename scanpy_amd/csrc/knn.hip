@@ -2321,16 +2321,8 @@ __global__ void ivf_pack_image_kernel(const float* __restrict__ x, const float* 
 // ------------------------------------------------------------------------------------------------
 // host side
 // ------------------------------------------------------------------------------------------------
-// SCAMD_KNN_* switches, each read at the call that uses it: the tests flip them inside one process
-static int env_int(const char* name, int dflt, bool* is_set = nullptr) {
-  const char* e = getenv(name);
-  if (is_set) *is_set = e != nullptr;
-  return e ? atoi(e) : dflt;
-}
-static bool env_is(const char* name, char c) {  // the switch is set and starts with c ("0 turns off")
-  const char* e = getenv(name);
-  return e && e[0] == c;
-}
+// SCAMD_KNN_* switches, each read at the call that uses it (common.h: env_int / env_is): the tests
+// flip them inside one process
 
 struct KnnPlan {
   int H, TC, NW, KP;

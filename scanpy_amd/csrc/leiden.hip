@@ -30,29 +30,62 @@
 
 namespace scamd {
 
-// per-call statistics of the last scamd_leiden_csr_f32 on this thread (scamd_leiden_last_stats): [0] outer iterations,
-// [1] kernel launches, [2] blocking host round trips, [3] full sweeps / [4] rounds / [5] moves of the final polish,
-// [6] 1 if the polish was skipped because the last iteration had already proven node optimality, [7] levels of iteration 0,
-// [8] local-moving sweeps of the levels that run as separate kernels (all iterations), [9] their algorithmic traffic in MB:
-//     active rows x (12 B per entry + 16 B per vertex), SURVEY.md 8(d)'s per-sweep figure restricted to the rows a sweep visits,
-// [10] communities the polish split off because a departure had cut them in two, [11] 1 if the iteration cap ended the run,
-// [12] 1 if a polish pass stopped at MAX_POLISH_ROUNDS (node optimality then NOT proven), [13] the iteration cap in force,
-// [14] unused, [15] ld_fill_kernel launches,
-// [16] levels that took their coarse graph from the stored hierarchy instead of refining and aggregating (LevelStore),
-// [17] iterations that ran on the stored hierarchy to its end without a move at any level,
-// [18] vertices the 64-lane overflow pass took over from a 16- / 32-lane decide launch, [19] vertices handed to the hub pass
-//     (decide_tiers: local moving, polish and refinement together; the list builders' counts, so no read-back of their own)
+// Per-call statistics of the last Leiden run on this thread (scamd_leiden_last_stats; scamd_leiden_stat_name gives the key of a
+// slot, the Python layers build their dicts from it).  What the keys of LD_STAT_NAMES do not say:
+//   ST_LM_SWEEPS / ST_LM_SWEEP_MB  the levels that run as separate kernels, all iterations; the traffic is algorithmic: active
+//                                   rows x (12 B per entry + 16 B per vertex), SURVEY.md 8(d)'s per-sweep figure restricted to
+//                                   the rows a sweep visits
+//   ST_POLISH_SKIPPED_PROVEN       the last iteration had already proven node optimality
+//   ST_POLISH_SPLITS               communities the polish split off because a departure had cut them in two
+//   ST_POLISH_ROUND_CAP            a polish pass stopped at MAX_POLISH_ROUNDS: node optimality then NOT proven
+//   ST_LEVELS_REUSED               levels that took their coarse graph from the stored hierarchy (StoredLevel) instead of
+//                                   refining and aggregating
+//   ST_QUIET_REUSE_ITERS           iterations that ran on the stored hierarchy to its end without a move at any level
+//   ST_OVERFLOW_VERTICES / ST_HUB_VERTICES  vertices the 64-lane overflow pass took over from a 16- / 32-lane decide launch /
+//                                   handed to the hub pass (decide_tiers: local moving, polish and refinement together; the list
+//                                   builders' counts, so no read-back of their own)
+enum LdStat : int {
+  ST_ITERATIONS = 0, ST_LAUNCHES, ST_ROUND_TRIPS, ST_POLISH_FULL_SWEEPS, ST_POLISH_ROUNDS, ST_POLISH_MOVES,
+  ST_POLISH_SKIPPED_PROVEN, ST_LEVELS_FIRST_ITER, ST_LM_SWEEPS, ST_LM_SWEEP_MB, ST_POLISH_SPLITS, ST_ENDED_BY_ITER_CAP,
+  ST_POLISH_ROUND_CAP, ST_ITER_CAP, ST_UNUSED_14, ST_DEVICE_FILLS, ST_LEVELS_REUSED, ST_QUIET_REUSE_ITERS,
+  ST_OVERFLOW_VERTICES, ST_HUB_VERTICES, LD_NSTATS
+};
+static_assert(LD_NSTATS == 20 && ST_UNUSED_14 == 14, "the slot numbers are part of the C ABI (scamd_leiden_last_stats)");
+struct LdStatName {
+  int slot;
+  const char* key;
+};
+static const LdStatName LD_STAT_NAMES[] = {
+    {ST_ITERATIONS, "iterations"},
+    {ST_LAUNCHES, "launches"},
+    {ST_ROUND_TRIPS, "host_round_trips"},
+    {ST_POLISH_FULL_SWEEPS, "polish_full_sweeps"},
+    {ST_POLISH_ROUNDS, "polish_rounds"},
+    {ST_POLISH_MOVES, "polish_moves"},
+    {ST_POLISH_SKIPPED_PROVEN, "polish_skipped_proven"},
+    {ST_LEVELS_FIRST_ITER, "levels_first_iteration"},
+    {ST_LM_SWEEPS, "lm_sweeps"},
+    {ST_LM_SWEEP_MB, "lm_sweep_algorithmic_MB"},
+    {ST_POLISH_SPLITS, "polish_splits"},
+    {ST_ENDED_BY_ITER_CAP, "ended_by_iteration_cap"},
+    {ST_POLISH_ROUND_CAP, "polish_ended_by_round_cap"},
+    {ST_ITER_CAP, "iteration_cap"},
+    {ST_DEVICE_FILLS, "device_fills"},
+    {ST_LEVELS_REUSED, "levels_reused"},
+    {ST_QUIET_REUSE_ITERS, "quiet_reuse_iterations"},
+    {ST_OVERFLOW_VERTICES, "overflow_pass_vertices"},
+    {ST_HUB_VERTICES, "hub_pass_vertices"},
+};
 // table slots of a vertex of the sixteen-lanes-per-vertex kernels (the kNN graph itself); rows longer than 3/4 of them go to
 // the wave-per-vertex tier
 constexpr int G16_SLOTS = 128;
 constexpr int G16_MAX = G16_SLOTS * 3 / 4;
-constexpr int LD_NSTATS = 20;
 static thread_local int g_ld_stats[LD_NSTATS] = {0};
-static thread_local double g_ld_sweep_bytes = 0.0;  // -> stats[9] (MB)
+static thread_local double g_ld_sweep_bytes = 0.0;  // -> ST_LM_SWEEP_MB
 #undef SCAMD_LAUNCH_CHECK
 #define SCAMD_LAUNCH_CHECK()                \
   do {                                      \
-    ++g_ld_stats[1];                        \
+    ++g_ld_stats[ST_LAUNCHES];              \
     SCAMD_HIP_CHECK(hipGetLastError());     \
   } while (0)
 // host round trips: the values the host decides on are fetched into a pinned page (common.h: HostReadback -- a copy into
@@ -64,7 +97,7 @@ static thread_local double g_ld_sweep_bytes = 0.0;  // -> stats[9] (MB)
   } while (0)
 #define LD_SYNC(stream)                                       \
   do {                                                        \
-    ++g_ld_stats[2];                                          \
+    ++g_ld_stats[ST_ROUND_TRIPS];                             \
     const int rc_sync_ = host_readback().sync(stream);        \
     if (rc_sync_ != SCAMD_OK) return rc_sync_;                \
   } while (0)
@@ -79,7 +112,19 @@ constexpr int CTR_STRIDE = 16;    // ints per sub-round counter block:
 // [CTR_OVF] rows handed to the 64-lane overflow pass; counted while the class lists are built (count_long_rows): [CTR_N_MID] /
 // [CTR_N_HUB] rows of the class longer than the lanes-per-vertex table / than the wave table
 constexpr int CTR_JOINED = 0, CTR_HUB = 4, CTR_OVF = 5, CTR_N_MID = 8, CTR_N_HUB = 9;
-constexpr int PHASE_ERR = 7;      // slot of the phase counters (LeidenBuffers::counters) a kernel raises when a table overflows
+// Phase counters (LeidenBuffers::counters, 16 ints), by the phase that owns a slot.  Slots [0, PH_PER_PHASE) are cleared when a
+// phase begins (local_moving, polish_level0, refinement, aggregate / reuse_level: one after the other, never overlapping).
+// The component split runs INSIDE a polish pass and clears its own three slots only: it must leave PH_MOVED, PH_BLOCKED and
+// PHASE_ERR alone, and nothing of the aggregation is live then.
+constexpr int PH_PER_PHASE = 8;
+constexpr int PH_MOVED = 0, PH_BLOCKED = 1;  // local moving, polish: moves / blocked (polish: lost the lock), cumulative over the phase
+constexpr int PH_CC_CHANGED = 2, PH_CC_COMPONENTS = 3, PH_CC_COMMUNITIES = 4;  // component split (split_disconnected)
+// aggregation: pmoff slots handed out, parts of split rows, rows of the 512-thread tier, of the 1024-thread tier, split rows
+constexpr int PH_AGG_PART_SLOTS = 2, PH_AGG_PARTS = 3, PH_AGG_MID = 4, PH_AGG_BIG = 5, PH_AGG_SPLIT = 6;
+constexpr int PHASE_ERR = 7;      // every phase: raised by a kernel when a table overflows (and by the input checks of an entry)
+constexpr int PH_MAX_DEG = 8;     // longest row of the level being built (ld_degstats_kernel)
+// written by ld_small_levels_kernel through SmallArgs::info = counters + PH_SMALL_INFO
+constexpr int PH_SMALL_INFO = 12, SM_INFO_LEVELS = 0, SM_INFO_MOVES = 1, SM_INFO_MERGES = 2, SM_INFO_NODES = 3;
 // counter area of a sweep / a refinement: MAX_CLASSES class-list lengths, then one CTR_STRIDE block per sub-round
 constexpr int CTR_AREA = MAX_CLASSES + CTR_STRIDE * MAX_CLASSES;
 constexpr int MAX_LEVELS = 64;
@@ -87,7 +132,7 @@ constexpr int MAX_LEVELS = 64;
 // On graphs without clear communities that takes dozens of iterations in the sequential algorithm as well: oracle/leiden.c
 // needs 44 on the 1M-cell `weak` graph of bench.py (gains of 1e-7 .. 1e-5 Q per iteration from the 6th on; round-6 probe,
 // profiles/r06a_oracle_iters_weak.log), 18 on a 100k sample.  The loop is bounded (SCAMD_LEIDEN_ITER_CAP overrides); a run the
-// bound ends sets stats[11] and `tl.leiden` warns.
+// bound ends sets ST_ENDED_BY_ITER_CAP and `tl.leiden` warns.
 constexpr int MAX_OUTER_ITERS = 32;
 
 __host__ __device__ __forceinline__ unsigned int hash32(unsigned int x) {
@@ -228,6 +273,18 @@ __global__ void ld_iter_init_kernel(int n, const int* __restrict__ memb, int* __
 __global__ void ld_copy_i32_kernel(int n, const int* __restrict__ src, int* __restrict__ dst) {
   const int v = blockIdx.x * blockDim.x + threadIdx.x;
   if (v < n) dst[v] = src[v];
+}
+// memb[v] = init[v]; *err |= 1 when an id lies outside [0, n)
+__global__ void ld_copy_membership_kernel(int n, const int* __restrict__ init, int* __restrict__ memb, int* __restrict__ err) {
+  const int v = blockIdx.x * blockDim.x + threadIdx.x;
+  if (v >= n) return;
+  const int c = init[v];
+  if (c < 0 || c >= n) {
+    atomicOr(err, 1);
+    memb[v] = v;
+  } else {
+    memb[v] = c;
+  }
 }
 
 // ---- block-local pre-aggregation of per-community reductions ---------------------------------------
@@ -773,8 +830,8 @@ __global__ __launch_bounds__(256) void ld_apply_kernel(int n_act, const int* __r
   }
   __syncthreads();
   if (threadIdx.x == 0) {
-    if (s_moved) atomicAdd(&counters[0], s_moved);
-    if (s_blocked) atomicAdd(&counters[1], s_blocked);
+    if (s_moved) atomicAdd(&counters[PH_MOVED], s_moved);
+    if (s_blocked) atomicAdd(&counters[PH_BLOCKED], s_blocked);
   }
 }
 
@@ -901,8 +958,8 @@ __global__ __launch_bounds__(256) void ld_polish_apply_kernel(int n_act, const i
   }
   __syncthreads();
   if (threadIdx.x == 0) {
-    if (s_moved) atomicAdd(&counters[0], s_moved);
-    if (s_lost) atomicAdd(&counters[1], s_lost);
+    if (s_moved) atomicAdd(&counters[PH_MOVED], s_moved);
+    if (s_lost) atomicAdd(&counters[PH_BLOCKED], s_lost);
   }
 }
 
@@ -1399,7 +1456,7 @@ __global__ __launch_bounds__(HUB_THREADS) void ld_refine_propose_hub_kernel(Prop
   }
 }
 
-// counters: [0] merges of this sub-round (= joiner list length)
+// counters: the sub-round's counter block; [CTR_JOINED] merges of this sub-round (= joiner list length)
 __global__ void ld_refine_apply_kernel(int n_cand, const int* __restrict__ list, const int* __restrict__ target,
                                        const long long* __restrict__ k, int* __restrict__ ref,
                                        int* __restrict__ refsize, unsigned long long* __restrict__ Kref,
@@ -1414,7 +1471,7 @@ __global__ void ld_refine_apply_kernel(int n_cand, const int* __restrict__ list,
     // list appends are aggregated per wave: one returning atomic per wave instead of one per element
     const unsigned long long mj = __ballot(t >= 0);
     int bj = 0;
-    if (lane == 0 && mj) bj = atomicAdd(&counters[0], __popcll(mj));
+    if (lane == 0 && mj) bj = atomicAdd(&counters[CTR_JOINED], __popcll(mj));
     bj = __shfl(bj, 0);
     if (t >= 0) {
       // v is a singleton (ref[v] == v) joining t; t's members do not move in this sub-round
@@ -1446,7 +1503,7 @@ __global__ void ld_refine_init_kernel(int n, const long long* __restrict__ k, co
   int v = blockIdx.x * blockDim.x + threadIdx.x;
   if (blockIdx.x == 0) {  // class list lengths + per-sub-round counters of this refinement, phase counters
     for (int i = threadIdx.x; i < rc0_words; i += blockDim.x) rc0[i] = 0;
-    if (threadIdx.x < 8) counters[threadIdx.x] = 0;
+    if (threadIdx.x < PH_PER_PHASE) counters[threadIdx.x] = 0;
   }
   if (v < n) {
     touched[v] = -1;  // join sub-round stamps: -1 = never
@@ -1536,7 +1593,7 @@ __global__ void ld_coarse_comm_kernel(int n, const int* __restrict__ cid, const 
   int v = blockIdx.x * blockDim.x + threadIdx.x;
   if (v < n) comm_new[cid[v]] = rep[comm[v]];
   if (v < nn) cursor[v] = 0;  // (nn <= n: fill cursors of the member scatter)
-  if (v < 8) counters[v] = 0;
+  if (v < PH_PER_PHASE) counters[v] = 0;
 }
 __global__ void ld_remap_kernel(int n_orig, const int* __restrict__ cid, int* __restrict__ node_of) {
   int i = blockIdx.x * blockDim.x + threadIdx.x;
@@ -1576,7 +1633,7 @@ __device__ __forceinline__ int64_t agg_need(int64_t dsum, int nn) { return dsum 
 constexpr int AGG_SPLIT_NN_MAX = 5600;
 
 // one wave per coarse node; nodes needing more than the wave table go to the mid / big lists
-// (counters[4] / counters[5])
+// (counters[PH_AGG_MID] / counters[PH_AGG_BIG]); rows to be split go to split_list (counters[PH_AGG_SPLIT])
 __global__ __launch_bounds__(256) void ld_agg_wave_kernel(
     int nn, const int64_t* __restrict__ moff, const int64_t* __restrict__ eoff, const int* __restrict__ members,
     const int64_t* __restrict__ indptr, const int* __restrict__ indices, const long long* __restrict__ wq,
@@ -1600,9 +1657,9 @@ __global__ __launch_bounds__(256) void ld_agg_wave_kernel(
     if (lane == 0) {
       // (the very largest rows of a coarse level -- ~1e6 member entries behind a few hundred distinct neighbours -- are cut
       // into parts for several workgroups and merged: ld_agg_parts_kernel; only where one table holds every key of the level)
-      if (dsum > split_work && nn <= AGG_SPLIT_NN_MAX) split_list[atomicAdd(&counters[6], 1)] = c;
-      else if (need <= mid_max && dsum <= mid_work) mid_list[atomicAdd(&counters[4], 1)] = c;
-      else big_list[atomicAdd(&counters[5], 1)] = c;
+      if (dsum > split_work && nn <= AGG_SPLIT_NN_MAX) split_list[atomicAdd(&counters[PH_AGG_SPLIT], 1)] = c;
+      else if (need <= mid_max && dsum <= mid_work) mid_list[atomicAdd(&counters[PH_AGG_MID], 1)] = c;
+      else big_list[atomicAdd(&counters[PH_AGG_BIG], 1)] = c;
     }
     return;
   }
@@ -1776,12 +1833,12 @@ __global__ void ld_agg_parts_kernel(const int* __restrict__ split_list, int* __r
                                     const int64_t* __restrict__ eoff, int64_t chunk, int64_t* __restrict__ pmoff,
                                     int* __restrict__ part_list, int* __restrict__ split_first, int* __restrict__ split_np) {
   const int s = blockIdx.x * blockDim.x + threadIdx.x;
-  if (s >= counters[6]) return;
+  if (s >= counters[PH_AGG_SPLIT]) return;
   const int c = split_list[s];
   const int64_t m0 = moff[c], m1 = moff[c + 1];
   const int64_t u0 = eoff[m0], dsum = eoff[m1] - u0;
   const int np = (int)((dsum + chunk - 1) / chunk);
-  const int base = atomicAdd(&counters[2], np + 1);
+  const int base = atomicAdd(&counters[PH_AGG_PART_SLOTS], np + 1);
   split_first[s] = base;
   split_np[s] = np;
   for (int j = 0; j < np; ++j) {
@@ -1796,7 +1853,7 @@ __global__ void ld_agg_parts_kernel(const int* __restrict__ split_list, int* __r
       }
     }
     pmoff[base + j] = lo;
-    part_list[atomicAdd(&counters[3], 1)] = base + j;
+    part_list[atomicAdd(&counters[PH_AGG_PARTS], 1)] = base + j;
   }
   pmoff[base + np] = m1;
 }
@@ -1812,7 +1869,7 @@ __global__ __launch_bounds__(1024) void ld_agg_merge_kernel(const int* __restric
   int* keys = reinterpret_cast<int*>(agg_smem + BHUB_SLOTS);
   __shared__ int sh_cnt;
   const int lane = threadIdx.x & 63;
-  const int n_split = counters[6];
+  const int n_split = counters[PH_AGG_SPLIT];
   for (int s = blockIdx.x; s < n_split; s += gridDim.x) {
     const int c = split_list[s];
     const int64_t u0 = eoff[moff[c]];
@@ -1916,7 +1973,7 @@ struct SmallArgs {
   int iter;
   int lm_stop_permille;
   int seq_n;               // levels of at most this many vertices move one vertex at a time
-  int* info;               // [0] levels, [1] moves, [2] merges, [3] nodes of the last level
+  int* info;               // counters + PH_SMALL_INFO: [SM_INFO_LEVELS], [SM_INFO_MOVES], [SM_INFO_MERGES], [SM_INFO_NODES] of the last level
 };
 
 struct SmallLds {
@@ -2368,10 +2425,10 @@ __global__ __launch_bounds__(SM_THREADS) void ld_small_levels_kernel(SmallArgs a
   __syncthreads();
   for (int i = t; i < n_in; i += SM_THREADS) a.comm[i] = L.comm[L.tail_of[i]];
   if (t == 0) {
-    a.info[0] = levels;
-    a.info[1] = tot_moves;
-    a.info[2] = tot_merges;
-    a.info[3] = n;
+    a.info[SM_INFO_LEVELS] = levels;
+    a.info[SM_INFO_MOVES] = tot_moves;
+    a.info[SM_INFO_MERGES] = tot_merges;
+    a.info[SM_INFO_NODES] = n;
   }
 }
 
@@ -2556,14 +2613,8 @@ struct LeidenBuffers {
 
 // member entries per part of a split coarse row / entries from which a row is split (SCAMD_LEIDEN_AGG_SPLIT_CHUNK / _WORK:
 // tests push small graphs through the split path; resolved here so that the workspace query and the run agree)
-static int64_t agg_split_chunk() {
-  const char* e = getenv("SCAMD_LEIDEN_AGG_SPLIT_CHUNK");
-  return e ? std::max<int64_t>(64, atoll(e)) : 131072;
-}
-static int64_t agg_split_work() {
-  const char* e = getenv("SCAMD_LEIDEN_AGG_SPLIT_WORK");
-  return std::max<int64_t>(agg_split_chunk(), e ? atoll(e) : 262144);
-}
+static int64_t agg_split_chunk() { return std::max(64, env_int("SCAMD_LEIDEN_AGG_SPLIT_CHUNK", 131072)); }
+static int64_t agg_split_work() { return std::max<int64_t>(agg_split_chunk(), env_int("SCAMD_LEIDEN_AGG_SPLIT_WORK", 262144)); }
 static void leiden_carve(Workspace& ws, int64_t n, int64_t nnz, LeidenBuffers* b) {
   const size_t N = (size_t)n, E = (size_t)std::max<int64_t>(nnz, 1);
   b->wq0 = ws.take<long long>(E);
@@ -2622,7 +2673,7 @@ static void leiden_carve(Workspace& ws, int64_t n, int64_t nnz, LeidenBuffers* b
   }
   b->rowcnt = ws.take<int>(N);
   b->cursor = ws.take<int>(N);
-  b->counters = ws.take<int>(16);  // [0..7] phase counters, [8] longest row of the level being built
+  b->counters = ws.take<int>(16);  // the phase counters (PH_*)
   b->rcounters = ws.take<int>(2 * CTR_AREA);  // two counter areas: the sweeps of the local moving alternate between them
   b->total = ws.take<unsigned long long>(4);
   b->dscratch = ws.take<double>(4 + SUMSQ_BLOCKS);
@@ -2648,6 +2699,22 @@ constexpr int LM_STOP_PERMILLE = 20;
 constexpr int LM_STOP_PERMILLE_BIG = 40;
 constexpr size_t HUB_LDS = (size_t)BHUB_SLOTS * 12;
 
+// Which coarse levels of the pool belong to a partition, and how its hierarchy ended.
+struct Hierarchy {
+  int depth = 0;       // levels 1 .. depth of the pool belong to the hierarchy that produced the partition
+  int end_level = -1;  // that hierarchy ended at this level ...
+  int end_kind = 0;    // ... 1: its refinement merged nothing, 2: its aggregation merged nothing (0: otherwise)
+};
+// ... of the running iteration
+struct IterHierarchy {
+  int built = 0;       // its levels 1 .. built sit in the pool one behind the other (-1: a level did not fit)
+  int end_level = -1, end_kind = 0;
+  bool quiet = false;  // it ran on the stored hierarchy to its end and no separate-kernel level moved anything
+  int small_moves = 0; // moves inside ld_small_levels_kernel (fetched when quiet, handed out by evaluate()'s sync)
+  // what the stored hierarchy is once the iteration's partition has been accepted as b.memb: what it built or reused
+  Hierarchy accepted() const { return Hierarchy{std::max(built, 0), end_level, end_kind}; }
+};
+
 struct LeidenCtx {
   HostReadbackScope readback_scope;  // (the read-backs' destinations are locals of the functions this context is passed to)
   hipStream_t s;
@@ -2667,10 +2734,18 @@ struct LeidenCtx {
   double inv_beta = 0.0;  // 1 / (beta * 2^32): randomness of the refinement's merge rule (0 = greedy)
   int iter = 0;           // outer iteration: part of the refinement's noise seed
   unsigned int seed;
-  bool small_levels = true;   // levels of <= SMALL_N nodes in one workgroup (SCAMD_LEIDEN_SMALL=0: separate kernels)
   int l0_moves = -1;          // moves of the last iteration's level-0 local moving (0: its input was node optimal)
   int n_levels = 0;           // levels the last iteration went through
+  // ---- the SCAMD_LEIDEN_* switches, all read by read_knobs() once per call (tools and tests flip them inside one process) ----
+  bool debug = false;         // SCAMD_LEIDEN_DEBUG=1 / 2: trace on stderr
+  bool debug_sync = false;    // ... =2: also drain the stream after every launch of the class sub-rounds and name it (LD_DBG_SYNC)
+  bool small_levels = true;   // levels of <= SMALL_N nodes in one workgroup (SCAMD_LEIDEN_SMALL=0: separate kernels)
   bool polish = true;         // SCAMD_LEIDEN_POLISH=0: no final polish (A/B; the round-4 behaviour)
+  bool reuse = true;          // SCAMD_LEIDEN_REUSE=0: every iteration refines and aggregates every level (test hook, A/B)
+  int force_lanes = 0;        // SCAMD_LEIDEN_QUAD = 0 / 1 / 2: 64 / 16 / 32 lanes per vertex on every level (0: by row length)
+  int iter_cap = MAX_OUTER_ITERS;  // SCAMD_LEIDEN_ITER_CAP: outer iterations of an n_iterations < 0 run
+  int max_iters = 0;          // SCAMD_LEIDEN_MAX_ITERS (test knob, > 0: in force): cuts such a run short, so that the polish meets an
+                              // unfinished partition
   // coarse-row build tiers (distinct-neighbour bounds); the env overrides exist so the tests can push small graphs
   // through the workgroup and multi-pass tiers
   int agg_wave_max = WH_MAX_DEG;
@@ -2681,29 +2756,42 @@ struct LeidenCtx {
   int agg_wave_work = 2048;
   int agg_mid_work = 65536;
   int hub_try_probes = HUB_TRY_PROBES;  // 0: no optimistic single pass over multi-pass rows (SCAMD_LEIDEN_HUB_TRY_PROBES; tests)
+  int64_t agg_split_chunk = 0, agg_split_work = 0;  // (agg_split_chunk() / agg_split_work(): as the workspace query saw them)
   // ---- the stored hierarchy (StoredLevel) ----
   size_t cap_e = 0, cap_p = 0, cap_c = 0;  // pool capacities: entries, row pointers / vertex weights, map elements
   StoredLevel lv[MAX_LEVELS + 1];          // [l], l >= 1: level l as the running iteration sees it
-  bool reuse = true;      // SCAMD_LEIDEN_REUSE=0: every iteration refines and aggregates every level (test hook, A/B)
-  int depth = 0;          // levels 1 .. depth of the pool belong to the hierarchy that produced b.memb
-  int end_level = -1;     // that hierarchy ended at this level ...
-  int end_kind = 0;       // ... 1: its refinement merged nothing, 2: its aggregation merged nothing (0: otherwise)
-  // of the running iteration (leiden_run commits them when it accepts the iteration's partition)
-  int it_built = 0;       // its levels 1 .. it_built sit in the pool one behind the other (-1: a level did not fit)
-  int it_end_level = -1, it_end_kind = 0;
-  bool it_quiet = false;  // it ran on the stored hierarchy to its end and no separate-kernel level moved anything
-  int it_small_moves = 0; // moves inside ld_small_levels_kernel (fetched when it_quiet, handed out by quality()'s sync)
+  Hierarchy kept;        // of the hierarchy that produced b.memb
+  IterHierarchy it;      // of the running iteration (accept_iteration commits it when it accepts the iteration's partition)
 };
 
-static bool g_leiden_debug = false;  // SCAMD_LEIDEN_DEBUG=1, read at every entry (tools switch it inside one process)
-static bool leiden_debug() { return g_leiden_debug; }
+// every SCAMD_LEIDEN_* switch (agg_split_chunk() / agg_split_work() are shared with the workspace query)
+static void read_knobs(LeidenCtx& cx) {
+  cx.debug = env_is("SCAMD_LEIDEN_DEBUG", '1') || env_is("SCAMD_LEIDEN_DEBUG", '2');
+  cx.debug_sync = env_is("SCAMD_LEIDEN_DEBUG", '2');
+  cx.small_levels = !env_is("SCAMD_LEIDEN_SMALL", '0');
+  cx.polish = !env_is("SCAMD_LEIDEN_POLISH", '0');
+  cx.reuse = !env_is("SCAMD_LEIDEN_REUSE", '0');
+  bool quad_set = false;
+  const int quad = env_int("SCAMD_LEIDEN_QUAD", 0, &quad_set);
+  cx.force_lanes = !quad_set ? 0 : (quad == 1 ? 16 : (quad == 2 ? 32 : 64));
+  const int cap = env_int("SCAMD_LEIDEN_ITER_CAP", 0);
+  cx.iter_cap = cap > 0 ? cap : MAX_OUTER_ITERS;
+  cx.max_iters = env_int("SCAMD_LEIDEN_MAX_ITERS", 0);
+  cx.agg_wave_max = std::min(env_int("SCAMD_LEIDEN_AGG_WAVE_MAX", WH_MAX_DEG), (int)WH_MAX_DEG);
+  cx.agg_mid_max = std::min(env_int("SCAMD_LEIDEN_AGG_MID_MAX", AGG_MID_MAX), (int)AGG_MID_MAX);
+  cx.agg_pass_keys = std::max(16, std::min(env_int("SCAMD_LEIDEN_AGG_PASS_KEYS", AGG_BIG_PASS), (int)AGG_BIG_PASS));
+  cx.agg_wave_work = std::max(1, env_int("SCAMD_LEIDEN_AGG_WAVE_WORK", 2048));
+  cx.agg_mid_work = std::max(1, env_int("SCAMD_LEIDEN_AGG_MID_WORK", 65536));
+  cx.hub_try_probes = std::max(0, env_int("SCAMD_LEIDEN_HUB_TRY_PROBES", HUB_TRY_PROBES));
+  cx.agg_split_chunk = agg_split_chunk();
+  cx.agg_split_work = agg_split_work();
+}
 
 // SCAMD_LEIDEN_DEBUG=2: drain the stream after every launch of the class sub-rounds and name it (a device fault then
 // surfaces at the launch that caused it)
-static bool g_leiden_debug_sync = false;
 #define LD_DBG_SYNC(cx, ...)                                  \
   do {                                                        \
-    if (g_leiden_debug_sync) {                                \
+    if ((cx).debug_sync) {                                    \
       (void)hipStreamSynchronize((cx).s);                     \
       fprintf(stderr, "[leiden] done: " __VA_ARGS__);         \
       fputc('\n', stderr);                                    \
@@ -2731,7 +2819,7 @@ static int run_fill(LeidenCtx& cx, const Filler& f) {
   const unsigned grid = (unsigned)std::min<unsigned long long>(2048ull, std::max<unsigned long long>(1ull, (f.max_words / 4 + 255) / 256));
   hipLaunchKernelGGL(ld_fill_kernel, dim3(grid), dim3(256), 0, cx.s, f.a);
   SCAMD_LAUNCH_CHECK();
-  ++g_ld_stats[15];
+  ++g_ld_stats[ST_DEVICE_FILLS];
   return SCAMD_OK;
 }
 
@@ -2792,22 +2880,25 @@ static int quality(LeidenCtx& cx, const LevelGraph& g, const int* comm, double* 
   return SCAMD_OK;
 }
 
+// Ktot / csize and the quality of `comm` on g
+static int evaluate(LeidenCtx& cx, const LevelGraph& g, const int* comm, double* q) {
+  const int rc = compute_totals(cx, g, comm);
+  return rc != SCAMD_OK ? rc : quality(cx, g, comm, q);
+}
+
 // levels whose rows are short on average (the kNN graph itself) take the four-vertices-per-wave kernels
 static_assert(WH_SLOTS / 2 * 3 / 4 == 192 && WH_MAX_DEG == 384,
               "the table ladders of the decide kernels (rows <= 96 / 192 / 384) are written out in their nslots expressions");
 // lanes per vertex of the decision kernels for this level: 16 (four vertices per wave, rows <= 96), 32 (two per wave,
 // rows <= 192: the first coarse levels, ~64 entries per row) or 64.  SCAMD_LEIDEN_QUAD = 0 / 1 / 2 forces 64 / 16 / 32.
-static int level_lanes(const LevelGraph& g) {
-  if (const char* e = getenv("SCAMD_LEIDEN_QUAD")) {
-    const int v = atoi(e);
-    return v == 1 ? 16 : (v == 2 ? 32 : 64);
-  }
+static int level_lanes(const LeidenCtx& cx, const LevelGraph& g) {
+  if (cx.force_lanes) return cx.force_lanes;
   if (g.n <= 0) return 64;
   const int64_t avg = g.nnz / g.n;
   return avg <= 40 ? 16 : (avg <= 110 ? 32 : 64);
 }
 // ... of the refinement's kernels, which exist for 16 and 64 lanes
-static int refine_lanes(const LevelGraph& g) { return level_lanes(g) == 16 ? 16 : 64; }
+static int refine_lanes(const LeidenCtx& cx, const LevelGraph& g) { return level_lanes(cx, g) == 16 ? 16 : 64; }
 // longest row the table of a `lanes`-lane decide kernel takes: longer rows of such a launch overflow to the 64-lane pass
 // (-1: no such tier, the launch is the 64-lane one)
 static int lanes_thr_mid(int lanes) { return lanes == 16 ? (int)G16_MAX : (lanes == 32 ? (int)(WH_SLOTS / 2 * 3 / 4) : -1); }
@@ -2857,13 +2948,13 @@ static int decide_tiers(LeidenCtx& cx, const char* what, int n, int cls, int lan
     launch_overflow_tier(cx, (unsigned)std::min(2048, blocks_for(64, n_mid)), ovf);
     SCAMD_LAUNCH_CHECK();
     LD_DBG_SYNC(cx, "%s<64> overflow n=%d class=%d", what, n, cls);
-    g_ld_stats[18] += n_mid;
+    g_ld_stats[ST_OVERFLOW_VERTICES] += n_mid;
   }
   if (n_hub > 0) {
     launch_hub_tier(cx, (unsigned)std::min(HUB_GRID, n_hub), a, HubTry{cx.b.counters + PHASE_ERR, cx.hub_try_probes});
     SCAMD_LAUNCH_CHECK();
     LD_DBG_SYNC(cx, "%s hub n=%d class=%d", what, n, cls);
-    g_ld_stats[19] += n_hub;
+    g_ld_stats[ST_HUB_VERTICES] += n_hub;
   }
   return SCAMD_OK;
 }
@@ -2894,11 +2985,11 @@ static int local_moving(LeidenCtx& cx, const LevelGraph& g, int* total_moves) {
   const double gg = cx.gscale();
   *total_moves = 0;
   const size_t n = (size_t)g.n;
-  // (one clear launch: totals, re-queue flags, phase counters ([0] moved, [1] blocked (cumulative), [PHASE_ERR] error), the counter
+  // (one clear launch: totals, re-queue flags, phase counters (PH_MOVED, PH_BLOCKED (cumulative), PHASE_ERR), the counter
   // area of sweep 0 -- every later sweep's area is cleared by the ld_compact_cls_kernel launch of the sweep before it)
-  int rc = compute_totals(cx, g, b.comm, Filler().add(b.flag, sizeof(int) * n).add(b.counters, sizeof(int) * 8).add(b.rcounters, sizeof(int) * CTR_AREA));
+  int rc = compute_totals(cx, g, b.comm, Filler().add(b.flag, sizeof(int) * n).add(b.counters, sizeof(int) * PH_PER_PHASE).add(b.rcounters, sizeof(int) * CTR_AREA));
   if (rc != SCAMD_OK) return rc;
-  const int lanes = level_lanes(g);
+  const int lanes = level_lanes(cx, g);
   const int thr_mid = lanes_thr_mid(lanes);
   const int n_cls = lm_classes(cx, g.n);
   int moved_before = 0, quiet = 0, moved_prev2 = 0;
@@ -2910,24 +3001,24 @@ static int local_moving(LeidenCtx& cx, const LevelGraph& g, int* total_moves) {
                        sweep == 0 ? (int*)nullptr : b.flag, b.cls_lists, sw, n_cls, salt, g.indptr, thr_mid, (int)WH_MAX_DEG,
                        b.rcounters + ((sweep + 1) & 1) * CTR_AREA, (int)CTR_AREA);
     SCAMD_LAUNCH_CHECK();
-    int hc[CTR_AREA], ht[8];  // class list lengths, then per sub-round [CTR_N_MID] / [CTR_N_HUB]: long rows of the class
+    int hc[CTR_AREA], ht[PH_PER_PHASE];  // class list lengths, then per sub-round [CTR_N_MID] / [CTR_N_HUB]: long rows of the class
     LD_FETCH(hc, sw, sizeof(int) * (MAX_CLASSES + CTR_STRIDE * n_cls), cx.s);
-    LD_FETCH(ht, b.counters, sizeof(int) * 8, cx.s);
+    LD_FETCH(ht, b.counters, sizeof(ht), cx.s);
     LD_SYNC(cx.s);
     SCAMD_REQUIRE(ht[PHASE_ERR] == 0, SCAMD_EINTERNAL, "leiden: hub table overflow (local moving)");
     int n_act = 0;
     for (int c = 0; c < n_cls; ++c) n_act += hc[c];
-    const int moved_last = ht[0] - moved_before;  // moves of the previous sweep
-    moved_before = ht[0];
-    *total_moves = ht[0];
-    if (leiden_debug()) {
+    const int moved_last = ht[PH_MOVED] - moved_before;  // moves of the previous sweep
+    moved_before = ht[PH_MOVED];
+    *total_moves = ht[PH_MOVED];
+    if (cx.debug) {
       int tot_mid = 0, tot_hub = 0;
       for (int c = 0; c < n_cls; ++c) tot_mid += hc[MAX_CLASSES + CTR_STRIDE * c + CTR_N_MID], tot_hub += hc[MAX_CLASSES + CTR_STRIDE * c + CTR_N_HUB];
       fprintf(stderr, "[leiden] lm n=%d sweep=%d classes=%d act=%d moved_prev=%d blocked_total=%d long rows: mid %d hub %d\n", g.n, sweep,
-              n_cls, n_act, moved_last, ht[1], tot_mid, tot_hub);
+              n_cls, n_act, moved_last, ht[PH_BLOCKED], tot_mid, tot_hub);
     }
     if (n_act == 0) break;
-    ++g_ld_stats[8];
+    ++g_ld_stats[ST_LM_SWEEPS];
     g_ld_sweep_bytes += (double)n_act * (12.0 * (double)g.nnz / (double)std::max(g.n, 1) + 16.0);
     if (sweep > 0) {
       // (with the direction rule on, blocked vertices stay active without anybody moving: two such sweeps end the level)
@@ -2992,10 +3083,9 @@ static int local_moving(LeidenCtx& cx, const LevelGraph& g, int* total_moves) {
 
 // Final polish of the level-0 partition in b.memb (see ld_polish_lock_kernel): full sweeps of lock-arbitrated moves until
 // a sweep over ALL vertices finds no improving move -- node optimality by construction.  b.memb is updated in place;
-// stats[0] = full sweeps, [1] = rounds, [2] = moves, [3] = communities split off (split_disconnected).  Needs b.Kref (the
-// refinement's scratch) as the lock table.
+// *out = what the pass did.  Needs b.Kref (the refinement's scratch) as the lock table.
 // b.comm: every connected component of a community becomes its own community (ids = smallest member); totals recomputed.
-// *n_split = components - communities (0: nothing changed).  Scratch: b.cid, b.counters[2..4].
+// *n_split = components - communities (0: nothing changed).  Scratch: b.cid, the PH_CC_* counters.
 static int split_disconnected(LeidenCtx& cx, const LevelGraph& g, int* n_split) {
   LeidenBuffers& b = cx.b;
   *n_split = 0;
@@ -3003,27 +3093,28 @@ static int split_disconnected(LeidenCtx& cx, const LevelGraph& g, int* n_split) 
   SCAMD_LAUNCH_CHECK();
   for (int it = 0; it < g.n; ++it) {
     {
-      const int rcf = run_fill(cx, Filler().add(b.counters + 2, sizeof(int) * 3));
+      const int rcf = run_fill(cx, Filler().add(b.counters + PH_CC_CHANGED, sizeof(int) * 3));
       if (rcf != SCAMD_OK) return rcf;
     }
     // (several propagation steps per host round trip: the flag only says whether any of them changed something)
     for (int rep = 0; rep < 4; ++rep) {
       hipLaunchKernelGGL(ld_cc_prop_kernel, dim3((unsigned)ceil_div(g.n, 16)), dim3(256), 0, cx.s, g.n, g.indptr, g.indices,
-                         (const int*)b.comm, b.cid, b.counters + 2);
+                         (const int*)b.comm, b.cid, b.counters + PH_CC_CHANGED);
       SCAMD_LAUNCH_CHECK();
     }
     int changed = 0;
-    LD_FETCH(&changed, b.counters + 2, sizeof(int), cx.s);
+    LD_FETCH(&changed, b.counters + PH_CC_CHANGED, sizeof(int), cx.s);
     LD_SYNC(cx.s);
     if (!changed) break;
   }
-  hipLaunchKernelGGL(ld_cc_count_kernel, GRID1(g.n), 0, cx.s, g.n, (const int*)b.cid, (const int*)b.csize, b.counters + 3);
+  hipLaunchKernelGGL(ld_cc_count_kernel, GRID1(g.n), 0, cx.s, g.n, (const int*)b.cid, (const int*)b.csize, b.counters + PH_CC_COMPONENTS);
   SCAMD_LAUNCH_CHECK();
-  int cnt[2] = {0, 0};
-  LD_FETCH(cnt, b.counters + 3, sizeof(cnt), cx.s);
+  static_assert(PH_CC_COMPONENTS == PH_CC_CHANGED + 1 && PH_CC_COMMUNITIES == PH_CC_COMPONENTS + 1, "one clear, one fetch");
+  int cnt[2] = {0, 0};  // components, communities
+  LD_FETCH(cnt, b.counters + PH_CC_COMPONENTS, sizeof(cnt), cx.s);
   LD_SYNC(cx.s);
   *n_split = cnt[0] - cnt[1];
-  if (leiden_debug()) fprintf(stderr, "[leiden] components %d, communities %d\n", cnt[0], cnt[1]);
+  if (cx.debug) fprintf(stderr, "[leiden] components %d, communities %d\n", cnt[0], cnt[1]);
   if (*n_split > 0) {
     std::swap(b.comm, b.cid);  // (the component labels ARE the new partition; b.cid is scratch)
     return compute_totals(cx, g, b.comm);
@@ -3033,19 +3124,24 @@ static int split_disconnected(LeidenCtx& cx, const LevelGraph& g, int* n_split) 
 
 constexpr int MAX_POLISH_ROUNDS = 1 << 16;
 constexpr int MAX_POLISH_PASSES = 6;  // polish -> verifying iteration -> polish ... (each accepted pass raises Q)
-static int polish_level0(LeidenCtx& cx, const LevelGraph& g, int* stats) {
+struct PolishPass {
+  int full_sweeps = 0, rounds = 0, moves = 0;
+  int splits = 0;  // communities split off (split_disconnected)
+};
+static int polish_level0(LeidenCtx& cx, const LevelGraph& g, PolishPass* out) {
   LeidenBuffers& b = cx.b;
   const double gg = cx.gscale();
   const size_t n = (size_t)g.n;
-  stats[0] = stats[1] = stats[2] = stats[3] = 0;
+  PolishPass& ps = *out;
+  ps = PolishPass();
   // the polish works on b.comm in place: the partition changes buffers instead of being copied (b.comm <-> b.memb now and
   // back at the end; what b.comm held is scratch between iterations)
   std::swap(b.comm, b.memb);
   unsigned long long* lock = b.Kref;
-  int rc = compute_totals(cx, g, b.comm, Filler().add(lock, sizeof(unsigned long long) * n).add(b.flag, sizeof(int) * n).add(b.counters, sizeof(int) * 8)
+  int rc = compute_totals(cx, g, b.comm, Filler().add(lock, sizeof(unsigned long long) * n).add(b.flag, sizeof(int) * n).add(b.counters, sizeof(int) * PH_PER_PHASE)
                                               .add(b.rcounters, sizeof(int) * CTR_AREA));
   if (rc != SCAMD_OK) return rc;  // (cx.b lives for this call only: an error return need not swap back)
-  const int lanes = level_lanes(g);
+  const int lanes = level_lanes(cx, g);
   const int thr_mid = lanes_thr_mid(lanes);
   unsigned int round = 0, area = 0;  // (the rounds alternate between the two counter areas, as the sweeps of the local moving do)
   int moved_before = 0, moved_at_full = 0;
@@ -3059,46 +3155,47 @@ static int polish_level0(LeidenCtx& cx, const LevelGraph& g, int* stats) {
                        b.rcounters + ((area + 1u) & 1u) * CTR_AREA, (int)(MAX_CLASSES + CTR_STRIDE));
     SCAMD_LAUNCH_CHECK();
     ++area;
-    int hc[MAX_CLASSES + CTR_STRIDE], ht[8];
+    int hc[MAX_CLASSES + CTR_STRIDE], ht[PH_PER_PHASE];
     LD_FETCH(hc, sw, sizeof(hc), cx.s);
     LD_FETCH(ht, b.counters, sizeof(ht), cx.s);
     LD_SYNC(cx.s);
     SCAMD_REQUIRE(ht[PHASE_ERR] == 0, SCAMD_EINTERNAL, "leiden: hub table overflow (polish)");
     const int cnt = hc[0];
-    const int moved_last = ht[0] - moved_before;  // moves of the previous round
-    moved_before = ht[0];
-    stats[2] = ht[0];
-    if (leiden_debug())
+    const int moved = ht[PH_MOVED];               // ... of the pass so far
+    const int moved_last = moved - moved_before;  // moves of the previous round
+    moved_before = moved;
+    ps.moves = moved;
+    if (cx.debug)
       fprintf(stderr, "[leiden] polish round=%u %s act=%d moved_prev=%d lost_total=%d\n", round, full ? "full" : "flagged", cnt,
-              moved_last, ht[1]);
+              moved_last, ht[PH_BLOCKED]);
     if (round >= MAX_POLISH_ROUNDS) {  // (every round moves at least one vertex and raises Q: a cap, not a rule)
-      g_ld_stats[12] = 1;  // ... but one that leaves node optimality unproven: reported (scamd_leiden_last_stats, tl.leiden warns)
+      g_ld_stats[ST_POLISH_ROUND_CAP] = 1;  // ... but one that leaves node optimality unproven: reported (scamd_leiden_last_stats, tl.leiden warns)
       break;
     }
     if (cnt == 0) {
       // nobody is flagged any more.  If nothing moved since the last sweep over ALL vertices, that sweep was the proof
       // of node optimality; otherwise another full sweep has to give it.
-      if (ht[0] == moved_at_full) {
+      if (moved == moved_at_full) {
         // ... and if anything has moved since the communities were last known to be connected: split what a departure
         // cut in two (the parts are communities of their own then, and the proof has to be given again)
-        if (ht[0] + stats[3] == checked_at) break;
+        if (moved + ps.splits == checked_at) break;
         int n_split = 0;
         rc = split_disconnected(cx, g, &n_split);
         if (rc != SCAMD_OK) return rc;
-        stats[3] += n_split;
-        checked_at = ht[0] + stats[3];
+        ps.splits += n_split;
+        checked_at = moved + ps.splits;
         if (n_split == 0) break;
       }
       full = true;
       continue;
     }
     if (full) {
-      ++stats[0];
-      moved_at_full = ht[0];
+      ++ps.full_sweeps;
+      moved_at_full = moved;
     }
     full = false;
     ++round;
-    ++stats[1];
+    ++ps.rounds;
     const int* list = b.cls_lists;
     rc = decide_tiers(cx, "polish move", g.n, 0, lanes, true, hc + MAX_CLASSES,
                       MoveArgs{cnt, list, nullptr, nullptr, g.indptr, g.indices, g.wq, g.k, b.comm, b.Ktot, b.csize, gg, -1, cx.seed,
@@ -3124,7 +3221,7 @@ static int refinement(LeidenCtx& cx, const LevelGraph& g, int* n_merged) {
   const unsigned int rseed = cx.seed + 0x9E3779B9u * (unsigned int)cx.iter;
   const unsigned int salt = hash32(rseed ^ 0x5bd1e995u);
   const size_t n = (size_t)g.n;
-  const int lanes = refine_lanes(g);
+  const int lanes = refine_lanes(cx, g);
   with_lanes<false>(lanes, [&](auto G) {
     constexpr int L = decltype(G)::value;
     hipLaunchKernelGGL(ld_within_kernel<L>, dim3((unsigned)blocks_for(L, g.n)), dim3(256), 0, cx.s, g.n, g.indptr, g.indices, g.wq,
@@ -3178,7 +3275,7 @@ static int refinement(LeidenCtx& cx, const LevelGraph& g, int* n_merged) {
   SCAMD_REQUIRE(herr == 0, SCAMD_EINTERNAL, "leiden: hub table overflow (refinement)");
   for (int c = 0; c < n_cls; ++c) {
     *n_merged += hr[MAX_CLASSES + CTR_STRIDE * c + CTR_JOINED];
-    if (leiden_debug())
+    if (cx.debug)
       fprintf(stderr, "[leiden] rf n=%d class=%d/%d cand=%d merges=%d\n", g.n, c, n_cls, hc[c], hr[MAX_CLASSES + CTR_STRIDE * c + CTR_JOINED]);
   }
   return SCAMD_OK;
@@ -3196,21 +3293,21 @@ static int place_level(LeidenCtx& cx, const LevelGraph& g, int level, int nn, St
   const size_t need_e = (size_t)std::max<int64_t>(g.nnz, 1), need_p = (size_t)nn + 1, need_c = (size_t)g.n;
   StoredLevel d;
   d.c_n = need_c;
-  if (cx.it_built == level) {
+  if (cx.it.built == level) {
     d.e_off = ext ? 0 : align_up(src.e_off + (size_t)src.g.nnz, POOL_ALIGN);
     d.p_off = ext ? 0 : align_up(src.p_off + (size_t)src.g.n + 1, POOL_ALIGN);
     d.c_off = ext ? 0 : align_up(src.c_off + src.c_n, POOL_ALIGN);
     if (d.e_off + need_e <= cx.cap_e && d.p_off + need_p <= cx.cap_p && d.c_off + need_c <= cx.cap_c) {
       d.cid = b.cid_pool + d.c_off;
-      cx.it_built = level + 1;
-      cx.depth = std::min(cx.depth, level);
+      cx.it.built = level + 1;
+      cx.kept.depth = std::min(cx.kept.depth, level);
       *out = d;
       return SCAMD_OK;
     }
-    cx.it_built = -1;
-    if (leiden_debug()) fprintf(stderr, "[leiden] level %d does not fit behind level %d in the pool: the hierarchy is not kept\n", level + 1, level);
+    cx.it.built = -1;
+    if (cx.debug) fprintf(stderr, "[leiden] level %d does not fit behind level %d in the pool: the hierarchy is not kept\n", level + 1, level);
   }
-  cx.depth = 0;
+  cx.kept.depth = 0;
   d.e_off = (ext || src.e_off >= need_e) ? 0 : cx.cap_e / 2;
   d.p_off = (ext || src.p_off >= need_p) ? 0 : cx.cap_p / 2;
   d.c_off = 0;
@@ -3262,44 +3359,46 @@ static int aggregate(LeidenCtx& cx, const LevelGraph& g, int n_orig, int level, 
   const int inn = (int)nn;
   hipLaunchKernelGGL(ld_agg_wave_kernel, GRIDW(inn), 0, cx.s, inn, b.moff, b.eoff, b.members, g.indptr, g.indices, g.wq,
                      cid, b.agg_col, b.agg_w, b.rowcnt, b.mid_list, b.big_list, b.counters, cx.agg_wave_max,
-                     cx.agg_mid_max, cx.agg_wave_work, cx.agg_mid_work, b.hub_list, agg_split_work());
+                     cx.agg_mid_max, cx.agg_wave_work, cx.agg_mid_work, b.hub_list, cx.agg_split_work);
   SCAMD_LAUNCH_CHECK();
   // workgroup tiers: 512 threads on the 48 KB tables (3 per CU), 1024 threads on the 96 KB table (1 per CU).  Their list
   // lengths are read back first: an empty launch of these shapes costs 40 / 140 us (768 x 512 / 512 x 1024 threads with
   // 48 / 96 KB of LDS each), a host round trip 15 -- and most levels of a clustered graph have no such rows at all.
-  int htier[3] = {0, 0, 0};  // rows of the 512-thread tier, of the 1024-thread tier, split rows
-  LD_FETCH(htier, b.counters + 4, sizeof(int) * 3, cx.s);
+  static_assert(PH_AGG_BIG == PH_AGG_MID + 1 && PH_AGG_SPLIT == PH_AGG_BIG + 1, "one fetch");
+  int htier[3] = {0, 0, 0};
+  LD_FETCH(htier, b.counters + PH_AGG_MID, sizeof(htier), cx.s);
   LD_SYNC(cx.s);
-  if (leiden_debug() && (htier[0] || htier[1]))
+  const int n_mid = htier[0], n_big = htier[1], n_split = htier[2];
+  if (cx.debug && (n_mid || n_big))
     fprintf(stderr, "[leiden] aggregate n=%d -> %d: %d rows through the workgroup tier, %d through the 8192-slot tier\n", g.n, inn,
-            htier[0], htier[1]);
-  if (htier[0] > 0) {
-    hipLaunchKernelGGL((ld_agg_block_kernel<AGG_MID_SLOTS, 512>), dim3((unsigned)std::min(AGG_MID_GRID, htier[0])), dim3(512),
-                       (size_t)AGG_MID_SLOTS * 12, cx.s, b.mid_list, b.counters + 4, inn, b.moff, b.eoff, b.members, g.indptr,
+            n_mid, n_big);
+  if (n_mid > 0) {
+    hipLaunchKernelGGL((ld_agg_block_kernel<AGG_MID_SLOTS, 512>), dim3((unsigned)std::min(AGG_MID_GRID, n_mid)), dim3(512),
+                       (size_t)AGG_MID_SLOTS * 12, cx.s, b.mid_list, b.counters + PH_AGG_MID, inn, b.moff, b.eoff, b.members, g.indptr,
                        g.indices, g.wq, cid, b.agg_col, b.agg_w, b.rowcnt, b.counters + PHASE_ERR, AGG_MID_MAX, cx.hub_try_probes);
     SCAMD_LAUNCH_CHECK();
   }
-  if (htier[1] > 0) {
-    hipLaunchKernelGGL((ld_agg_block_kernel<BHUB_SLOTS, 1024>), dim3((unsigned)std::min(HUB_GRID, htier[1])), dim3(1024),
-                       HUB_LDS, cx.s, b.big_list, b.counters + 5, inn, b.moff, b.eoff, b.members, g.indptr, g.indices, g.wq,
+  if (n_big > 0) {
+    hipLaunchKernelGGL((ld_agg_block_kernel<BHUB_SLOTS, 1024>), dim3((unsigned)std::min(HUB_GRID, n_big)), dim3(1024),
+                       HUB_LDS, cx.s, b.big_list, b.counters + PH_AGG_BIG, inn, b.moff, b.eoff, b.members, g.indptr, g.indices, g.wq,
                        cid, b.agg_col, b.agg_w, b.rowcnt, b.counters + PHASE_ERR, cx.agg_pass_keys, cx.hub_try_probes);
     SCAMD_LAUNCH_CHECK();
   }
-  if (htier[2] > 0) {
+  if (n_split > 0) {
     // split rows: parts -> built as pseudo rows by the 1024-thread builder -> merged (ld_agg_parts_kernel).  The list of
     // split rows borrows b.hub_list, their first part / part count b.rlist / b.touched (refinement scratch, idle here)
-    const int64_t chunk = agg_split_chunk();
-    if (leiden_debug()) fprintf(stderr, "[leiden] aggregate n=%d -> %d: %d rows split into parts of %lld entries\n", g.n, inn, htier[2], (long long)chunk);
-    hipLaunchKernelGGL(ld_agg_parts_kernel, GRID1(htier[2]), 0, cx.s, (const int*)b.hub_list, b.counters, b.moff, b.eoff, chunk,
+    const int64_t chunk = cx.agg_split_chunk;
+    if (cx.debug) fprintf(stderr, "[leiden] aggregate n=%d -> %d: %d rows split into parts of %lld entries\n", g.n, inn, n_split, (long long)chunk);
+    hipLaunchKernelGGL(ld_agg_parts_kernel, GRID1(n_split), 0, cx.s, (const int*)b.hub_list, b.counters, b.moff, b.eoff, chunk,
                        b.pmoff, b.part_list, b.rlist, b.touched);
     SCAMD_LAUNCH_CHECK();
-    const int64_t parts_bound = (int64_t)htier[2] + g.nnz / chunk + 1;
+    const int64_t parts_bound = (int64_t)n_split + g.nnz / chunk + 1;
     hipLaunchKernelGGL((ld_agg_block_kernel<BHUB_SLOTS, 1024>), dim3((unsigned)std::min<int64_t>(HUB_GRID, parts_bound)), dim3(1024),
-                       HUB_LDS, cx.s, (const int*)b.part_list, (const int*)(b.counters + 3), inn, (const int64_t*)b.pmoff, b.eoff,
+                       HUB_LDS, cx.s, (const int*)b.part_list, (const int*)(b.counters + PH_AGG_PARTS), inn, (const int64_t*)b.pmoff, b.eoff,
                        b.members, g.indptr, g.indices, g.wq, cid, b.agg_col, b.agg_w, b.part_cnt, b.counters + PHASE_ERR,
                        cx.agg_pass_keys, cx.hub_try_probes);
     SCAMD_LAUNCH_CHECK();
-    hipLaunchKernelGGL(ld_agg_merge_kernel, dim3((unsigned)std::min(HUB_GRID, htier[2])), dim3(1024), HUB_LDS, cx.s,
+    hipLaunchKernelGGL(ld_agg_merge_kernel, dim3((unsigned)std::min(HUB_GRID, n_split)), dim3(1024), HUB_LDS, cx.s,
                        (const int*)b.hub_list, (const int*)b.counters, b.moff, b.eoff, (const int64_t*)b.pmoff, (const int*)b.part_cnt,
                        (const int*)b.rlist, (const int*)b.touched, b.agg_col, b.agg_w, b.rowcnt, b.counters + PHASE_ERR);
     SCAMD_LAUNCH_CHECK();
@@ -3310,15 +3409,15 @@ static int aggregate(LeidenCtx& cx, const LevelGraph& g, int n_orig, int level, 
   // the order of a row's entries is arbitrary: nothing downstream depends on it (all sums are integer, every
   // choice is an argmax under a total order)
   hipLaunchKernelGGL(ld_agg_compact_kernel, GRIDW(inn), 0, cx.s, inn, b.moff, b.eoff, cb.indptr, b.agg_col, b.agg_w,
-                     cb.indices, cb.wq, b.counters + 8);  // (+ clears the row-length statistics ld_degstats_kernel adds to)
+                     cb.indices, cb.wq, b.counters + PH_MAX_DEG);  // (+ clears the row-length statistics ld_degstats_kernel adds to)
   SCAMD_LAUNCH_CHECK();
   int64_t nnz_new = 0;
   int max_deg = 0;
   int agg_err = 0;
   LD_FETCH(&agg_err, b.counters + PHASE_ERR, sizeof(int), cx.s);
-  hipLaunchKernelGGL(ld_degstats_kernel, GRIDK(nn), 0, cx.s, cb.indptr, (int)nn, b.counters + 8);
+  hipLaunchKernelGGL(ld_degstats_kernel, GRIDK(nn), 0, cx.s, cb.indptr, (int)nn, b.counters + PH_MAX_DEG);
   SCAMD_LAUNCH_CHECK();
-  LD_FETCH(&max_deg, b.counters + 8, sizeof(int), cx.s);
+  LD_FETCH(&max_deg, b.counters + PH_MAX_DEG, sizeof(int), cx.s);
   LD_FETCH(&nnz_new, cb.indptr + nn, sizeof(int64_t), cx.s);
   if (cx.cpm) {  // sizes add up over the members; strengths are the row sums of the coarse graph
     rc = run_fill(cx, Filler().add(cb.k, sizeof(long long) * nn));
@@ -3331,13 +3430,7 @@ static int aggregate(LeidenCtx& cx, const LevelGraph& g, int n_orig, int level, 
   std::swap(b.comm, b.comm_tmp);  // (the coarse phase-1 partition ld_coarse_comm_kernel wrote is b.comm from here on)
   LD_SYNC(cx.s);
   SCAMD_REQUIRE(agg_err == 0, SCAMD_EINTERNAL, "leiden: coarse-row table overflow");
-  out->n = (int)nn;
-  out->max_deg = max_deg;
-  out->nnz = nnz_new;
-  out->indptr = cb.indptr;
-  out->indices = cb.indices;
-  out->wq = cb.wq;
-  out->k = cb.k;
+  *out = LevelGraph{(int)nn, max_deg, nnz_new, cb.indptr, cb.indices, cb.wq, cb.k};
   sl.g = *out;
   cx.lv[level + 1] = sl;
   return SCAMD_OK;
@@ -3351,7 +3444,7 @@ static int reuse_level(LeidenCtx& cx, const LevelGraph& g, int n_orig, int level
   const int nn = sl.g.n;
   SCAMD_REQUIRE(sl.c_n == (size_t)g.n && nn >= 1 && nn < g.n, SCAMD_EINTERNAL, "leiden: stored level %d does not belong to a level of %d vertices",
                 level + 1, g.n);
-  if (leiden_debug()) {
+  if (cx.debug) {
     // every stored group lies inside one community of b.comm (nothing has moved below: b.comm is the projection of b.memb)
     for (int pass = 0; pass < 2; ++pass) {
       hipLaunchKernelGGL(ld_nest_check_kernel, GRID1(g.n), 0, cx.s, g.n, nn, sl.cid, (const int*)b.comm, b.comm_tmp, pass, b.counters + PHASE_ERR);
@@ -3372,48 +3465,54 @@ static int reuse_level(LeidenCtx& cx, const LevelGraph& g, int n_orig, int level
   SCAMD_LAUNCH_CHECK();
   std::swap(b.comm, b.comm_tmp);
   *out = sl.g;
-  ++g_ld_stats[16];
+  ++g_ld_stats[ST_LEVELS_REUSED];
   return SCAMD_OK;
 }
 
-// one Leiden iteration starting from the level-0 partition in b.memb; result back into b.memb
-static double dbg_now(LeidenCtx& cx) {  // debug trace only: drains the stream, then host time in ms
-  (void)hipStreamSynchronize(cx.s);
-  timespec ts;
-  clock_gettime(CLOCK_MONOTONIC, &ts);
-  return ts.tv_sec * 1e3 + ts.tv_nsec * 1e-6;
-}
+// SCAMD_LEIDEN_DEBUG trace of an iteration's levels: stage times (every lap drains the stream) and the lines on stderr.  Idle when
+// the trace is off: no synchronisation, no output.
+struct LevelTrace {
+  LeidenCtx& cx;
+  double last = 0.0;
+  char level[192] = "";  // the head of a level's line: the level and its local moving
+  double lap() {  // ms since the lap before
+    if (!cx.debug) return 0.0;
+    (void)hipStreamSynchronize(cx.s);
+    timespec ts;
+    clock_gettime(CLOCK_MONOTONIC, &ts);
+    const double now = ts.tv_sec * 1e3 + ts.tv_nsec * 1e-6, ms = now - last;
+    last = now;
+    return ms;
+  }
+  void moved(int l, const LevelGraph& g, int moves) {
+    if (cx.debug)
+      snprintf(level, sizeof(level), "[leiden] level %d n=%d nnz=%lld maxdeg=%d: local moving %.2f ms (%d moves)", l, g.n,
+               (long long)g.nnz, g.max_deg, lap(), moves);
+  }
+  __attribute__((format(printf, 2, 3))) void say(const char* fmt, ...) const {
+    if (!cx.debug) return;
+    va_list ap;
+    va_start(ap, fmt);
+    vfprintf(stderr, fmt, ap);
+    va_end(ap);
+  }
+};
 
 // all remaining levels in one workgroup (ld_small_levels_kernel); b.comm[i] = final community of entry node i
 static int small_levels(LeidenCtx& cx, const LevelGraph& g, int level) {
   LeidenBuffers& b = cx.b;
-  SmallArgs a;
-  a.indptr = g.indptr;
-  a.indices = g.indices;
-  a.wq = g.wq;
-  a.k = g.k;
-  a.n = g.n;
-  for (int i = 0; i < 2; ++i) {
-    a.ix[i] = b.sm_ix[i];
-    a.w[i] = b.sm_w[i];
-  }
-  a.first_dst = 0;  // (the entry level lives in the pool or is the caller's graph)
-  a.comm = b.comm;
-  a.gg = cx.gscale();
-  a.inv_beta = cx.inv_beta;
-  a.seed = cx.seed;
-  a.iter = cx.iter;
-  a.lm_stop_permille = LM_STOP_PERMILLE;
-  a.seq_n = SMALL_SEQ_N;
-  a.info = b.counters + 12;
+  int* info = b.counters + PH_SMALL_INFO;
+  // (first_dst = 0: the entry level lives in the pool or is the caller's graph)
+  const SmallArgs a{g.indptr, g.indices, g.wq, g.k, g.n, {b.sm_ix[0], b.sm_ix[1]}, {b.sm_w[0], b.sm_w[1]}, /*first_dst=*/0, b.comm,
+                    cx.gscale(), cx.inv_beta, cx.seed, cx.iter, LM_STOP_PERMILLE, SMALL_SEQ_N, info};
   hipLaunchKernelGGL(ld_small_levels_kernel, dim3(1), dim3(SM_THREADS), sizeof(SmallLds), cx.s, a);
   SCAMD_LAUNCH_CHECK();
-  if (leiden_debug()) {
+  if (cx.debug) {
     int h[4];
-    LD_FETCH(h, b.counters + 12, sizeof(h), cx.s);
+    LD_FETCH(h, info, sizeof(h), cx.s);
     LD_SYNC(cx.s);
     fprintf(stderr, "[leiden] small levels from level %d (n=%d nnz=%lld): %d levels, %d moves, %d merges -> n=%d\n", level, g.n,
-            (long long)g.nnz, h[0], h[1], h[2], h[3]);
+            (long long)g.nnz, h[SM_INFO_LEVELS], h[SM_INFO_MOVES], h[SM_INFO_MERGES], h[SM_INFO_NODES]);
   }
   return SCAMD_OK;
 }
@@ -3431,89 +3530,74 @@ static int leiden_iteration(LeidenCtx& cx, const LevelGraph& g0) {
   cx.l0_moves = -1;  // (a graph small enough to start in the one-workgroup kernel reports no level-0 count)
   bool quiet = cx.reuse && cx.iter >= 1;  // no level so far has moved anything
   int reused = 0;
-  cx.it_built = 0;
-  cx.it_end_level = -1;
-  cx.it_end_kind = 0;
-  cx.it_quiet = false;
-  cx.it_small_moves = 0;
+  cx.it = IterHierarchy();
+  const Hierarchy& kept = cx.kept;  // (place_level lowers its depth as the iteration writes over stored levels)
+  LevelTrace tr{cx};
   for (int level = 0; level < MAX_LEVELS; ++level) {
-    int moves = 0;
-    const bool dbg = leiden_debug();
-    const double t0 = dbg ? dbg_now(cx) : 0.0;
+    tr.lap();
     if (cx.small_levels && g.n <= SMALL_N && g.nnz <= SMALL_NNZ) {
       const int rcs = small_levels(cx, g, level);
       if (rcs != SCAMD_OK) return rcs;
-      if (dbg) fprintf(stderr, "[leiden] small levels %.2f ms\n", dbg_now(cx) - t0);
-      cx.it_end_level = level;
-      if (quiet && level >= 1 && reused == level) {  // (its move count: handed out by the synchronisation of the quality that follows)
-        cx.it_quiet = true;
-        LD_FETCH(&cx.it_small_moves, b.counters + 13, sizeof(int), cx.s);
+      tr.say("[leiden] small levels %.2f ms\n", tr.lap());
+      cx.it.end_level = level;
+      if (quiet && level >= 1 && reused == level) {  // (its move count: handed out by the synchronisation of the evaluate() that follows)
+        cx.it.quiet = true;
+        LD_FETCH(&cx.it.small_moves, b.counters + PH_SMALL_INFO + SM_INFO_MOVES, sizeof(int), cx.s);
       }
       break;
     }
+    int moves = 0;
     int rc = local_moving(cx, g, &moves);
     if (rc != SCAMD_OK) return rc;
     if (level == 0) cx.l0_moves = moves;
     cx.n_levels = level + 1;
-    const double t1 = dbg ? dbg_now(cx) : 0.0;
+    tr.moved(level, g, moves);
     if (moves != 0) quiet = false;
-    if (quiet && cx.it_built == level && cx.depth >= level + 1) {
+    const bool on_store = quiet && cx.it.built == level;  // nothing has moved, and every level so far came from the store
+    if (on_store && kept.depth >= level + 1) {  // reuse this level
       LevelGraph gs;
       rc = reuse_level(cx, g, g0.n, level, &gs);
       if (rc != SCAMD_OK) return rc;
-      cx.it_built = level + 1;
+      cx.it.built = level + 1;
       ++reused;
-      if (dbg)
-        fprintf(stderr, "[leiden] level %d n=%d nnz=%lld maxdeg=%d: local moving %.2f ms (%d moves), reused %.2f ms -> n=%d\n",
-                level, g.n, (long long)g.nnz, g.max_deg, t1 - t0, moves, dbg_now(cx) - t1, gs.n);
+      tr.say("%s, reused %.2f ms -> n=%d\n", tr.level, tr.lap(), gs.n);
       g = gs;
       continue;
     }
-    if (quiet && level >= 1 && reused == level && cx.it_built == level && cx.depth == level && cx.end_level == level && cx.end_kind != 0) {
+    if (on_store && level >= 1 && reused == level && kept.depth == level && kept.end_level == level && kept.end_kind != 0) {
       // the stored hierarchy ended here because nothing merged: so does this one
-      if (dbg)
-        fprintf(stderr, "[leiden] level %d n=%d nnz=%lld maxdeg=%d: local moving %.2f ms (%d moves), reused: the last level\n",
-                level, g.n, (long long)g.nnz, g.max_deg, t1 - t0, moves);
-      cx.it_end_level = level;
-      cx.it_end_kind = cx.end_kind;
-      cx.it_quiet = true;
-      ++g_ld_stats[16];
+      tr.say("%s, reused: the last level\n", tr.level);
+      cx.it.end_level = level;
+      cx.it.end_kind = kept.end_kind;
+      cx.it.quiet = true;
+      ++g_ld_stats[ST_LEVELS_REUSED];
       break;
     }
+    // refine and aggregate
     int merged = 0;
     rc = refinement(cx, g, &merged);
     if (rc != SCAMD_OK) return rc;
-    const double t2 = dbg ? dbg_now(cx) : 0.0;
-    if (dbg)
-      fprintf(stderr, "[leiden] level %d n=%d nnz=%lld maxdeg=%d: local moving %.2f ms (%d moves), refinement %.2f ms (%d merged)\n",
-              level, g.n, (long long)g.nnz, g.max_deg, t1 - t0, moves, t2 - t1, merged);
-    cx.it_end_level = level;
+    tr.say("%s, refinement %.2f ms (%d merged)\n", tr.level, tr.lap(), merged);
+    cx.it.end_level = level;
     if (merged == 0) {
-      cx.it_end_kind = 1;
+      cx.it.end_kind = 1;
       break;
     }
     LevelGraph gn;
     int n_new = 0;
     rc = aggregate(cx, g, g0.n, level, &gn, &n_new);
     if (rc != SCAMD_OK) return rc;
-    if (dbg) fprintf(stderr, "[leiden] level %d aggregate %.2f ms -> n=%d\n", level, dbg_now(cx) - t2, n_new);
+    tr.say("[leiden] level %d aggregate %.2f ms -> n=%d\n", level, tr.lap(), n_new);
     if (n_new == g.n) {
-      cx.it_end_kind = 2;
+      cx.it.end_kind = 2;
       break;
     }
-    cx.it_end_level = -1;
+    cx.it.end_level = -1;
     g = gn;
   }
   hipLaunchKernelGGL(ld_gather_kernel, GRID1(g0.n), 0, cx.s, g0.n, b.comm, b.node_of, b.memb_work);
   SCAMD_LAUNCH_CHECK();
   return SCAMD_OK;
-}
-
-// the iteration's partition was accepted as b.memb: what it built or reused is the stored hierarchy now
-static void own_hierarchy(LeidenCtx& cx) {
-  cx.depth = std::max(cx.it_built, 0);
-  cx.end_level = cx.it_end_level;
-  cx.end_kind = cx.it_end_kind;
 }
 
 // b.memb (values < n) relabelled to consecutive ids ordered by (size desc, first member asc) -> out (the caller's buffer)
@@ -3562,21 +3646,15 @@ static int setup_level0(LeidenCtx& cx, const int64_t* indptr, const int32_t* ind
   SCAMD_LAUNCH_CHECK();
   hipLaunchKernelGGL(ld_sum_kernel, dim3(256), dim3(256), 0, cx.s, b.k0, (int)n, b.total);
   SCAMD_LAUNCH_CHECK();
-  hipLaunchKernelGGL(ld_degstats_kernel, GRIDK(n), 0, cx.s, indptr, (int)n, b.counters + 8);
+  hipLaunchKernelGGL(ld_degstats_kernel, GRIDK(n), 0, cx.s, indptr, (int)n, b.counters + PH_MAX_DEG);
   SCAMD_LAUNCH_CHECK();
   unsigned long long tot = 0;
   int max_deg = 0;
   LD_FETCH(&tot, b.total, sizeof(tot), cx.s);
-  LD_FETCH(&max_deg, b.counters + 8, sizeof(int), cx.s);
+  LD_FETCH(&max_deg, b.counters + PH_MAX_DEG, sizeof(int), cx.s);
   LD_SYNC(cx.s);
   cx.m2 = (double)tot;
-  g0->max_deg = max_deg;
-  g0->n = (int)n;
-  g0->nnz = nnz;
-  g0->indptr = indptr;
-  g0->indices = indices;
-  g0->wq = b.wq0;
-  g0->k = b.k0;
+  *g0 = LevelGraph{(int)n, max_deg, nnz, indptr, indices, b.wq0, b.k0};
   if (cx.cpm && cx.node_weights) {
     // (b.counters[PHASE_ERR] is zero: cleared above, nothing has raised it since)
     hipLaunchKernelGGL(ld_nodeweight_quantize_kernel, GRID1(n), 0, cx.s, cx.node_weights, (int)n, b.k0, b.counters + PHASE_ERR);
@@ -3593,6 +3671,192 @@ static int setup_level0(LeidenCtx& cx, const int64_t* indptr, const int32_t* ind
   return SCAMD_OK;
 }
 
+// What the three Leiden entries (the run, the component-split test entry, the modularity of a given partition) share: the
+// checks of the graph's pointers and shape, the switches, the context over the caller's workspace, the level-0 graph.
+// `what` prefixes the error messages ("leiden", "leiden split", "modularity").
+static int leiden_open(LeidenCtx& cx, const char* what, const int64_t* indptr, const int32_t* indices, const float* weights,
+                       int64_t n, int64_t nnz, void* workspace, size_t workspace_bytes, scamd_stream_t stream, LevelGraph* g0) {
+  SCAMD_REQUIRE(indptr && (nnz == 0 || (indices && weights)), SCAMD_EINVAL, "%s: null pointer", what);
+  SCAMD_REQUIRE(n >= 1 && n < ((int64_t)1 << 31) && nnz >= 0, SCAMD_EINVAL, "%s: bad shape n=%lld nnz=%lld", what, (long long)n,
+                (long long)nnz);
+  read_knobs(cx);
+  cx.s = stream;
+  cx.cap_e = 2 * (size_t)std::max<int64_t>(nnz, 1);
+  cx.cap_p = 2 * ((size_t)n + 1);
+  cx.cap_c = 2 * (size_t)n;
+  Workspace ws(workspace, workspace_bytes);
+  leiden_carve(ws, n, nnz, &cx.b);
+  SCAMD_REQUIRE(workspace && ws.ok, SCAMD_EWORKSPACE, "%s: workspace %zu < required %zu", what, workspace_bytes, ws.used());
+  return setup_level0(cx, indptr, indices, weights, n, nnz, g0);
+}
+
+// what the four scamd_leiden_csr_* entries pass
+struct LeidenCall {
+  const int64_t* indptr; const int32_t* indices; const float* weights; int64_t n, nnz;
+  double resolution; int n_iterations; double beta; uint64_t seed;
+  int objective;  // 0 = modularity, 1 = CPM
+  const float* node_weights; const int32_t* initial_membership;  // NULL: every vertex weighs 1 (CPM) / singletons
+  int32_t* membership; double* modularity_host; int32_t* n_communities_host;
+  void* workspace; size_t workspace_bytes; scamd_stream_t stream;
+};
+
+// One outer iteration from b.memb and its verdict: +1 improved (accepted: the partition is b.memb now and what the iteration
+// built or reused is the stored hierarchy), 0 the same quality, -1 worse (b.memb stands either way: synchronous moves and the
+// randomised refinement are not monotone).  *q_best is raised when the iteration is accepted.
+static int accept_iteration(LeidenCtx& cx, const LevelGraph& g0, int it, double* q_best, int* verdict) {
+  LeidenBuffers& b = cx.b;
+  cx.iter = it;
+  g_ld_stats[ST_ITERATIONS] = it + 1;
+  double q = 0.0;
+  int rc = leiden_iteration(cx, g0);
+  if (rc == SCAMD_OK) rc = evaluate(cx, g0, b.memb_work, &q);
+  if (rc != SCAMD_OK) return rc;
+  if (cx.debug) fprintf(stderr, "[leiden] iteration %d: Q = %.10f (best before %.10f), level-0 moves %d\n", it, q, *q_best, cx.l0_moves);
+  if (cx.it.quiet && cx.it.small_moves == 0) ++g_ld_stats[ST_QUIET_REUSE_ITERS];
+  *verdict = q > *q_best + 1e-12 ? 1 : (q < *q_best - 1e-12 ? -1 : 0);
+  if (*verdict > 0) {
+    *q_best = q;
+    std::swap(b.memb, b.memb_work);
+    cx.kept = cx.it.accepted();
+  }
+  return SCAMD_OK;
+}
+
+static int leiden_run(const LeidenCall& c) {
+  SCAMD_REQUIRE(c.membership, SCAMD_EINVAL, "leiden: null pointer");
+  SCAMD_REQUIRE(c.resolution >= 0.0, SCAMD_EINVAL, "leiden: negative resolution");
+  for (int i = 0; i < LD_NSTATS; ++i) g_ld_stats[i] = 0;
+  g_ld_sweep_bytes = 0.0;
+  const int64_t n = c.n;
+  const int n_iterations = c.n_iterations;
+  LeidenCtx cx;
+  cx.gamma = c.resolution;
+  cx.inv_beta = c.beta > 0.0 ? 1.0 / (c.beta * WSCALE) : 0.0;  // beta <= 0: the greedy limit (largest gain, no "stay")
+  cx.seed = (unsigned int)(c.seed ^ (c.seed >> 32)) * 0x9E3779B1u + 0x632BE5ABu;
+  cx.cpm = c.objective == 1;
+  cx.node_weights = c.node_weights;
+  LevelGraph g0;
+  int rc = leiden_open(cx, "leiden", c.indptr, c.indices, c.weights, n, c.nnz, c.workspace, c.workspace_bytes, c.stream, &g0);
+  if (rc != SCAMD_OK) return rc;
+  if (cx.cpm) cx.small_levels = false;  // (ld_small_levels_kernel derives its coarse vertex weights from row sums: strengths)
+  const struct {
+    const void* kernel;
+    size_t lds;
+  } dyn_lds[] = {{reinterpret_cast<const void*>(ld_move_hub_kernel), HUB_LDS},
+                 {reinterpret_cast<const void*>(ld_refine_propose_hub_kernel), HUB_LDS},
+                 {reinterpret_cast<const void*>(ld_agg_merge_kernel), HUB_LDS},
+                 {reinterpret_cast<const void*>(ld_agg_block_kernel<BHUB_SLOTS, 1024>), HUB_LDS},
+                 {reinterpret_cast<const void*>(ld_small_levels_kernel), sizeof(SmallLds)}};
+  for (const auto& k : dyn_lds) SCAMD_HIP_CHECK(hipFuncSetAttribute(k.kernel, hipFuncAttributeMaxDynamicSharedMemorySize, (int)k.lds));
+  LeidenBuffers& b = cx.b;
+  if (c.initial_membership) {
+    // (b.counters[PHASE_ERR] is zero: setup_level0 cleared the counters and checked whatever it raised)
+    hipLaunchKernelGGL(ld_copy_membership_kernel, GRID1(n), 0, cx.s, (int)n, c.initial_membership, b.memb, b.counters + PHASE_ERR);
+    SCAMD_LAUNCH_CHECK();
+    int bad = 0;
+    LD_FETCH(&bad, b.counters + PHASE_ERR, sizeof(int), cx.s);
+    LD_SYNC(cx.s);
+    SCAMD_REQUIRE(bad == 0, SCAMD_EINVAL, "leiden: initial membership ids must lie in [0, n)");
+  } else {
+    hipLaunchKernelGGL(ld_iota_kernel, GRID1(n), 0, cx.s, b.memb, (int)n);
+    SCAMD_LAUNCH_CHECK();
+  }
+  double q_best = 0.0;
+  if (cx.m2 > 0.0) {
+    rc = evaluate(cx, g0, b.memb, &q_best);
+    if (rc != SCAMD_OK) return rc;
+    // b.memb is ALWAYS the best partition seen (the input of the next iteration); an iteration writes into b.memb_work and
+    // the two change places when it improved -- no copies (round 5: two 4-byte-per-vertex blits per iteration)
+    g_ld_stats[ST_ITER_CAP] = cx.iter_cap;
+    int max_iter = n_iterations < 0 ? cx.iter_cap : n_iterations;
+    if (n_iterations < 0 && cx.max_iters > 0) max_iter = std::min(max_iter, cx.max_iters);
+    int bad_iters = 0;
+    // true once b.memb has been the INPUT of an iteration whose level-0 local moving found nothing to move: its
+    // first sweep decides for every vertex on the final state, so that is a proof of node optimality
+    bool best_is_clean = false;
+    bool ended_by_cap = true;  // the loop below ran out of iterations (n_iterations < 0: the iteration cap) instead of converging
+    for (int it = 0; it < max_iter; ++it) {
+      int verdict = 0;
+      rc = accept_iteration(cx, g0, it, &q_best, &verdict);
+      if (rc != SCAMD_OK) return rc;
+      if (it == 0) g_ld_stats[ST_LEVELS_FIRST_ITER] = cx.n_levels;
+      if (verdict > 0) {
+        bad_iters = 0;
+        best_is_clean = false;
+      } else if (cx.l0_moves == 0) {
+        best_is_clean = true;
+      }
+      // n_iterations < 0: until an iteration changes nothing (leidenalg: `while diff_inc > 0`).  An iteration that
+      // reproduces the best quality exactly found nothing to move -> done.  One that came out WORSE was unlucky in its
+      // random merges (the next one draws different noise, cx.iter is part of the noise seed): two of those in a row end
+      // the run as well -- without this patience a single unlucky iteration right after the first one froze the
+      // result of ONE iteration (Q 0.8028 instead of 0.812 on the 700-cell fixture).
+      if (n_iterations < 0 && verdict <= 0) {
+        ended_by_cap = false;
+        if (verdict == 0 || ++bad_iters >= 2) break;
+        ended_by_cap = true;
+      }
+    }
+    // n_iterations < 0 promises a STABLE partition (leidenalg iterates until an iteration changes nothing; such a
+    // partition is node optimal and g-separated).  Ours is the best of a run of non-monotone iterations.  Unless the last
+    // iteration proved it (best_is_clean): strictly monotone single-vertex moves until a sweep over all vertices finds
+    // none (polish_level0), then -- the moved vertices may have made two communities mergeable, or cut one in two -- ONE
+    // ordinary iteration from the polished partition: its level-0 moving finds nothing, its refinement and coarse levels
+    // re-examine everything else.  No gain: stable, done.  A gain: accepted, and the polish runs again.
+    int n_iter_total = g_ld_stats[ST_ITERATIONS];
+    ended_by_cap = ended_by_cap && max_iter == cx.iter_cap;  // (not the test knob's cap: that one is followed up)
+    g_ld_stats[ST_ENDED_BY_ITER_CAP] = (n_iterations < 0 && ended_by_cap) ? 1 : 0;
+    for (int pr = 0; n_iterations < 0 && cx.polish && pr <= MAX_POLISH_PASSES; ++pr) {
+      if (best_is_clean) {
+        if (pr == 0) g_ld_stats[ST_POLISH_SKIPPED_PROVEN] = 1;
+        break;
+      }
+      PolishPass ps;
+      rc = polish_level0(cx, g0, &ps);
+      if (rc != SCAMD_OK) return rc;
+      g_ld_stats[ST_POLISH_FULL_SWEEPS] += ps.full_sweeps;
+      g_ld_stats[ST_POLISH_ROUNDS] += ps.rounds;
+      g_ld_stats[ST_POLISH_MOVES] += ps.moves;
+      g_ld_stats[ST_POLISH_SPLITS] += ps.splits;
+      if (ps.moves == 0) break;  // the full sweep found no improving move: node optimal as it stands
+      cx.kept.depth = 0;  // b.memb changed in place: the stored hierarchy is no longer its own, the iteration below runs in full
+      double q = 0.0;
+      rc = evaluate(cx, g0, b.memb, &q);
+      if (rc != SCAMD_OK) return rc;
+      if (cx.debug)
+        fprintf(stderr, "[leiden] polish %d: %d full sweeps, %d rounds, %d moves: Q %.10f -> %.10f\n", pr, ps.full_sweeps, ps.rounds,
+                ps.moves, q_best, q);
+      SCAMD_REQUIRE(q >= q_best - 1e-12, SCAMD_EINTERNAL, "leiden: the monotone polish lowered the quality (%.12f -> %.12f)", q_best, q);
+      q_best = q;
+      // (the last pass only polishes what the last accepted iteration left.  A run that the iteration cap ended was still
+      // gaining a little with every iteration -- structure-less graphs do that for dozens of iterations: there is no stable
+      // partition to verify, the polished one is node optimal and connected, and that is what is returned)
+      if (pr == MAX_POLISH_PASSES || ended_by_cap) break;
+      int verdict = 0;
+      rc = accept_iteration(cx, g0, n_iter_total++, &q_best, &verdict);
+      if (rc != SCAMD_OK) return rc;
+      if (verdict <= 0) break;  // stable: the polished partition (b.memb) stands
+    }
+  }
+  if (cx.cpm && cx.m2 > 0.0) {
+    // what is reported is the modularity of the partition (the reference stores `part.modularity`), not the CPM quality the
+    // run maximised: strengths back into k0, totals, resolution 1
+    hipLaunchKernelGGL(ld_strength_kernel, GRIDW(n), 0, cx.s, c.indptr, b.wq0, (int)n, b.k0);
+    SCAMD_LAUNCH_CHECK();
+    cx.cpm = false;
+    cx.gamma = 1.0;
+    rc = evaluate(cx, g0, b.memb, &q_best);
+    if (rc != SCAMD_OK) return rc;
+  }
+  int nc = 0;
+  rc = renumber(cx, (int)n, &nc, c.membership);  // (writes the caller's buffer directly)
+  if (rc != SCAMD_OK) return rc;
+  LD_SYNC(cx.s);
+  if (c.modularity_host) *c.modularity_host = q_best;
+  if (c.n_communities_host) *c.n_communities_host = nc;
+  return SCAMD_OK;
+}
+
 }  // namespace scamd
 
 using namespace scamd;
@@ -3605,30 +3869,12 @@ extern "C" size_t scamd_leiden_workspace_bytes(int64_t n, int64_t nnz) {
   return ws.used();
 }
 
-// memb[v] = init[v]; *err |= 1 when an id lies outside [0, n)
-__global__ void ld_copy_membership_kernel(int n, const int* __restrict__ init, int* __restrict__ memb, int* __restrict__ err) {
-  const int v = blockIdx.x * blockDim.x + threadIdx.x;
-  if (v >= n) return;
-  const int c = init[v];
-  if (c < 0 || c >= n) {
-    atomicOr(err, 1);
-    memb[v] = v;
-  } else {
-    memb[v] = c;
-  }
-}
-
-static int leiden_run(const int64_t* indptr, const int32_t* indices, const float* weights, int64_t n, int64_t nnz,
-                      double resolution, int n_iterations, double beta, uint64_t seed, const int32_t* initial_membership,
-                      int32_t* membership, double* modularity_host, int32_t* n_communities_host, void* workspace,
-                      size_t workspace_bytes, scamd_stream_t stream, int objective, const float* node_weights = nullptr);
-
 extern "C" int scamd_leiden_csr_f32(const int64_t* indptr, const int32_t* indices, const float* weights, int64_t n,
                                     int64_t nnz, double resolution, int n_iterations, double beta, uint64_t seed,
                                     int32_t* membership, double* modularity_host, int32_t* n_communities_host,
                                     void* workspace, size_t workspace_bytes, scamd_stream_t stream) {
-  return leiden_run(indptr, indices, weights, n, nnz, resolution, n_iterations, beta, seed, nullptr, membership,
-                    modularity_host, n_communities_host, workspace, workspace_bytes, stream, 0);
+  return leiden_run(LeidenCall{indptr, indices, weights, n, nnz, resolution, n_iterations, beta, seed, 0, nullptr, nullptr, membership,
+                               modularity_host, n_communities_host, workspace, workspace_bytes, stream});
 }
 
 // ... starting from a given partition instead of singletons (`initial_membership` of leidenalg.find_partition /
@@ -3640,8 +3886,8 @@ extern "C" int scamd_leiden_csr_init_f32(const int64_t* indptr, const int32_t* i
                                          double* modularity_host, int32_t* n_communities_host, void* workspace,
                                          size_t workspace_bytes, scamd_stream_t stream) {
   SCAMD_REQUIRE(initial_membership, SCAMD_EINVAL, "leiden: null initial membership");
-  return leiden_run(indptr, indices, weights, n, nnz, resolution, n_iterations, beta, seed, initial_membership, membership,
-                    modularity_host, n_communities_host, workspace, workspace_bytes, stream, 0);
+  return leiden_run(LeidenCall{indptr, indices, weights, n, nnz, resolution, n_iterations, beta, seed, 0, nullptr, initial_membership,
+                               membership, modularity_host, n_communities_host, workspace, workspace_bytes, stream});
 }
 
 // ... with the objective named: 0 = modularity (the two entry points above), 1 = CPM -- igraph's
@@ -3655,8 +3901,8 @@ extern "C" int scamd_leiden_csr_ex_f32(const int64_t* indptr, const int32_t* ind
                                        double* modularity_host, int32_t* n_communities_host, void* workspace,
                                        size_t workspace_bytes, scamd_stream_t stream) {
   SCAMD_REQUIRE(objective == 0 || objective == 1, SCAMD_EINVAL, "leiden: objective %d (0 = modularity, 1 = CPM)", objective);
-  return leiden_run(indptr, indices, weights, n, nnz, resolution, n_iterations, beta, seed, initial_membership, membership,
-                    modularity_host, n_communities_host, workspace, workspace_bytes, stream, objective);
+  return leiden_run(LeidenCall{indptr, indices, weights, n, nnz, resolution, n_iterations, beta, seed, objective, nullptr,
+                               initial_membership, membership, modularity_host, n_communities_host, workspace, workspace_bytes, stream});
 }
 
 // ... CPM with the caller's vertex weights: igraph's `community_leiden(objective_function='CPM', node_weights=...)`, reachable
@@ -3672,202 +3918,8 @@ extern "C" int scamd_leiden_csr_nw_f32(const int64_t* indptr, const int32_t* ind
   SCAMD_REQUIRE(objective == 0 || objective == 1, SCAMD_EINVAL, "leiden: objective %d (0 = modularity, 1 = CPM)", objective);
   SCAMD_REQUIRE(objective == 1 || node_weights == nullptr, SCAMD_EUNSUPPORTED,
                 "leiden: node weights with the modularity objective (its vertex weights are the strengths)");
-  return leiden_run(indptr, indices, weights, n, nnz, resolution, n_iterations, beta, seed, initial_membership, membership,
-                    modularity_host, n_communities_host, workspace, workspace_bytes, stream, objective, node_weights);
-}
-
-static int leiden_run(const int64_t* indptr, const int32_t* indices, const float* weights, int64_t n, int64_t nnz,
-                      double resolution, int n_iterations, double beta, uint64_t seed, const int32_t* initial_membership,
-                      int32_t* membership, double* modularity_host, int32_t* n_communities_host, void* workspace,
-                      size_t workspace_bytes, scamd_stream_t stream, int objective, const float* node_weights) {
-  SCAMD_REQUIRE(indptr && membership && (nnz == 0 || (indices && weights)), SCAMD_EINVAL, "leiden: null pointer");
-  SCAMD_REQUIRE(n >= 1 && n < ((int64_t)1 << 31) && nnz >= 0, SCAMD_EINVAL, "leiden: bad shape n=%lld nnz=%lld",
-                (long long)n, (long long)nnz);
-  SCAMD_REQUIRE(resolution >= 0.0, SCAMD_EINVAL, "leiden: negative resolution");
-  {
-    const char* e = getenv("SCAMD_LEIDEN_DEBUG");
-    g_leiden_debug = e && (e[0] == '1' || e[0] == '2');
-    g_leiden_debug_sync = e && e[0] == '2';
-  }
-  LeidenCtx cx;
-  cx.s = stream;
-  cx.gamma = resolution;
-  cx.inv_beta = beta > 0.0 ? 1.0 / (beta * WSCALE) : 0.0;  // beta <= 0: the greedy limit (largest gain, no "stay")
-  cx.seed = (unsigned int)(seed ^ (seed >> 32)) * 0x9E3779B1u + 0x632BE5ABu;
-  if (const char* e = getenv("SCAMD_LEIDEN_SMALL")) cx.small_levels = e[0] != '0';
-  if (const char* e = getenv("SCAMD_LEIDEN_POLISH")) cx.polish = e[0] != '0';
-  if (const char* e = getenv("SCAMD_LEIDEN_REUSE")) cx.reuse = e[0] != '0';
-  cx.cap_e = 2 * (size_t)std::max<int64_t>(nnz, 1);
-  cx.cap_p = 2 * ((size_t)n + 1);
-  cx.cap_c = 2 * (size_t)n;
-  cx.cpm = objective == 1;
-  cx.node_weights = node_weights;
-  if (cx.cpm) cx.small_levels = false;  // (ld_small_levels_kernel derives its coarse vertex weights from row sums: strengths)
-  for (int i = 0; i < LD_NSTATS; ++i) g_ld_stats[i] = 0;
-  g_ld_sweep_bytes = 0.0;
-  if (const char* e = getenv("SCAMD_LEIDEN_AGG_WAVE_MAX")) cx.agg_wave_max = std::min(atoi(e), (int)WH_MAX_DEG);
-  if (const char* e = getenv("SCAMD_LEIDEN_AGG_MID_MAX")) cx.agg_mid_max = std::min(atoi(e), (int)AGG_MID_MAX);
-  if (const char* e = getenv("SCAMD_LEIDEN_HUB_TRY_PROBES")) cx.hub_try_probes = std::max(0, atoi(e));
-  if (const char* e = getenv("SCAMD_LEIDEN_AGG_WAVE_WORK")) cx.agg_wave_work = std::max(1, atoi(e));
-  if (const char* e = getenv("SCAMD_LEIDEN_AGG_MID_WORK")) cx.agg_mid_work = std::max(1, atoi(e));
-  if (const char* e = getenv("SCAMD_LEIDEN_AGG_PASS_KEYS"))
-    cx.agg_pass_keys = std::max(16, std::min(atoi(e), (int)AGG_BIG_PASS));
-  Workspace ws(workspace, workspace_bytes);
-  leiden_carve(ws, n, nnz, &cx.b);
-  SCAMD_REQUIRE(workspace && ws.ok, SCAMD_EWORKSPACE, "leiden: workspace %zu < required %zu", workspace_bytes,
-                ws.used());
-  SCAMD_HIP_CHECK(hipFuncSetAttribute(reinterpret_cast<const void*>(ld_move_hub_kernel),
-                                      hipFuncAttributeMaxDynamicSharedMemorySize, (int)HUB_LDS));
-  SCAMD_HIP_CHECK(hipFuncSetAttribute(reinterpret_cast<const void*>(ld_refine_propose_hub_kernel),
-                                      hipFuncAttributeMaxDynamicSharedMemorySize, (int)HUB_LDS));
-  SCAMD_HIP_CHECK(hipFuncSetAttribute(reinterpret_cast<const void*>(ld_agg_merge_kernel),
-                                      hipFuncAttributeMaxDynamicSharedMemorySize, (int)HUB_LDS));
-  SCAMD_HIP_CHECK(hipFuncSetAttribute(reinterpret_cast<const void*>(ld_agg_block_kernel<BHUB_SLOTS, 1024>),
-                                      hipFuncAttributeMaxDynamicSharedMemorySize, (int)HUB_LDS));
-  SCAMD_HIP_CHECK(hipFuncSetAttribute(reinterpret_cast<const void*>(ld_small_levels_kernel),
-                                      hipFuncAttributeMaxDynamicSharedMemorySize, (int)sizeof(SmallLds)));
-  LevelGraph g0;
-  int rc = setup_level0(cx, indptr, indices, weights, n, nnz, &g0);
-  if (rc != SCAMD_OK) return rc;
-  LeidenBuffers& b = cx.b;
-  if (initial_membership) {
-    // (b.counters[PHASE_ERR] is zero: setup_level0 cleared the counters and checked whatever it raised)
-    hipLaunchKernelGGL(ld_copy_membership_kernel, GRID1(n), 0, cx.s, (int)n, initial_membership, b.memb, b.counters + PHASE_ERR);
-    SCAMD_LAUNCH_CHECK();
-    int bad = 0;
-    LD_FETCH(&bad, b.counters + PHASE_ERR, sizeof(int), cx.s);
-    LD_SYNC(cx.s);
-    SCAMD_REQUIRE(bad == 0, SCAMD_EINVAL, "leiden: initial membership ids must lie in [0, n)");
-  } else {
-    hipLaunchKernelGGL(ld_iota_kernel, GRID1(n), 0, cx.s, b.memb, (int)n);
-    SCAMD_LAUNCH_CHECK();
-  }
-  double q_best = 0.0;
-  if (cx.m2 > 0.0) {
-    rc = compute_totals(cx, g0, b.memb);
-    if (rc == SCAMD_OK) rc = quality(cx, g0, b.memb, &q_best);
-    if (rc != SCAMD_OK) return rc;
-    // b.memb is ALWAYS the best partition seen (the input of the next iteration); an iteration writes into b.memb_work and
-    // the two change places when it improved -- no copies (round 5: two 4-byte-per-vertex blits per iteration)
-    int iter_cap = MAX_OUTER_ITERS;
-    if (const char* e = getenv("SCAMD_LEIDEN_ITER_CAP"))
-      if (atoi(e) > 0) iter_cap = atoi(e);
-    g_ld_stats[13] = iter_cap;
-    int max_iter = n_iterations < 0 ? iter_cap : n_iterations;
-    // (test knob: caps the outer loop of an n_iterations < 0 run, so that the polish meets an unfinished partition)
-    if (const char* e = getenv("SCAMD_LEIDEN_MAX_ITERS"))
-      if (n_iterations < 0 && atoi(e) > 0) max_iter = std::min(max_iter, atoi(e));
-    int bad_iters = 0;
-    // true once b.memb has been the INPUT of an iteration whose level-0 local moving found nothing to move: its
-    // first sweep decides for every vertex on the final state, so that is a proof of node optimality
-    bool best_is_clean = false;
-    bool ended_by_cap = true;  // the loop below ran out of iterations (n_iterations < 0: MAX_OUTER_ITERS) instead of converging
-    for (int it = 0; it < max_iter; ++it) {
-      cx.iter = it;
-      g_ld_stats[0] = it + 1;
-      rc = leiden_iteration(cx, g0);
-      if (rc != SCAMD_OK) return rc;
-      if (it == 0) g_ld_stats[7] = cx.n_levels;
-      double q = 0.0;
-      rc = compute_totals(cx, g0, b.memb_work);
-      if (rc == SCAMD_OK) rc = quality(cx, g0, b.memb_work, &q);
-      if (rc != SCAMD_OK) return rc;
-      const bool improved = q > q_best + 1e-12;
-      const bool worse = q < q_best - 1e-12;
-      if (leiden_debug()) fprintf(stderr, "[leiden] iteration %d: Q = %.10f (best before %.10f)\n", it, q, q_best);
-      if (cx.it_quiet && cx.it_small_moves == 0) ++g_ld_stats[17];
-      if (improved) {
-        q_best = q;
-        bad_iters = 0;
-        best_is_clean = false;
-        std::swap(b.memb, b.memb_work);
-        own_hierarchy(cx);
-      } else {
-        if (cx.l0_moves == 0) best_is_clean = true;
-        // synchronous moves and the randomised refinement are not monotone: the best partition seen stays in b.memb
-      }
-      // n_iterations < 0: until an iteration changes nothing (leidenalg: `while diff_inc > 0`).  An iteration that
-      // reproduces the best quality exactly found nothing to move -> done.  One that came out WORSE was unlucky in its
-      // random merges (the next one draws different noise, cx.iter is part of the noise seed): two of those in a row end
-      // the run as well -- without this patience a single unlucky iteration right after the first one froze the
-      // result of ONE iteration (Q 0.8028 instead of 0.812 on the 700-cell fixture).
-      if (n_iterations < 0 && !improved) {
-        ended_by_cap = false;
-        if (!worse || ++bad_iters >= 2) break;
-        ended_by_cap = true;
-      }
-    }
-    // n_iterations < 0 promises a STABLE partition (leidenalg iterates until an iteration changes nothing; such a
-    // partition is node optimal and g-separated).  Ours is the best of a run of non-monotone iterations.  Unless the last
-    // iteration proved it (best_is_clean): strictly monotone single-vertex moves until a sweep over all vertices finds
-    // none (polish_level0), then -- the moved vertices may have made two communities mergeable, or cut one in two -- ONE
-    // ordinary iteration from the polished partition: its level-0 moving finds nothing, its refinement and coarse levels
-    // re-examine everything else.  No gain: stable, done.  A gain: accepted, and the polish runs again.
-    int n_iter_total = g_ld_stats[0];
-    ended_by_cap = ended_by_cap && max_iter == iter_cap;  // (not the test knob's cap: that one is followed up)
-    g_ld_stats[11] = (n_iterations < 0 && ended_by_cap) ? 1 : 0;
-    for (int pr = 0; n_iterations < 0 && cx.polish && pr <= MAX_POLISH_PASSES; ++pr) {
-      if (best_is_clean) {
-        if (pr == 0) g_ld_stats[6] = 1;
-        break;
-      }
-      int ps[4] = {0, 0, 0, 0};
-      rc = polish_level0(cx, g0, ps);
-      if (rc != SCAMD_OK) return rc;
-      g_ld_stats[3] += ps[0];
-      g_ld_stats[4] += ps[1];
-      g_ld_stats[5] += ps[2];
-      g_ld_stats[10] += ps[3];
-      if (ps[2] == 0) break;  // the full sweep found no improving move: node optimal as it stands
-      cx.depth = 0;  // b.memb changed in place: the stored hierarchy is no longer its own, the iteration below runs in full
-      double q = 0.0;
-      rc = compute_totals(cx, g0, b.memb);
-      if (rc == SCAMD_OK) rc = quality(cx, g0, b.memb, &q);
-      if (rc != SCAMD_OK) return rc;
-      if (leiden_debug())
-        fprintf(stderr, "[leiden] polish %d: %d full sweeps, %d rounds, %d moves: Q %.10f -> %.10f\n", pr, ps[0], ps[1], ps[2], q_best, q);
-      SCAMD_REQUIRE(q >= q_best - 1e-12, SCAMD_EINTERNAL, "leiden: the monotone polish lowered the quality (%.12f -> %.12f)", q_best, q);
-      q_best = q;
-      // (the last pass only polishes what the last accepted iteration left.  A run that the iteration cap ended was still
-      // gaining a little with every iteration -- structure-less graphs do that for dozens of iterations: there is no stable
-      // partition to verify, the polished one is node optimal and connected, and that is what is returned)
-      if (pr == MAX_POLISH_PASSES || ended_by_cap) break;
-      cx.iter = n_iter_total++;
-      g_ld_stats[0] = n_iter_total;
-      rc = leiden_iteration(cx, g0);
-      if (rc != SCAMD_OK) return rc;
-      rc = compute_totals(cx, g0, b.memb_work);
-      if (rc == SCAMD_OK) rc = quality(cx, g0, b.memb_work, &q);
-      if (rc != SCAMD_OK) return rc;
-      if (leiden_debug()) fprintf(stderr, "[leiden] iteration after polish %d: Q = %.10f (polished %.10f), level-0 moves %d\n", pr, q, q_best, cx.l0_moves);
-      if (cx.it_quiet && cx.it_small_moves == 0) ++g_ld_stats[17];
-      if (q > q_best + 1e-12) {
-        q_best = q;
-        std::swap(b.memb, b.memb_work);
-        own_hierarchy(cx);
-      } else {
-        break;  // stable: the polished partition (b.memb) stands
-      }
-    }
-  }
-  if (cx.cpm && cx.m2 > 0.0) {
-    // what is reported is the modularity of the partition (the reference stores `part.modularity`), not the CPM quality the
-    // run maximised: strengths back into k0, totals, resolution 1
-    hipLaunchKernelGGL(ld_strength_kernel, GRIDW(n), 0, cx.s, indptr, b.wq0, (int)n, b.k0);
-    SCAMD_LAUNCH_CHECK();
-    cx.cpm = false;
-    cx.gamma = 1.0;
-    rc = compute_totals(cx, g0, b.memb);
-    if (rc == SCAMD_OK) rc = quality(cx, g0, b.memb, &q_best);
-    if (rc != SCAMD_OK) return rc;
-  }
-  int nc = 0;
-  rc = renumber(cx, (int)n, &nc, membership);  // (writes the caller's buffer directly)
-  if (rc != SCAMD_OK) return rc;
-  LD_SYNC(cx.s);
-  if (modularity_host) *modularity_host = q_best;
-  if (n_communities_host) *n_communities_host = nc;
-  return SCAMD_OK;
+  return leiden_run(LeidenCall{indptr, indices, weights, n, nnz, resolution, n_iterations, beta, seed, objective, node_weights,
+                               initial_membership, membership, modularity_host, n_communities_host, workspace, workspace_bytes, stream});
 }
 
 // Test entry: the component split of the polish (split_disconnected) on a GIVEN membership (ids in [0, n)): every
@@ -3876,17 +3928,12 @@ static int leiden_run(const int64_t* indptr, const int32_t* indices, const float
 extern "C" int scamd_leiden_debug_split_f32(const int64_t* indptr, const int32_t* indices, const float* weights, int64_t n,
                                             int64_t nnz, int32_t* membership, int32_t* n_split_host, void* workspace,
                                             size_t workspace_bytes, scamd_stream_t stream) {
-  SCAMD_REQUIRE(indptr && membership && n_split_host && (nnz == 0 || (indices && weights)), SCAMD_EINVAL, "leiden split: null pointer");
-  SCAMD_REQUIRE(n >= 1 && n < ((int64_t)1 << 31) && nnz >= 0, SCAMD_EINVAL, "leiden split: bad shape");
+  SCAMD_REQUIRE(membership && n_split_host, SCAMD_EINVAL, "leiden split: null pointer");
   LeidenCtx cx;
-  cx.s = stream;
   cx.gamma = 1.0;
   cx.seed = 0;
-  Workspace ws(workspace, workspace_bytes);
-  leiden_carve(ws, n, nnz, &cx.b);
-  SCAMD_REQUIRE(workspace && ws.ok, SCAMD_EWORKSPACE, "leiden split: workspace %zu < required %zu", workspace_bytes, ws.used());
   LevelGraph g0;
-  int rc = setup_level0(cx, indptr, indices, weights, n, nnz, &g0);
+  int rc = leiden_open(cx, "leiden split", indptr, indices, weights, n, nnz, workspace, workspace_bytes, stream, &g0);
   if (rc != SCAMD_OK) return rc;
   hipLaunchKernelGGL(ld_copy_i32_kernel, GRID1(n), 0, cx.s, (int)n, (const int*)membership, cx.b.comm);
   SCAMD_LAUNCH_CHECK();
@@ -3905,36 +3952,29 @@ extern "C" int scamd_leiden_debug_split_f32(const int64_t* indptr, const int32_t
 }
 
 extern "C" void scamd_leiden_last_stats(int32_t* out, int n) {
-  g_ld_stats[9] = (int)std::min(2.0e9, g_ld_sweep_bytes / 1.0e6);
+  g_ld_stats[ST_LM_SWEEP_MB] = (int)std::min(2.0e9, g_ld_sweep_bytes / 1.0e6);
   for (int i = 0; i < n && i < LD_NSTATS; ++i) out[i] = g_ld_stats[i];
+}
+
+// key of a statistics slot (LD_STAT_NAMES); NULL: no such slot, or the unused one
+extern "C" const char* scamd_leiden_stat_name(int slot) {
+  for (const LdStatName& e : LD_STAT_NAMES)
+    if (e.slot == slot) return e.key;
+  return nullptr;
 }
 
 extern "C" int scamd_modularity_csr_f32(const int64_t* indptr, const int32_t* indices, const float* weights, int64_t n,
                                         int64_t nnz, const int32_t* membership, double resolution,
                                         double* modularity_host, void* workspace, size_t workspace_bytes,
                                         scamd_stream_t stream) {
-  SCAMD_REQUIRE(indptr && membership && modularity_host && (nnz == 0 || (indices && weights)), SCAMD_EINVAL,
-                "modularity: null pointer");
-  SCAMD_REQUIRE(n >= 1 && n < ((int64_t)1 << 31) && nnz >= 0, SCAMD_EINVAL, "modularity: bad shape");
-  {
-    const char* e = getenv("SCAMD_LEIDEN_DEBUG");
-    g_leiden_debug = e && e[0] == '1';
-  }
+  SCAMD_REQUIRE(membership && modularity_host, SCAMD_EINVAL, "modularity: null pointer");
   LeidenCtx cx;
-  cx.s = stream;
   cx.gamma = resolution;
   cx.seed = 0;
-  Workspace ws(workspace, workspace_bytes);
-  leiden_carve(ws, n, nnz, &cx.b);
-  SCAMD_REQUIRE(workspace && ws.ok, SCAMD_EWORKSPACE, "modularity: workspace %zu < required %zu", workspace_bytes,
-                ws.used());
   LevelGraph g0;
-  int rc = setup_level0(cx, indptr, indices, weights, n, nnz, &g0);
+  const int rc = leiden_open(cx, "modularity", indptr, indices, weights, n, nnz, workspace, workspace_bytes, stream, &g0);
   if (rc != SCAMD_OK) return rc;
   *modularity_host = 0.0;
   if (cx.m2 <= 0.0) return SCAMD_OK;
-  // membership ids must lie in [0, n)
-  rc = compute_totals(cx, g0, membership);
-  if (rc == SCAMD_OK) rc = quality(cx, g0, membership, modularity_host);
-  return rc;
+  return evaluate(cx, g0, membership, modularity_host);  // membership ids must lie in [0, n)
 }

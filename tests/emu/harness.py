@@ -14,7 +14,7 @@ import numpy as np
 HERE = Path(__file__).resolve().parent
 ROOT = HERE.parent.parent
 sys.path.insert(0, str(ROOT))
-from scanpy_amd._lib import SIGNATURES  # noqa: E402
+from scanpy_amd._lib import SIGNATURES, leiden_stat_names  # noqa: E402
 
 
 @lru_cache(maxsize=2)
@@ -87,24 +87,10 @@ def leiden(lib, adj, *, resolution=1.0, n_iterations=-1, beta=0.01, seed=0, init
     q = C.c_double(0)
     nc = C.c_int32(0)
     ws = _ws(lib.scamd_leiden_workspace_bytes(n, adj.nnz))
-    if node_weights is not None:
-        init = None if initial_membership is None else np.ascontiguousarray(initial_membership, dtype=np.int32)
-        nw = np.ascontiguousarray(node_weights, dtype=np.float32)
-        rc = lib.scamd_leiden_csr_nw_f32(_p(indptr), _p(indices), _p(w), n, adj.nnz, float(resolution), int(n_iterations), float(beta),
-                                         int(seed), int(objective), _p(nw), None if init is None else _p(init), _p(memb),
-                                         C.byref(q), C.byref(nc), _p(ws), ws.size, None)
-    elif objective:
-        init = None if initial_membership is None else np.ascontiguousarray(initial_membership, dtype=np.int32)
-        rc = lib.scamd_leiden_csr_ex_f32(_p(indptr), _p(indices), _p(w), n, adj.nnz, float(resolution), int(n_iterations), float(beta),
-                                         int(seed), int(objective), None if init is None else _p(init), _p(memb), C.byref(q),
-                                         C.byref(nc), _p(ws), ws.size, None)
-    elif initial_membership is not None:
-        init = np.ascontiguousarray(initial_membership, dtype=np.int32)
-        rc = lib.scamd_leiden_csr_init_f32(_p(indptr), _p(indices), _p(w), n, adj.nnz, float(resolution), int(n_iterations),
-                                           float(beta), int(seed), _p(init), _p(memb), C.byref(q), C.byref(nc), _p(ws), ws.size, None)
-    else:
-        rc = lib.scamd_leiden_csr_f32(_p(indptr), _p(indices), _p(w), n, adj.nnz, float(resolution), int(n_iterations), float(beta),
-                                      int(seed), _p(memb), C.byref(q), C.byref(nc), _p(ws), ws.size, None)
+    init = None if initial_membership is None else np.ascontiguousarray(initial_membership, dtype=np.int32)
+    nw = None if node_weights is None else np.ascontiguousarray(node_weights, dtype=np.float32)
+    rc = lib.scamd_leiden_csr_nw_f32(_p(indptr), _p(indices), _p(w), n, adj.nnz, float(resolution), int(n_iterations), float(beta),
+                                     int(seed), int(objective), _p(nw), _p(init), _p(memb), C.byref(q), C.byref(nc), _p(ws), ws.size, None)
     _check(lib, rc, "leiden")
     return memb, float(q.value), int(nc.value)
 
@@ -144,11 +130,10 @@ def leiden_split(lib, adj, membership):
 
 
 def leiden_stats(lib) -> dict:
-    out = (C.c_int32 * 12)()
-    lib.scamd_leiden_last_stats(out, 12)
-    keys = ("iterations", "launches", "host_round_trips", "polish_full_sweeps", "polish_rounds", "polish_moves",
-            "polish_skipped_proven", "levels_first_iteration", "lm_sweeps", "lm_sweep_algorithmic_MB", "polish_splits", "ended_by_iteration_cap")
-    return dict(zip(keys, (int(v) for v in out)))
+    keys = leiden_stat_names(lib)
+    out = (C.c_int32 * len(keys))()
+    lib.scamd_leiden_last_stats(out, len(keys))
+    return {k: int(v) for k, v in zip(keys, out) if k is not None}
 
 
 def pca_csr(lib, x, n_comps, *, zero_center=True, seed=0, tol=2e-8):

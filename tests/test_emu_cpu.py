@@ -460,8 +460,8 @@ def test_leiden_hub_rows(emu):
 def test_leiden_long_row_tiers_agree(emu, monkeypatch):
     """the decide step of a row is the same rule in every tier: with 64, 16 and 32 lanes per vertex (SCAMD_LEIDEN_QUAD = 0 /
     1 / 2) the rows of 150 .. 2500 entries are decided by the main launch, the 64-lane overflow pass or the hub pass, and the
-    partition must not depend on which.  Slots 18 / 19 of scamd_leiden_last_stats (vertices taken over by the overflow pass /
-    handed to the hub pass) show that the tiers were reached: with 64 lanes there is no overflow tier."""
+    partition must not depend on which.  `overflow_pass_vertices` / `hub_pass_vertices` of the statistics (vertices taken over by
+    the overflow pass / handed to the hub pass) show that the tiers were reached: with 64 lanes there is no overflow tier."""
     from helpers import long_rows_graph
     from oracle import leiden as ol
 
@@ -472,15 +472,36 @@ def test_leiden_long_row_tiers_agree(emu, monkeypatch):
     for quad in ("0", "1", "2"):
         monkeypatch.setenv("SCAMD_LEIDEN_QUAD", quad)
         memb, q, nc = H.leiden(lib, m, seed=0, n_iterations=2)
-        st = (C.c_int32 * 20)()
-        lib.scamd_leiden_last_stats(st, 20)
-        print(f"QUAD={quad}: Q={q!r} communities={nc} overflow pass={st[18]} hub pass={st[19]}")
-        out[quad] = (memb, q, nc, st[18], st[19])
+        st = H.leiden_stats(lib)
+        print(f"QUAD={quad}: Q={q!r} communities={nc} overflow pass={st['overflow_pass_vertices']} hub pass={st['hub_pass_vertices']}")
+        out[quad] = (memb, q, nc, st["overflow_pass_vertices"], st["hub_pass_vertices"])
         assert abs(q - ol.modularity(m, memb)) < 1e-8
-        assert st[19] > 0
-        assert (st[18] == 0) if quad == "0" else (st[18] > 0)
+        assert st["hub_pass_vertices"] > 0
+        assert (st["overflow_pass_vertices"] == 0) if quad == "0" else (st["overflow_pass_vertices"] > 0)
     for quad in ("1", "2"):
         assert out[quad][1] == out["0"][1] and out[quad][2] == out["0"][2] and np.array_equal(out[quad][0], out["0"][0])
+
+
+def test_leiden_entry_points_are_one_run(emu, pbmc68k):
+    """scamd_leiden_csr_f32 / _init_f32 / _ex_f32 / _nw_f32 on the 700-cell fixture graph (helpers.check_leiden_entry_points)"""
+    from helpers import check_leiden_entry_points
+
+    H, lib = emu
+    adj = pbmc68k["connectivities"].astype(np.float32).tocsr()
+    adj.sort_indices()
+    n = adj.shape[0]
+    graph = (adj.indptr.astype(np.int64), adj.indices.astype(np.int32), adj.data.astype(np.float32), n, adj.nnz)
+    ws = np.full(int(lib.scamd_leiden_workspace_bytes(n, adj.nnz)), 0xAB, dtype=np.uint8)
+    check_leiden_entry_points(lib, lambda a: C.c_void_p(a.ctypes.data), graph, lambda m: np.empty(m, dtype=np.int32), lambda a: a,
+                              np.arange(n, dtype=np.int32), np.ones(n, dtype=np.float32), ws, None)
+
+
+def test_leiden_stat_keys(emu):
+    """the statistics dict is built from the library's own slot -> key table: the keys are the documented ones"""
+    from helpers import check_leiden_stat_keys
+
+    H, lib = emu
+    check_leiden_stat_keys(lib, H.leiden_stats(lib))
 
 
 def test_pca_chain(emu):

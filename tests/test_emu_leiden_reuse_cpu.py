@@ -4,9 +4,8 @@ graph and the vertex map of the hierarchy that produced the best partition inste
 `SCAMD_LEIDEN_REUSE=0` is the behaviour without it.  `SCAMD_LEIDEN_SMALL=0` throughout: graphs of this size would otherwise
 leave the separate-kernel levels after one level.
 
-Slots 16 / 17 of `scamd_leiden_last_stats`: levels reused / iterations that ran on the stored hierarchy to its end without a
-move."""
-import ctypes as C
+`levels_reused` / `quiet_reuse_iterations` of the statistics: levels reused / iterations that ran on the stored hierarchy to
+its end without a move."""
 import sys
 from pathlib import Path
 
@@ -41,20 +40,13 @@ def _blob_graph(n, seed, spread):
     return conn
 
 
-def _stats(lib):
-    out = (C.c_int32 * 18)()
-    lib.scamd_leiden_last_stats(out, 18)
-    return {"iterations": int(out[0]), "launches": int(out[1]), "polish_moves": int(out[5]), "levels_reused": int(out[16]),
-            "quiet_reuse_iterations": int(out[17])}
-
-
 def _with_and_without(H, lib, monkeypatch, conn, **kw):
     monkeypatch.delenv("SCAMD_LEIDEN_REUSE", raising=False)
     new = H.leiden(lib, conn, **kw)
-    st_new = _stats(lib)
+    st_new = H.leiden_stats(lib)
     monkeypatch.setenv("SCAMD_LEIDEN_REUSE", "0")
     old = H.leiden(lib, conn, **kw)
-    st_old = _stats(lib)
+    st_old = H.leiden_stats(lib)
     monkeypatch.delenv("SCAMD_LEIDEN_REUSE")
     print(f"reuse: {st_new}  Q {new[1]!r} nc {new[2]}\nhook : {st_old}  Q {old[1]!r} nc {old[2]}")
     return new, st_new, old, st_old
@@ -96,10 +88,10 @@ def test_overlapping_graph_keeps_the_guarantees(emu, monkeypatch):
     monkeypatch.delenv("SCAMD_LEIDEN_REUSE", raising=False)
     conn = _blob_graph(6000, 0, 0.8)
     memb, q, nc = H.leiden(lib, conn, seed=0)
-    st = _stats(lib)
+    st = H.leiden_stats(lib)
     memb2, q2, nc2 = H.leiden(lib, conn, seed=0)
     print(f"overlapping: Q {q!r}, {nc} communities, {st}")
-    assert np.array_equal(memb, memb2) and q == q2 and nc == nc2 and _stats(lib) == st
+    assert np.array_equal(memb, memb2) and q == q2 and nc == nc2 and H.leiden_stats(lib) == st
     assert abs(q - ol.modularity(conn, memb)) < 1e-8 and nc == int(memb.max()) + 1
     assert lg.improving_moves(conn, memb)["count"] == 0 and lg.mergeable_pairs(conn, memb)["count"] == 0
     assert _connected_communities(conn, memb) == nc
@@ -124,7 +116,7 @@ def test_iteration_after_the_polish_reuses_nothing(emu, monkeypatch):
     idx, dist = oknn.knn_exact_f64(x, np.arange(n), 15)
     conn, _, _ = oconn.fuzzy_simplicial_set(idx, dist, n, 15)
     memb, q, nc = H.leiden(lib, conn, seed=0)
-    st = _stats(lib)
+    st = H.leiden_stats(lib)
     print(f"polish path: Q {q!r}, {nc} communities, {st}")
     assert st["polish_moves"] > 0 and st["iterations"] >= 2, st  # (the polish moved vertices, an iteration followed it)
     assert st["levels_reused"] == 0 and st["quiet_reuse_iterations"] == 0, st

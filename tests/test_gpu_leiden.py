@@ -246,8 +246,8 @@ def test_leiden_quarter_wave_kernels_agree(K, monkeypatch):
 def test_leiden_long_row_tiers_agree(K, monkeypatch):
     """the decide step of a row is the same rule in every tier: with 64, 16 and 32 lanes per vertex (SCAMD_LEIDEN_QUAD = 0 /
     1 / 2) the rows of 150 .. 2500 entries are decided by the main launch, the 64-lane overflow pass or the hub pass, and the
-    partition must not depend on which.  Slots 18 / 19 of scamd_leiden_last_stats (vertices taken over by the overflow pass /
-    handed to the hub pass) show that the tiers were reached: with 64 lanes there is no overflow tier."""
+    partition must not depend on which.  `overflow_pass_vertices` / `hub_pass_vertices` of the statistics (vertices taken over by
+    the overflow pass / handed to the hub pass) show that the tiers were reached: with 64 lanes there is no overflow tier."""
     from helpers import long_rows_graph
 
     m = long_rows_graph()
@@ -265,3 +265,28 @@ def test_leiden_long_row_tiers_agree(K, monkeypatch):
         assert (st["overflow_pass_vertices"] == 0) if quad == "0" else (st["overflow_pass_vertices"] > 0)
     for quad in ("1", "2"):
         assert out[quad][1] == out["0"][1] and out[quad][2] == out["0"][2] and np.array_equal(out[quad][0], out["0"][0])
+
+
+def test_leiden_entry_points_are_one_run(K, pbmc68k):
+    """scamd_leiden_csr_f32 / _init_f32 / _ex_f32 / _nw_f32 on the 700-cell fixture graph (helpers.check_leiden_entry_points)"""
+    import torch
+    from helpers import check_leiden_entry_points
+
+    from scanpy_amd import _lib
+    from scanpy_amd._device import ptr, stream_ptr
+
+    lib = _lib.load()
+    ip, ix, w, n = _graph_dev(pbmc68k["connectivities"].astype(np.float32))
+    ws = torch.full((int(lib.scamd_leiden_workspace_bytes(n, w.numel())),), 0xAB, dtype=torch.uint8, device="cuda")
+    check_leiden_entry_points(lib, ptr, (ip, ix, w, n, w.numel()), lambda m: torch.empty(m, dtype=torch.int32, device="cuda"),
+                              lambda t: t.cpu().numpy(), torch.arange(n, dtype=torch.int32, device="cuda"),
+                              torch.ones(n, dtype=torch.float32, device="cuda"), ws, stream_ptr())
+
+
+def test_leiden_stat_keys(K):
+    """the statistics dict is built from the library's own slot -> key table: the keys are the documented ones"""
+    from helpers import check_leiden_stat_keys
+
+    from scanpy_amd import _lib
+
+    check_leiden_stat_keys(_lib.load(), K.leiden_last_stats())

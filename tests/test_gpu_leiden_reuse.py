@@ -6,11 +6,10 @@ Q, community count and iteration count are those of a run that refines and aggre
 (`SCAMD_LEIDEN_REUSE=0`).  weak: a run of many iterations, most of which move vertices at level 0 (nothing to reuse) -- the
 paper's guarantees hold for what it returns.
 
-Slots 16 / 17 of `scamd_leiden_last_stats`: levels reused / iterations that ran on the stored hierarchy to its end without a
-move."""
+`levels_reused` / `quiet_reuse_iterations` of the statistics: levels reused / iterations that ran on the stored hierarchy to
+its end without a move."""
 from __future__ import annotations
 
-import ctypes as C
 import sys
 from pathlib import Path
 
@@ -37,15 +36,6 @@ def _graph(structure):
     return res.conn_indptr, res.conn_indices, res.conn_data
 
 
-def _stats18():
-    from scanpy_amd import _lib
-
-    out = (C.c_int32 * 18)()
-    _lib.load().scamd_leiden_last_stats(out, 18)
-    return {"iterations": int(out[0]), "launches": int(out[1]), "host_round_trips": int(out[2]),
-            "levels_first_iteration": int(out[7]), "levels_reused": int(out[16]), "quiet_reuse_iterations": int(out[17])}
-
-
 def _run(ip, ix, w, seed):
     import torch
 
@@ -53,7 +43,7 @@ def _run(ip, ix, w, seed):
 
     labels, q, nc = K.leiden(ip, ix, w, N, seed=seed)
     torch.cuda.synchronize()
-    return labels.cpu().numpy(), q, nc, _stats18()
+    return labels.cpu().numpy(), q, nc, K.leiden_last_stats()
 
 
 @pytest.fixture(scope="module")
