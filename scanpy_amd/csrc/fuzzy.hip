@@ -719,11 +719,11 @@ extern "C" int scamd_fuzzy_simplicial_set_f32(const int32_t* knn_idx, const floa
 extern "C" int scamd_fuzzy_weights_f32(const int32_t* knn_idx, const float* knn_dist, int64_t n_local, int k,
                                        int64_t row_begin, int64_t n_total, const double* sum_all_dev, float* w,
                                        float* out_sigma, float* out_rho, int32_t* out_count, scamd_stream_t stream) {
-  SCAMD_REQUIRE(knn_idx && knn_dist && sum_all_dev && w && out_count, SCAMD_EINVAL, "fuzzy_weights: null pointer");
   SCAMD_REQUIRE(n_local >= 0 && k >= 2 && k <= 1024 && row_begin >= 0 && row_begin + n_local <= n_total &&
                     n_total < ((int64_t)1 << 31),
                 SCAMD_EINVAL, "fuzzy_weights: bad shape");
-  if (n_local == 0) return SCAMD_OK;
+  if (n_local == 0) return SCAMD_OK;  // a rank that owns no rows: nothing to do (empty tensors may be null)
+  SCAMD_REQUIRE(knn_idx && knn_dist && sum_all_dev && w && out_count, SCAMD_EINVAL, "fuzzy_weights: null pointer");
   scamd::launch_sigma(knn_idx, knn_dist, n_local, k, sum_all_dev, out_sigma, out_rho, w, out_count, row_begin, n_total,
                       stream);
   SCAMD_LAUNCH_CHECK();

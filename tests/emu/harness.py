@@ -190,3 +190,211 @@ def modularity(lib, adj, membership, resolution=1.0):
     rc = lib.scamd_modularity_csr_f32(_p(indptr), _p(indices), _p(w), n, adj.nnz, _p(memb), float(resolution), C.byref(q), _p(ws), ws.size, None)
     _check(lib, rc, "modularity")
     return float(q.value)
+
+
+# ---------------------------------------------------------------------------------------------------------------------
+# The connectivity kernels (csrc/fuzzy.hip) and the sparse half of PCA (csrc/pca.hip) through the raw C ABI: numpy in, numpy
+# out, the return code handed back instead of raised (the argument checks are part of what is tested), outputs prefilled so
+# that an element nobody wrote shows.  `Abi` does not care where the buffers live: `HostMem` (below) for the emulated
+# library, tests/graph_kernel_cases.py:DeviceMem for the product library on a GPU -- one set of callers for both suites.
+# ---------------------------------------------------------------------------------------------------------------------
+class HostMem:
+    stream = None
+
+    def put(self, a, dtype):
+        return np.array(a, dtype=dtype, order="C", copy=True)
+
+    def full(self, shape, dtype, fill):
+        return np.full(shape, fill, dtype=dtype)
+
+    def ptr(self, a):
+        # an empty buffer travels as NULL, as an empty torch tensor does on the product's side
+        return C.c_void_p(a.ctypes.data) if a is not None and a.size else C.c_void_p(0)
+
+    def get(self, a):
+        return a
+
+    def sync(self):
+        pass
+
+
+class Abi:
+    def __init__(self, lib, mem):
+        self.lib, self.mem = lib, mem
+
+    def _ws(self, nbytes, short=0):
+        # exact size (less `short` bytes), filled with 0xAB: an entry point initialises what it reads
+        ws = self.mem.full(max(int(nbytes) - short, 1), np.uint8, 0xAB)
+        return ws, max(int(nbytes) - short, 0)
+
+    def connectivity(self, method, idx, dist, *, cap=None, ws_short=0):
+        """method: 'umap' | 'gauss' | 'jaccard' -> (rc, indptr, indices, data, sigma, rho); sigma / rho None but for umap"""
+        m, lib = self.mem, self.lib
+        n, k = idx.shape
+        cap = 2 * n * (k - 1) if cap is None else cap
+        d_idx, d_dist = m.put(idx, np.int32), m.put(dist, np.float32)
+        indptr = m.full(n + 1, np.int64, -1)
+        indices = m.full(max(cap, 1), np.int32, -1)
+        data = m.full(max(cap, 1), np.float32, np.nan)
+        sigma, rho = m.full(n, np.float32, np.nan), m.full(n, np.float32, np.nan)
+        ws, wsz = self._ws(lib.scamd_fuzzy_workspace_bytes(n, k), ws_short)
+        nnz = C.c_int64(-1)
+        p = m.ptr
+        if method == "umap":
+            rc = lib.scamd_fuzzy_simplicial_set_f32(p(d_idx), p(d_dist), n, k, p(indptr), p(indices), p(data), cap, p(sigma), p(rho),
+                                                    C.byref(nnz), p(ws), wsz, m.stream)
+        elif method == "gauss":
+            rc = lib.scamd_gauss_connectivities_f32(p(d_idx), p(d_dist), n, k, p(indptr), p(indices), p(data), cap, C.byref(nnz), p(ws), wsz, m.stream)
+        else:
+            rc = lib.scamd_jaccard_connectivities_f32(p(d_idx), n, k, p(indptr), p(indices), p(data), cap, C.byref(nnz), p(ws), wsz, m.stream)
+        m.sync()
+        if rc != 0:
+            return rc, None, None, None, None, None
+        z = int(nnz.value)
+        um = method == "umap"
+        return rc, m.get(indptr), m.get(indices)[:z].copy(), m.get(data)[:z].copy(), m.get(sigma) if um else None, m.get(rho) if um else None
+
+    def fuzzy_weights(self, idx, dist, row_begin, n_total, sum_all):
+        """-> (rc, w [n_local, k], sigma, rho, count)"""
+        m = self.mem
+        n, k = idx.shape
+        d_idx, d_dist, d_sum = m.put(idx, np.int32), m.put(dist, np.float32), m.put([sum_all], np.float64)
+        w = m.full((n, k), np.float32, np.nan)
+        sigma, rho, cnt = m.full(n, np.float32, np.nan), m.full(n, np.float32, np.nan), m.full(max(n, 1), np.int32, -1)
+        p = m.ptr
+        rc = self.lib.scamd_fuzzy_weights_f32(p(d_idx), p(d_dist), n, k, int(row_begin), int(n_total), p(d_sum), p(w), p(sigma), p(rho),
+                                              p(cnt), m.stream)
+        m.sync()
+        return rc, m.get(w), m.get(sigma), m.get(rho), m.get(cnt)[:n]
+
+    def fuzzy_merge_rows(self, idx, w, in_indptr, in_src, in_w):
+        """-> (rc, indptr [n_local + 1], indices, data)"""
+        m, lib = self.mem, self.lib
+        n, k = idx.shape
+        cap = n * (k - 1) + int(len(in_src))
+        bufs = [m.put(idx, np.int32), m.put(w, np.float32), m.put(in_indptr, np.int64), m.put(in_src, np.int32), m.put(in_w, np.float32)]
+        indptr = m.full(n + 1, np.int64, -1)
+        indices, data = m.full(max(cap, 1), np.int32, -1), m.full(max(cap, 1), np.float32, np.nan)
+        ws, wsz = self._ws(lib.scamd_fuzzy_merge_workspace_bytes(n, cap))
+        nnz = C.c_int64(-1)
+        p = m.ptr
+        rc = lib.scamd_fuzzy_merge_rows_f32(*(p(b) for b in bufs[:2]), n, k, *(p(b) for b in bufs[2:]), p(indptr), p(indices), p(data), cap,
+                                            C.byref(nnz), p(ws), wsz, m.stream)
+        m.sync()
+        z = max(int(nnz.value), 0)
+        return rc, m.get(indptr), m.get(indices)[:z].copy(), m.get(data)[:z].copy()
+
+    def _csr(self, x):
+        m = self.mem
+        return m.put(x.indptr, np.int64), m.put(x.indices, np.int32), m.put(x.data, np.float32)
+
+    def spmm(self, x, b, shift=None, *, l=None):
+        """x: scipy CSR with sorted unique columns -> (rc, y [n, l] float32, prefilled with NaN)"""
+        m = self.mem
+        n, g = x.shape
+        l = b.shape[1] if l is None else l
+        ip, ix, dv = self._csr(x)
+        d_b = m.put(b, np.float32)
+        d_s = None if shift is None else m.put(shift, np.float32)
+        y = m.full((n, max(l, 1)), np.float32, np.nan)
+        p = m.ptr
+        rc = self.lib.scamd_spmm_csr_f32(p(ip), p(ix), p(dv), n, g, p(d_b), l, p(d_s) if d_s is not None else C.c_void_p(0), p(y), m.stream)
+        m.sync()
+        return rc, m.get(y)
+
+    def spmm_f64acc(self, x, b, scale=None, colsum=None, *, l=None):
+        """-> (rc, w [n_rows, l] float64, prefilled with NaN)"""
+        m, lib = self.mem, self.lib
+        n = x.shape[0]
+        l = b.shape[1] if l is None else l
+        ip, ix, dv = self._csr(x)
+        d_b = m.put(b, np.float32)
+        d_sc = None if scale is None else m.put(scale, np.float64)
+        d_cs = None if colsum is None else m.put(colsum, np.float64)
+        w = m.full((n, l), np.float64, np.nan)
+        ws, wsz = self._ws(lib.scamd_spmm_f64acc_workspace_bytes(n, x.nnz, l))
+        p = m.ptr
+        null = C.c_void_p(0)
+        rc = lib.scamd_spmm_csr_f32_f64acc(p(ip), p(ix), p(dv), n, x.nnz, p(d_b), l, p(d_sc) if d_sc is not None else null,
+                                           p(d_cs) if d_cs is not None else null, p(w), p(ws), wsz, m.stream)
+        m.sync()
+        return rc, m.get(w)
+
+    def colsum(self, y):
+        m, lib = self.mem, self.lib
+        n, l = y.shape
+        d_y = m.put(y, np.float32)
+        out = m.full(l, np.float64, np.nan)
+        ws, wsz = self._ws(lib.scamd_colsum_workspace_bytes(l))
+        rc = lib.scamd_colsum_f32_f64(m.ptr(d_y), n, l, m.ptr(out), m.ptr(ws), wsz, m.stream)
+        m.sync()
+        return rc, m.get(out)
+
+    def csr_transpose(self, x, *, g=None):
+        """-> (rc, t_indptr [g + 1], t_indices, t_data)"""
+        m, lib = self.mem, self.lib
+        n = x.shape[0]
+        g = x.shape[1] if g is None else g
+        ip, ix, dv = self._csr(x)
+        t_ip = m.full(g + 1, np.int64, -1)
+        t_ix, t_dv = m.full(max(x.nnz, 1), np.int32, -1), m.full(max(x.nnz, 1), np.float32, np.nan)
+        ws, wsz = self._ws(lib.scamd_csr_transpose_workspace_bytes(n, g, x.nnz))
+        p = m.ptr
+        rc = lib.scamd_csr_transpose_f32(p(ip), p(ix), p(dv), n, g, x.nnz, p(t_ip), p(t_ix), p(t_dv), p(ws), wsz, m.stream)
+        m.sync()
+        return rc, m.get(t_ip), m.get(t_ix)[: x.nnz], m.get(t_dv)[: x.nnz]
+
+    def csr_row_stats(self, x):
+        """-> (rc, row sums, row sums of squares), float64"""
+        m = self.mem
+        n = x.shape[0]
+        ip, _, dv = self._csr(x)
+        s, q = m.full(n, np.float64, np.nan), m.full(n, np.float64, np.nan)
+        rc = self.lib.scamd_csr_row_stats_f32(m.ptr(ip), m.ptr(dv), n, m.ptr(s), m.ptr(q), m.stream)
+        m.sync()
+        return rc, m.get(s), m.get(q)
+
+
+def abi(lib) -> Abi:
+    return Abi(lib, HostMem())
+
+
+def _ok(lib, what, out):
+    _check(lib, out[0], what)
+    return out[1:] if len(out) > 2 else out[1]
+
+
+def gauss_connectivities(lib, idx, dist):
+    return _ok(lib, "gauss", abi(lib).connectivity("gauss", idx, dist))[:3]
+
+
+def jaccard_connectivities(lib, idx):
+    return _ok(lib, "jaccard", abi(lib).connectivity("jaccard", idx, np.zeros(idx.shape, np.float32)))[:3]
+
+
+def fuzzy_weights(lib, idx, dist, row_begin, n_total, sum_all):
+    return _ok(lib, "fuzzy_weights", abi(lib).fuzzy_weights(idx, dist, row_begin, n_total, sum_all))
+
+
+def fuzzy_merge_rows(lib, idx, w, in_indptr, in_src, in_w):
+    return _ok(lib, "fuzzy_merge_rows", abi(lib).fuzzy_merge_rows(idx, w, in_indptr, in_src, in_w))
+
+
+def spmm(lib, x, b, shift=None):
+    return _ok(lib, "spmm", abi(lib).spmm(x, b, shift))
+
+
+def spmm_f64acc(lib, x, b, scale=None, colsum=None):
+    return _ok(lib, "spmm_f64acc", abi(lib).spmm_f64acc(x, b, scale, colsum))
+
+
+def colsum(lib, y):
+    return _ok(lib, "colsum", abi(lib).colsum(y))
+
+
+def csr_transpose(lib, x):
+    return _ok(lib, "csr_transpose", abi(lib).csr_transpose(x))
+
+
+def csr_row_stats(lib, x):
+    return _ok(lib, "csr_row_stats", abi(lib).csr_row_stats(x))
