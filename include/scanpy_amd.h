@@ -422,6 +422,48 @@ int scamd_pp_scale_dense_f32(const int64_t* indptr, const int32_t* indices, cons
                              const uint8_t* row_mask, void* out, int out_is_f64, scamd_stream_t stream);
 
 /* ------------------------------------------------------------------------------------------
+ * Marker genes: the device half of tl.rank_genes_groups (reference: `_RankGenes` in
+ * src/scanpy/tools/_rank_genes_groups.py -- `_aggregate_group_stats`, `_ranks`, `_tiecorrect`, `wilcoxon`; csrc/rank_genes.hip,
+ * DESIGN.md 3.8).  Input: the CSC copy of the cells x genes matrix as scamd_csr_transpose_f32 writes it (t_indptr int64[g + 1],
+ * t_indices int32 = row ids ascending within a column, t_data f32) and codes int32[n]: the group of every cell,
+ * 0 <= code < n_groups, or -1 for a cell that does not take part.  n_groups (the remainder group of reference='rest'
+ * included) <= SCAMD_RANK_GENES_MAX_GROUPS, SCAMD_EUNSUPPORTED beyond.  A stored 0.0 / -0.0 counts as a zero everywhere
+ * (the reference calls eliminate_zeros); values are assumed finite.  One gene = one workgroup; every accumulation is an
+ * integer one, so all outputs are bitwise reproducible.  n = 0, g = 0 and empty columns are legal.  Outputs [n_groups x g]
+ * are group-major: out[k * g + j].
+ *
+ * scamd_rank_genes_group_stats_f32: sum / sumsq (float64) and nnz (stored non-zeros) per (group, gene).  transform 0: x as
+ *   stored; 1: expm1(x * tscale) as a float32 value, correctly rounded (the float32 product, expm1 evaluated in float64,
+ *   rounded once).  Sums are 64-bit fixed point with a scale PER GENE:
+ *   with L_j the column's stored entries and absmax_j its max |value| after the transform,
+ *   sb = floor(62 - log2(L_j * absmax_j)) fractional bits for the sum and floor(62 - log2(L_j * absmax_j^2)) for the squares;
+ *   every value is rounded once.  Hence |sum - exact| <= L_j * 2^-sb / 2 <= L_j^2 * absmax_j * 2^-62 (squares: absmax_j^2)
+ *   before the one rounding of the result to float64.  The workspace is not used (NULL is accepted).
+ * scamd_rank_genes_wilcoxon_f32: twice the rank sums.  group_sizes int64[n_groups] (device): cells per code.
+ *   reference = -1 ('rest'): ranks are over all participating cells (average ranks, the implicit zeros one tie block);
+ *     ranksum2[k, j] = 2 * sum of the ranks of group k; tie_term (NULL or [g]) = sum over the blocks of equal values of
+ *     t^3 - t, the zero block included.
+ *   reference = r: group k != r is ranked inside k u r: ranksum2[k, j] = n_k (n_k + 1) + 2 U with
+ *     2 U = sum_{a in k} (2 #{x in r: x < a} + #{x in r: x = a}); tie_term (NULL or [n_groups x g]) = sum over the values v
+ *     of k u r of (t_k(v) + t_r(v))^3 - (t_k(v) + t_r(v)).  Row r of both outputs is written as 0.
+ *   The tie term is summed in integers and converted once: exact below 2^53.  n <= 2^21 (a block of all cells cubed stays
+ *   below 2^63), SCAMD_EUNSUPPORTED beyond.
+ * scamd_rank_genes_chunk_entries: stored entries of a column that one LDS chunk holds for that group count (0: unsupported
+ *   count); a longer column is sorted chunk by chunk into the workspace and costs O(L * chunks * log chunk) searches.
+ * ---------------------------------------------------------------------------------------- */
+#define SCAMD_RANK_GENES_MAX_GROUPS 2000
+size_t scamd_rank_genes_workspace_bytes(int64_t n, int64_t g, int64_t nnz, int n_groups);
+int scamd_rank_genes_chunk_entries(int n_groups);
+int scamd_rank_genes_group_stats_f32(const int64_t* t_indptr, const int32_t* t_indices, const float* t_data, int64_t n,
+                                     int64_t g, const int32_t* codes, int n_groups, int transform, double tscale,
+                                     double* sum, double* sumsq, int64_t* nnz, void* workspace, size_t workspace_bytes,
+                                     scamd_stream_t stream);
+int scamd_rank_genes_wilcoxon_f32(const int64_t* t_indptr, const int32_t* t_indices, const float* t_data, int64_t n,
+                                  int64_t g, const int32_t* codes, int n_groups, const int64_t* group_sizes,
+                                  int reference /* -1 = rest */, int64_t* ranksum2, double* tie_term /* may be NULL */,
+                                  void* workspace, size_t workspace_bytes, scamd_stream_t stream);
+
+/* ------------------------------------------------------------------------------------------
  * UMAP layout: the SGD of umap-learn's optimize_layout_euclidean, which
  * simplicial_set_embedding runs for sc.tl.umap (src/scanpy/tools/_umap.py:196-216), in a synchronous, race-free
  * gather formulation (csrc/umap.hip).  Input: CSR of the pruned symmetric fuzzy graph (indptr [n+1], indices [nnz]),

@@ -613,6 +613,41 @@ def pp_scale_dense(indptr, indices, data, n: int, g: int, mean: torch.Tensor, st
 
 
 # ---- UMAP layout (csrc/umap.hip) -----------------------------------------------------------------------------------
+def rank_genes_group_stats(t_indptr, t_indices, t_data, n: int, g: int, codes: torch.Tensor, n_groups: int, *,
+                           expm1_scale: float | None = None):
+    """-> (sum float64, sumsq float64, nnz int64), each [n_groups, g], of the cells with code k in gene j; expm1_scale = s:
+    of expm1(x * s).  Input: the CSC copy (`csr_transpose`) and codes int32[n] (-1: the cell takes no part)."""
+    dev = require_gpu()
+    lib = _lib.load()
+    assert codes.dtype == torch.int32 and codes.numel() == n
+    s = _empty((n_groups, g), dtype=torch.float64, device=dev)
+    sq = _empty((n_groups, g), dtype=torch.float64, device=dev)
+    nz = _empty((n_groups, g), dtype=torch.int64, device=dev)
+    rc = lib.scamd_rank_genes_group_stats_f32(ptr(t_indptr), ptr(t_indices), ptr(t_data), n, g, ptr(codes), n_groups,
+                                              0 if expm1_scale is None else 1, 1.0 if expm1_scale is None else float(expm1_scale),
+                                              ptr(s), ptr(sq), ptr(nz), None, 0, stream_ptr())
+    _check(rc, "scamd_rank_genes_group_stats_f32")
+    return s, sq, nz
+
+
+def rank_genes_wilcoxon(t_indptr, t_indices, t_data, n: int, g: int, codes: torch.Tensor, n_groups: int,
+                        group_sizes: torch.Tensor, reference: int, *, tie_term: bool):
+    """-> (ranksum2 int64 [n_groups, g], tie term float64 ([g] for reference = -1, else [n_groups, g]) or None)."""
+    dev = require_gpu()
+    lib = _lib.load()
+    assert codes.dtype == torch.int32 and codes.numel() == n
+    assert group_sizes.dtype == torch.int64 and group_sizes.numel() == n_groups
+    rs = _empty((n_groups, g), dtype=torch.int64, device=dev)
+    tie = None
+    if tie_term:
+        tie = _empty(g if reference < 0 else (n_groups, g), dtype=torch.float64, device=dev)
+    ws, wsz = _ws(lib.scamd_rank_genes_workspace_bytes(n, g, t_data.numel(), n_groups), dev)
+    rc = lib.scamd_rank_genes_wilcoxon_f32(ptr(t_indptr), ptr(t_indices), ptr(t_data), n, g, ptr(codes), n_groups,
+                                           ptr(group_sizes), int(reference), ptr(rs), ptr(tie), ptr(ws), wsz, stream_ptr())
+    _check(rc, "scamd_rank_genes_wilcoxon_f32")
+    return rs, tie
+
+
 def umap_optimize_(indptr, indices, epochs_per_sample, n: int, y: torch.Tensor, *, n_epochs: int, a: float, b: float,
                    gamma: float = 1.0, initial_alpha: float = 1.0, negative_sample_rate: float = 5.0, seed: int = 0) -> None:
     """y [n, dim] float32 (device, contiguous): initial embedding in, optimised embedding out."""
