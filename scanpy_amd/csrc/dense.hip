@@ -14,7 +14,12 @@
 //   * the 128 x 128 Rayleigh-Ritz eigenproblem by one-sided (Hestenes) Jacobi in ONE workgroup, matrix resident in LDS
 //     (133 KB of the 160): 64 disjoint column pairs per step, 16 lanes per pair, round-robin ordering;
 //   * Chebyshev-filtered subspace iteration (Zhou & Saad) around them: the filter steps are the GEMM with the
-//     three-term recurrence in its epilogue.
+//     three-term recurrence in its epilogue.  The steps (CholeskyQR2, Rayleigh-Ritz, degree rule, filter) are written once over
+//     an operator in subspace.h; this file holds the two operators and their drivers.
+// Contents, in order: the float64 kernels (GEMM, Cholesky factor, panel x small, Jacobi, residuals, model finalisation);
+// `DenseOp` + `dense_topk` (scamd_eigh_topk_f64, scamd_dense_debug_f64); the batched, deflated solve and the dense half of the
+// Gram-route PCA (scamd_pca_solve_gram_f64, scamd_pca_csr_f32); the sp_* kernels, `SpectralOp` and the spectral
+// initialisation of the UMAP layout (scamd_spectral_embedding_f32).
 // Algorithmic work at g = 2000, b = 128: 2 g^2 b = 1.0e9 flop per operator application (~13 us at the 78.6 TFLOP/s
 // float64 matrix peak), ~11-26 applications; everything else is O(g b^2) or O(b^3).
 #include "common.h"
@@ -535,22 +540,27 @@ __global__ __launch_bounds__(256) void mean_shift_kernel(const double* __restric
 }
 
 // ---------------------------------------------------------------------------------------------------------------------
-// host orchestration
+// host orchestration: the steps of the subspace iteration (subspace.h) over the dense operator
 // ---------------------------------------------------------------------------------------------------------------------
+}  // namespace scamd
+#include "subspace.h"
+namespace scamd {
+
 struct DenseBuffers {
   double* z[7];  // g x b panels
-  double* gm; double* s; double* t; double* y; double* theta; double* resid; int* flags;
+  SubspaceScratch w;
+  double* resid;
 };
 
 static void dense_carve(Workspace& ws, int64_t g, int b, DenseBuffers* d) {
   for (int i = 0; i < 7; ++i) d->z[i] = ws.take<double>((size_t)g * b);
-  d->gm = ws.take<double>((size_t)b * b);
-  d->s = ws.take<double>((size_t)b * b);
-  d->t = ws.take<double>((size_t)b * b);
-  d->y = ws.take<double>((size_t)b * b);
-  d->theta = ws.take<double>((size_t)b + 8);
+  d->w.gm = ws.take<double>((size_t)b * b);
+  d->w.smat = ws.take<double>((size_t)b * b);
+  d->w.tmat = ws.take<double>((size_t)b * b);
+  d->w.ymat = ws.take<double>((size_t)b * b);
+  d->w.theta = ws.take<double>((size_t)b + 8);
   d->resid = ws.take<double>(8);
-  d->flags = ws.take<int>(8);
+  d->w.flags = ws.take<int>(8);
 }
 
 static int dense_block_size(int64_t g, int k) {
@@ -563,149 +573,94 @@ static int dense_block_size(int64_t g, int k) {
   return (int)std::min<int64_t>(b, g);
 }
 
-struct DenseCtx {
+// what a dense solve reports (info_host of the three entry points); a batched solve sums and maximises over its batches
+struct DenseStats {
+  int n_outer = 0, n_gemm = 0, block_size = 0, n_chol_retry = 0;
+  double residual = 0.0;
+};
+// info_host[0..3] = the counters, [4..5] = the residual (float64), [6] = scale_bits and [7] = 0 where the entry has one (>= 0)
+static void pack_dense_info(int32_t* info_host, const DenseStats& st, int scale_bits) {
+  if (!info_host) return;
+  info_host[0] = st.n_outer;
+  info_host[1] = st.n_gemm;
+  info_host[2] = st.block_size;
+  info_host[3] = st.n_chol_retry;
+  memcpy(info_host + 4, &st.residual, sizeof(double));
+  if (scale_bits >= 0) {
+    info_host[6] = scale_bits;
+    info_host[7] = 0;
+  }
+}
+
+// the dense operator: the symmetric PSD matrix a [g x g]; every product and Gram matrix is one GEMM on the f64 matrix cores
+struct DenseOp {
   hipStream_t s;
   const double* a;
   int64_t lda;
   int g, b;
   DenseBuffers d;
+  SubspaceScratch w;
+  const char* who = "dense eigensolver";
   int n_gemm = 0, n_chol_retry = 0;
+  int64_t rows() const { return g; }
+  void carve(Workspace& ws, int block) {
+    b = block;
+    dense_carve(ws, g, b, &d);
+    w = d.w;
+  }
+  int gram(const double* p, int bp, const double* q, int bq, double* out) {
+    return dgemm_tn(s, p, bp, q, bq, bp, bq, g, 1.0, nullptr, 0, 0.0, nullptr, 0, 0.0, out, bq);
+  }
+  // (the recurrence lives in the GEMM's epilogue)
+  int apply(const double* y, const double* yprev, double al, double center, double bcoef, double* out) {
+    ++n_gemm;
+    if (!yprev) return dgemm_tn(s, a, lda, y, b, g, b, g, 1.0, nullptr, 0, 0.0, nullptr, 0, 0.0, out, b);
+    return dgemm_tn(s, a, lda, y, b, g, b, g, al, y, b, -center * al, yprev, b, -bcoef, out, b);
+  }
+  int deflate(double*) { return SCAMD_OK; }
 };
 
-static constexpr size_t CHOL_LDS = (size_t)(DB_MAX * DB_LD + DB_MAX) * sizeof(double);
-static constexpr size_t JAC_LDS = (size_t)(DB_MAX * DB_LD + DB_MAX) * sizeof(double);
-
-// zout = orthonormal basis of span(zin) by CholeskyQR2: two rounds of (Gram matrix, Cholesky factor, block times factor).
-// A failed pivot (the block is a Chebyshev-filtered one: kappa 1e9 and beyond, up to numerical rank deficiency) inserts
-// a SHIFTED round (Fukaya et al. 2020: factor G + s I, s ~ 11 (g b + b (b + 1)) u |Y|^2; every such round divides kappa by
-// ~1 / sqrt(s) ~ 3e3) and starts the count of plain rounds again; directions that were lost to rounding come back as
-// orthonormal noise, as they do from a Householder QR.  zin and tmp are overwritten; zin, tmp, zout are distinct panels.
-// filtered = the block comes out of a Chebyshev filter: its plain first round fails (kappa 1e16 and beyond: the solve of the
-// bench spent two Cholesky launches and their read-backs on finding that out), so the first round is a shifted one at once
-static int cholqr2(DenseCtx& cx, double* zin, double* tmp, double* zout, bool filtered = false, int plain_rounds = 2) {
-  const int g = cx.g, b = cx.b;
-  double* cur = zin;
-  double* other = tmp;
-  int plain_ok = 0, shifted_rounds = 0;
-  const double s0 = 11.0 * ((double)g * b + (double)b * (b + 1)) * 2.220446049250313e-16 * b;
-  while (plain_ok < plain_rounds) {
-    int rc = dgemm_tn(cx.s, cur, b, cur, b, b, b, g, 1.0, nullptr, 0, 0.0, nullptr, 0, 0.0, cx.d.gm, b);
-    if (rc != SCAMD_OK) return rc;
-    double shift = (filtered && plain_ok == 0 && shifted_rounds == 0) ? s0 : 0.0;
-    for (int attempt = shift > 0.0 ? 1 : 0;; ++attempt) {
-      int bad = 0;
-      hipLaunchKernelGGL(chol_factor_kernel, dim3(1), dim3(1024), CHOL_LDS, cx.s, cx.d.gm, b, shift, cx.d.s, cx.d.flags);
-      SCAMD_LAUNCH_CHECK();
-      SCAMD_READBACK_NOW(&bad, cx.d.flags, sizeof(int), cx.s);
-      if (!bad) break;
-      SCAMD_REQUIRE(attempt < 4 && shifted_rounds < 8, SCAMD_EUNSUPPORTED,
-                    "dense eigensolver: CholeskyQR gave up on the block (%d shifted rounds, attempt %d)", shifted_rounds,
-                    attempt);
-      shift = shift == 0.0 ? s0 : shift * 1e3;
-      ++cx.n_chol_retry;
-    }
-    const bool was_shifted = shift > 0.0;
-    double* dst = (!was_shifted && plain_ok == plain_rounds - 1) ? zout : other;
-    hipLaunchKernelGGL(panel_small_kernel, dim3((g + 7) / 8), dim3(256), 0, cx.s, cur, cx.d.s, g, b, b, dst);
-    SCAMD_LAUNCH_CHECK();
-    if (dst == other) std::swap(cur, other);
-    if (was_shifted) {
-      plain_ok = 0;
-      ++shifted_rounds;
-    } else {
-      ++plain_ok;
-    }
-  }
-  return SCAMD_OK;
-}
-
-// Rayleigh-Ritz on the orthonormal block z: az = A z, T = z^T az, T = Y diag(theta) Y^T, v = z Y, av = az Y
-static int rayleigh_ritz(DenseCtx& cx, const double* z, double* az, double* v, double* av, double* h_theta) {
-  const int g = cx.g, b = cx.b;
-  int rc = dgemm_tn(cx.s, cx.a, cx.lda, z, b, g, b, g, 1.0, nullptr, 0, 0.0, nullptr, 0, 0.0, az, b);
-  if (rc != SCAMD_OK) return rc;
-  ++cx.n_gemm;
-  rc = dgemm_tn(cx.s, z, b, az, b, b, b, g, 1.0, nullptr, 0, 0.0, nullptr, 0, 0.0, cx.d.t, b);
-  if (rc != SCAMD_OK) return rc;
-  hipLaunchKernelGGL(symmetrize_kernel, dim3((b * b + 255) / 256), dim3(256), 0, cx.s, cx.d.t, b);
-  SCAMD_LAUNCH_CHECK();
-  hipLaunchKernelGGL(jacobi_eigh_kernel, dim3(1), dim3(512), JAC_LDS, cx.s, cx.d.t, b, cx.d.theta, cx.d.y,
-                     cx.d.flags + 1);
-  SCAMD_LAUNCH_CHECK();
-  hipLaunchKernelGGL(panel_small_kernel, dim3((g + 7) / 8), dim3(256), 0, cx.s, z, cx.d.y, g, b, b, v);
-  SCAMD_LAUNCH_CHECK();
-  hipLaunchKernelGGL(panel_small_kernel, dim3((g + 7) / 8), dim3(256), 0, cx.s, az, cx.d.y, g, b, b, av);
-  SCAMD_LAUNCH_CHECK();
-  SCAMD_READBACK(h_theta, cx.d.theta, sizeof(double) * b, cx.s);  // (handed out by the caller's next synchronisation)
-  return SCAMD_OK;
-}
-
 // top-k eigenpairs of the symmetric PSD matrix a [g x g]: theta (device, descending) and v = cx.d.z[3] [g x b]
-static int dense_topk(DenseCtx& cx, int k, unsigned int seed, double tol, int* n_outer_out, double* resid_out) {
+static int dense_topk(DenseOp& cx, int k, unsigned int seed, double tol, DenseStats& st) {
   const int g = cx.g, b = cx.b;
   DenseBuffers& d = cx.d;
-  SCAMD_HIP_CHECK(hipFuncSetAttribute(reinterpret_cast<const void*>(chol_factor_kernel),
-                                      hipFuncAttributeMaxDynamicSharedMemorySize, (int)CHOL_LDS));
-  SCAMD_HIP_CHECK(hipFuncSetAttribute(reinterpret_cast<const void*>(jacobi_eigh_kernel),
-                                      hipFuncAttributeMaxDynamicSharedMemorySize, (int)JAC_LDS));
+  int rc = prepare_lds_kernels();
+  if (rc != SCAMD_OK) return rc;
   HostReadbackScope readback_scope;  // (h_theta below is the destination of a fetch handed out one synchronisation later)
   std::vector<double> h_theta(b);
   double h_resid = INFINITY;
   double *z = d.z[0], *tmp = d.z[1], *az = d.z[2], *v = d.z[3], *av = d.z[4], *y0 = d.z[5], *y1 = d.z[6];
+  const int64_t cnt = (int64_t)g * b;
+  const unsigned egrid = (unsigned)((cnt + 255) / 256);
+  st.block_size = b;
+  hipLaunchKernelGGL(randn_kernel, dim3(egrid), dim3(256), 0, cx.s, z, cnt, seed);
+  SCAMD_LAUNCH_CHECK();
   if (b == g) {
     // the block is the whole space: one Rayleigh-Ritz on the identity-like basis = a full eigendecomposition
-    hipLaunchKernelGGL(randn_kernel, dim3((unsigned)(((int64_t)g * b + 255) / 256)), dim3(256), 0, cx.s, z, (int64_t)g * b,
-                       seed);
-    SCAMD_LAUNCH_CHECK();
-    int rc = cholqr2(cx, z, tmp, y0);
+    rc = cholqr2(cx, z, tmp, y0, false, 2);
     if (rc != SCAMD_OK) return rc;
     rc = rayleigh_ritz(cx, y0, az, v, av, h_theta.data());
     if (rc != SCAMD_OK) return rc;
     SCAMD_READBACK_SYNC(cx.s);
-    *n_outer_out = 0;
-    *resid_out = 0.0;
     return SCAMD_OK;
   }
-  hipLaunchKernelGGL(randn_kernel, dim3((unsigned)(((int64_t)g * b + 255) / 256)), dim3(256), 0, cx.s, z, (int64_t)g * b, seed);
-  SCAMD_LAUNCH_CHECK();
-  const int64_t cnt = (int64_t)g * b;
-  const unsigned egrid = (unsigned)((cnt + 255) / 256);
-  // One Chebyshev filter of degree m on the block (vv, avv = A vv), damping [0, c] and scaled to ~1 at `top`; the result
-  // ends up in z.  vv / avv are left intact.
-  auto filter = [&](const double* vv, const double* avv, double c, double top, int m) -> int {
-    const double e = 0.5 * c, center = 0.5 * c;
-    double sigma = e / (top - center);
-    const double sigma1 = sigma;
-    hipLaunchKernelGGL(axpby_kernel, dim3(egrid), dim3(256), 0, cx.s, cnt, sigma1 / e, avv, -center * sigma1 / e, vv, y0);
-    SCAMD_LAUNCH_CHECK();
-    const double* yprev = vv;
-    double* ycur = y0;
-    double* ynew = y1;
-    for (int it = 2; it <= m; ++it) {
-      const double sigma2 = 1.0 / (2.0 / sigma1 - sigma);
-      const double al = 2.0 * sigma2 / e;
-      int rcf = dgemm_tn(cx.s, cx.a, cx.lda, ycur, b, g, b, g, al, ycur, b, -center * al, yprev, b, -(sigma * sigma2), ynew, b);
-      if (rcf != SCAMD_OK) return rcf;
-      ++cx.n_gemm;
-      double* old = (yprev == vv) ? z : const_cast<double*>(yprev);  // vv is never written: z joins the rotation
-      yprev = ycur;
-      ycur = ynew;
-      ynew = old;
-      sigma = sigma2;
-    }
-    if (ycur != z) {  // (a copy by a kernel of ours, not a blit of the runtime)
-      hipLaunchKernelGGL(axpby_kernel, dim3(egrid), dim3(256), 0, cx.s, cnt, 1.0, ycur, 0.0, ycur, z);
+  // a filter whose result ends up in z (a copy by a kernel of ours, not a blit of the runtime)
+  auto filter_into_z = [&](const double* vv, const double* avv, double c, double top, int m) -> int {
+    double* last = nullptr;
+    const int rcf = chebyshev_filter(cx, vv, avv, c, top, m, y0, y1, z, &last);
+    if (rcf != SCAMD_OK) return rcf;
+    if (last != z) {
+      hipLaunchKernelGGL(axpby_kernel, dim3(egrid), dim3(256), 0, cx.s, cnt, 1.0, last, 0.0, last, z);
       SCAMD_LAUNCH_CHECK();
     }
     return SCAMD_OK;
   };
   // two power steps (A (A z): the condition number of the block grows by (lambda_1 / lambda_b)^2, well within
   // CholeskyQR2's reach) and one orthonormalisation
-  int rc = dgemm_tn(cx.s, cx.a, cx.lda, z, b, g, b, g, 1.0, nullptr, 0, 0.0, nullptr, 0, 0.0, y1, b);
+  rc = cx.apply(z, nullptr, 1.0, 0.0, 0.0, y1);
   if (rc != SCAMD_OK) return rc;
-  rc = dgemm_tn(cx.s, cx.a, cx.lda, y1, b, g, b, g, 1.0, nullptr, 0, 0.0, nullptr, 0, 0.0, z, b);
+  rc = cx.apply(y1, nullptr, 1.0, 0.0, 0.0, z);
   if (rc != SCAMD_OK) return rc;
-  cx.n_gemm += 2;
   // (ONE plain round here: the block has been through two power steps, kappa ~ (lambda_1 / lambda_b)^2, and serves for the
   // Rayleigh quotients that bound the first filter and as that filter's start -- orthonormal to ~kappa^2 u is enough for both;
   // the block is orthonormalised properly after the filter; two rounds, as until round 6: pca_fit 9.41 against 9.20 ms, same residual)
@@ -715,9 +670,8 @@ static int dense_topk(DenseCtx& cx, int k, unsigned int seed, double tol, int* n
   // the block (the filter does not care) at the price of one more 128 x 128 eigenproblem, the most expensive kernel of
   // the solve.  c = smallest quotient (>= lambda_b is not guaranteed, the filter only needs a cut inside the unwanted
   // part), top = largest quotient (a scaling).
-  rc = dgemm_tn(cx.s, cx.a, cx.lda, v, b, g, b, g, 1.0, nullptr, 0, 0.0, nullptr, 0, 0.0, av, b);
+  rc = cx.apply(v, nullptr, 1.0, 0.0, 0.0, av);
   if (rc != SCAMD_OK) return rc;
-  ++cx.n_gemm;
   hipLaunchKernelGGL(rq_minmax_kernel, dim3(1), dim3(1024), 0, cx.s, v, av, g, b, d.resid);
   SCAMD_LAUNCH_CHECK();
   double h_rq[3] = {0.0, 0.0, 0.0};
@@ -726,23 +680,21 @@ static int dense_topk(DenseCtx& cx, int k, unsigned int seed, double tol, int* n
     // degree of the first filter: 7 (8 until round 6).  On the bench's matrix 8 / 7 / 6 / 5 leave the residual at 4.5e-11 / 4.6e-10 /
     // 4.8e-9 / 5e-8 against the tolerance 2e-8: 8 buys nothing but a block so ill-conditioned that CholeskyQR needs a second
     // shifted round (pca_fit 9.76 / 9.45 / 9.35 ms; 5: a second outer iteration)
-    rc = filter(v, av, h_rq[1], h_rq[2], 7);
+    rc = filter_into_z(v, av, h_rq[1], h_rq[2], 7);
     if (rc != SCAMD_OK) return rc;
-    rc = cholqr2(cx, z, tmp, y0, true);
+    rc = cholqr2(cx, z, tmp, y0, true, 2);
     if (rc != SCAMD_OK) return rc;
-    rc = rayleigh_ritz(cx, y0, az, v, av, h_theta.data());
-  } else {
+  } else {  // (the Rayleigh-Ritz below writes v: it works on a copy)
     hipLaunchKernelGGL(axpby_kernel, dim3(egrid), dim3(256), 0, cx.s, cnt, 1.0, v, 0.0, v, y0);
     SCAMD_LAUNCH_CHECK();
-    rc = rayleigh_ritz(cx, y0, az, v, av, h_theta.data());
   }
+  rc = rayleigh_ritz(cx, y0, az, v, av, h_theta.data());
   if (rc != SCAMD_OK) return rc;
   int outer = 0;
-  const char* dbg_env = getenv("SCAMD_DENSE_DEBUG");
-  const bool dbg = dbg_env && dbg_env[0] == '1';
+  const bool dbg = env_is("SCAMD_DENSE_DEBUG", '1');
   constexpr int MAX_OUTER = 60;
   for (outer = 1;; ++outer) {
-    hipLaunchKernelGGL(residual_kernel, dim3(1), dim3(1024), 0, cx.s, v, av, d.theta, g, b, k, d.resid);
+    hipLaunchKernelGGL(residual_kernel, dim3(1), dim3(1024), 0, cx.s, v, av, cx.w.theta, g, b, k, d.resid);
     SCAMD_LAUNCH_CHECK();
     SCAMD_READBACK(&h_resid, d.resid, sizeof(double), cx.s);
     SCAMD_READBACK_SYNC(cx.s);  // (also completes the copy of theta)
@@ -757,30 +709,21 @@ static int dense_topk(DenseCtx& cx, int k, unsigned int seed, double tol, int* n
     bool filtered = false;
     if (!(top > c && c > 0.0)) {
       // rank-deficient block (c == 0): a plain power step on the Ritz block
-      rc = dgemm_tn(cx.s, cx.a, cx.lda, av, b, g, b, g, 1.0, nullptr, 0, 0.0, nullptr, 0, 0.0, z, b);
+      rc = cx.apply(av, nullptr, 1.0, 0.0, 0.0, z);
       if (rc != SCAMD_OK) return rc;
-      ++cx.n_gemm;
     } else {
-      // Degree: the filter grows like cosh(m acosh x), x = (lambda - center) / e, so the LARGEST wanted eigenvalue is
-      // amplified exp(m (acosh x_1 - acosh x_k)) times more than the smallest wanted one.  Beyond ~1e9 every column
-      // is the leading eigenvector plus rounding noise and the k-th pair never converges (seen with k = 40 on a
-      // matrix with 29 separated eigenvalues above a bulk: residual stuck at 1e-7, a Cholesky retry every iteration).
-      const double e = 0.5 * c, center = 0.5 * c;
-      const double x1 = (top - center) / e, xk = std::max((h_theta[k - 1] - center) / e, 1.0);
-      const double spread = std::acosh(x1) - std::acosh(xk);
-      int m = 16;
-      if (spread > 0.0) m = std::max(4, std::min(m, (int)std::floor(20.7 / spread)));
-      rc = filter(v, av, c, top, m);
+      const int m = chebyshev_degree(c, top, h_theta[k - 1], 16);
+      rc = filter_into_z(v, av, c, top, m);
       if (rc != SCAMD_OK) return rc;
       filtered = m >= 8;
     }
-    rc = cholqr2(cx, z, tmp, y0, filtered);
+    rc = cholqr2(cx, z, tmp, y0, filtered, 2);
     if (rc != SCAMD_OK) return rc;
     rc = rayleigh_ritz(cx, y0, az, v, av, h_theta.data());
     if (rc != SCAMD_OK) return rc;
   }
-  *n_outer_out = outer;
-  *resid_out = h_resid;
+  st.n_outer += outer;
+  st.residual = std::max(st.residual, h_resid);
   return SCAMD_OK;
 }
 
@@ -807,32 +750,25 @@ extern "C" int scamd_eigh_topk_f64(const double* a, int64_t g, int64_t lda, int 
                 "eigh_topk: k=%d needs a block beyond %d columns (use a full eigendecomposition)", k, DB_MAX);
   SCAMD_REQUIRE(b == g || g >= 2 * b, SCAMD_EUNSUPPORTED, "eigh_topk: g=%lld between %d and %d is served by a full eigh",
                 (long long)g, DB_MAX, 2 * DB_MAX);
-  DenseCtx cx;
+  DenseOp cx;
   cx.s = stream;
   cx.a = a;
   cx.lda = lda;
   cx.g = (int)g;
-  cx.b = b;
   Workspace ws(workspace, workspace_bytes);
-  dense_carve(ws, g, b, &cx.d);
+  cx.carve(ws, b);
   SCAMD_REQUIRE(workspace && ws.ok, SCAMD_EWORKSPACE, "eigh_topk: workspace %zu < required %zu", workspace_bytes, ws.used());
-  int n_outer = 0;
-  double resid = 0.0;
-  int rc = dense_topk(cx, k, (unsigned int)(seed ^ (seed >> 32)) * 0x9E3779B1u + 12345u, tol, &n_outer, &resid);
+  DenseStats st;
+  int rc = dense_topk(cx, k, eigensolver_seed(seed, 12345u), tol, st);
   if (rc != SCAMD_OK) return rc;
   // lam[k], v [g x k] row-major (column j = eigenvector j), unsigned
-  SCAMD_HIP_CHECK(hipMemcpyAsync(lam, cx.d.theta, sizeof(double) * k, hipMemcpyDeviceToDevice, stream));
+  SCAMD_HIP_CHECK(hipMemcpyAsync(lam, cx.w.theta, sizeof(double) * k, hipMemcpyDeviceToDevice, stream));
   SCAMD_HIP_CHECK(hipMemcpy2DAsync(v, sizeof(double) * k, cx.d.z[3], sizeof(double) * b, sizeof(double) * k, (size_t)g,
                                    hipMemcpyDeviceToDevice, stream));
   SCAMD_HIP_CHECK(hipStreamSynchronize(stream));
-  if (info_host) {
-    info_host[0] = n_outer;
-    info_host[1] = cx.n_gemm;
-    info_host[2] = b;
-    info_host[3] = cx.n_chol_retry;
-    double r = resid;
-    memcpy(info_host + 4, &r, sizeof(double));  // info_host[4..5] = residual (float64)
-  }
+  st.n_gemm = cx.n_gemm;
+  st.n_chol_retry = cx.n_chol_retry;
+  pack_dense_info(info_host, st, -1);
   return SCAMD_OK;
 }
 
@@ -851,14 +787,12 @@ extern "C" int scamd_dense_debug_f64(int op, const double* in0, const double* in
     int* dflag = nullptr;
     SCAMD_HIP_CHECK(hipMalloc(reinterpret_cast<void**>(&dflag), 2 * sizeof(int)));
     SCAMD_HIP_CHECK(hipMemsetAsync(dflag, 0, 2 * sizeof(int), stream));
+    int rc = prepare_lds_kernels();
+    if (rc != SCAMD_OK) return rc;
     if (op == 2) {
-      SCAMD_HIP_CHECK(hipFuncSetAttribute(reinterpret_cast<const void*>(chol_factor_kernel),
-                                          hipFuncAttributeMaxDynamicSharedMemorySize, (int)CHOL_LDS));
       hipLaunchKernelGGL(chol_factor_kernel, dim3(1), dim3(1024), CHOL_LDS, stream, in0, b, 0.0, out0, dflag);
     } else {
       SCAMD_REQUIRE(out1, SCAMD_EINVAL, "dense_debug: null pointer");
-      SCAMD_HIP_CHECK(hipFuncSetAttribute(reinterpret_cast<const void*>(jacobi_eigh_kernel),
-                                          hipFuncAttributeMaxDynamicSharedMemorySize, (int)JAC_LDS));
       hipLaunchKernelGGL(jacobi_eigh_kernel, dim3(1), dim3(512), JAC_LDS, stream, in0, b, out0, out1, dflag + 1);
     }
     SCAMD_LAUNCH_CHECK();
@@ -957,30 +891,21 @@ static bool dense_in_range(int64_t g, int k) {
 }
 // top-k eigenpairs of cx.a (DESTROYED when k needs more than one batch) -> comp64 [k x g] (sign convention applied),
 // v32 [g x k] (may be NULL), theta_all [k] (descending, raw).  `scratch` = kb_max x g doubles for the deflation.
-static int dense_topk_batched(DenseCtx& cx, double* a_mut, int k, unsigned int dseed, double tol, double* comp64, float* v32,
-                              double* theta_all, double* scratch, void* dense_ws, size_t dense_ws_bytes, int* n_outer, double* resid,
-                              int* bsz_out) {
+static int dense_topk_batched(DenseOp& cx, double* a_mut, int k, unsigned int dseed, double tol, double* comp64, float* v32,
+                              double* theta_all, double* scratch, void* dense_ws, size_t dense_ws_bytes, DenseStats& st) {
   const int g = cx.g;
-  *n_outer = 0;
-  *resid = 0.0;
   for (int k0 = 0; k0 < k;) {
     const int kb = g <= DB_MAX ? k : std::min(k - k0, DENSE_BATCH);
     const int bsz = dense_block_size(g, kb);
-    cx.b = bsz;
     Workspace dws(dense_ws, dense_ws_bytes);
-    dense_carve(dws, g, bsz, &cx.d);
+    cx.carve(dws, bsz);
     SCAMD_REQUIRE(dws.ok, SCAMD_EWORKSPACE, "dense eigensolver: workspace");
-    int outer = 0;
-    double rs = 0.0;
-    int rc = dense_topk(cx, kb, dseed + 0x9E3779B9u * (unsigned int)k0, tol, &outer, &rs);
+    int rc = dense_topk(cx, kb, dseed + 0x9E3779B9u * (unsigned int)k0, tol, st);
     if (rc != SCAMD_OK) return rc;
-    *n_outer += outer;
-    *resid = std::max(*resid, rs);
-    *bsz_out = bsz;
     hipLaunchKernelGGL(finalize_components_kernel, dim3(kb), dim3(256), 0, cx.s, cx.d.z[3], g, bsz, k, comp64 + (int64_t)k0 * g,
                        v32 ? v32 + k0 : (float*)nullptr);
     SCAMD_LAUNCH_CHECK();
-    hipLaunchKernelGGL(axpby_kernel, dim3((kb + 255) / 256), dim3(256), 0, cx.s, (int64_t)kb, 1.0, cx.d.theta, 0.0, cx.d.theta,
+    hipLaunchKernelGGL(axpby_kernel, dim3((kb + 255) / 256), dim3(256), 0, cx.s, (int64_t)kb, 1.0, cx.w.theta, 0.0, cx.w.theta,
                        theta_all + k0);
     SCAMD_LAUNCH_CHECK();
     k0 += kb;
@@ -994,32 +919,36 @@ static int dense_topk_batched(DenseCtx& cx, double* a_mut, int k, unsigned int d
       ++cx.n_gemm;
     }
   }
+  st.n_gemm = cx.n_gemm;
+  st.n_chol_retry = cx.n_chol_retry;
   return SCAMD_OK;
 }
+// where pca_solve_gram leaves the model (device): components [k x g], float32 loadings [g x k], shift [k] = mu^T V, variance [k],
+// variance_ratio [k], mean [g], eigenvalues [k] (may be NULL)
+struct PcaModel {
+  double* components; float* v32; float* shift; double* variance; double* variance_ratio; double* mean; double* eigenvalues;
+};
 // steps 3-5 and 7 of the route; `dseed` is handed to the eigensolver as it is.  No synchronisation: the caller drains.
 static int pca_solve_gram(const long long* gram, int64_t ld_gram, const long long* colsum, int64_t n, int64_t g, int scale_bits,
-                          int k, int zero_center, unsigned int dseed, double tol, double* components, float* v32, float* shift,
-                          double* variance, double* variance_ratio, double* mean, double* theta_out, PcaSolveBuffers& b,
-                          hipStream_t s, int* n_outer, double* resid, int* n_gemm, int* bsz_out, int* n_chol_retry) {
+                          int k, int zero_center, unsigned int dseed, double tol, const PcaModel& out, PcaSolveBuffers& b,
+                          hipStream_t s, DenseStats& st) {
   // 3. A = G - n mu mu^T, means, column variances
   const double inv = std::ldexp(1.0, -scale_bits);
   hipLaunchKernelGGL(cov_from_gram_kernel, dim3((unsigned)(((int64_t)g * g + 255) / 256)), dim3(256), 0, s, gram, ld_gram,
-                     colsum, (int)g, inv, (double)n, zero_center ? 1 : 0, b.a, mean, b.var);
+                     colsum, (int)g, inv, (double)n, zero_center ? 1 : 0, b.a, out.mean, b.var);
   SCAMD_LAUNCH_CHECK();
   // 4. top-k eigenpairs (batches of DENSE_BATCH with deflation when k needs more than one block)
   SCAMD_REQUIRE(dense_in_range(g, k), SCAMD_EUNSUPPORTED, "pca: n_comps=%d / g=%lld outside the device eigensolver's range", k,
                 (long long)g);
-  DenseCtx cx;
+  DenseOp cx;
   cx.s = s;
   cx.a = b.a;
   cx.lda = g;
   cx.g = (int)g;
-  int bsz = 0;
   // 5. (inside the batches) sign convention, float32 loadings; then the projected means
-  int rc = dense_topk_batched(cx, b.a, k, dseed, tol, components, v32, b.theta_all, b.deflate, b.dense_ws, b.dense_ws_bytes, n_outer,
-                              resid, &bsz);
+  int rc = dense_topk_batched(cx, b.a, k, dseed, tol, out.components, out.v32, b.theta_all, b.deflate, b.dense_ws, b.dense_ws_bytes, st);
   if (rc != SCAMD_OK) return rc;
-  hipLaunchKernelGGL(mean_shift_kernel, dim3(k), dim3(256), 0, s, mean, v32, (int)g, k, shift, b.proj);
+  hipLaunchKernelGGL(mean_shift_kernel, dim3(k), dim3(256), 0, s, out.mean, out.v32, (int)g, k, out.shift, b.proj);
   SCAMD_LAUNCH_CHECK();
   // 7. explained variance (sklearn: S^2 / (n - 1); ratio against the total variance with the same n / (n - 1) factor;
   //    zero_center = False is TruncatedSVD: the variance of the scores of the uncentred decomposition, lam / n - (mu^T v)^2)
@@ -1028,16 +957,13 @@ static int pca_solve_gram(const long long* gram, int64_t ld_gram, const long lon
   const double denom = zero_center ? (double)(n - 1) : (double)n;
   const double total_scale = zero_center ? (double)n / (double)(n - 1) : 1.0;
   hipLaunchKernelGGL(variance_kernel, dim3((k + 255) / 256), dim3(256), 0, s, b.theta_all, k, denom,
-                     zero_center ? (const double*)nullptr : (const double*)b.proj, b.varsum, total_scale, variance,
-                     variance_ratio);
+                     zero_center ? (const double*)nullptr : (const double*)b.proj, b.varsum, total_scale, out.variance,
+                     out.variance_ratio);
   SCAMD_LAUNCH_CHECK();
-  if (theta_out) {
-    hipLaunchKernelGGL(copy_theta_kernel, dim3((k + 255) / 256), dim3(256), 0, s, b.theta_all, k, theta_out);
+  if (out.eigenvalues) {
+    hipLaunchKernelGGL(copy_theta_kernel, dim3((k + 255) / 256), dim3(256), 0, s, b.theta_all, k, out.eigenvalues);
     SCAMD_LAUNCH_CHECK();
   }
-  *n_gemm = cx.n_gemm;
-  *bsz_out = bsz;
-  *n_chol_retry = cx.n_chol_retry;
   return SCAMD_OK;
 }
 }  // namespace scamd
@@ -1065,23 +991,13 @@ extern "C" int scamd_pca_solve_gram_f64(const int64_t* gram, int64_t ld_gram, co
   PcaSolveBuffers b;
   pca_solve_carve(ws, g, k, &b);
   SCAMD_REQUIRE(workspace && ws.ok, SCAMD_EWORKSPACE, "pca solve: workspace %zu < required %zu", workspace_bytes, ws.used());
-  int n_outer = 0, n_gemm = 0, bsz = 0, n_chol = 0;
-  double resid = 0.0;
+  DenseStats st;
+  const PcaModel model{components, loadings_f32, shift, variance, variance_ratio, mean, eigenvalues};
   int rc = pca_solve_gram(reinterpret_cast<const long long*>(gram), ld_gram, reinterpret_cast<const long long*>(colsum), n_total, g,
-                          scale_bits, k, zero_center, (unsigned int)(seed ^ (seed >> 32)) * 0x9E3779B1u + 12345u, tol, components,
-                          loadings_f32, shift, variance, variance_ratio, mean, eigenvalues, b, stream, &n_outer, &resid, &n_gemm,
-                          &bsz, &n_chol);
+                          scale_bits, k, zero_center, eigensolver_seed(seed, 12345u), tol, model, b, stream, st);
   if (rc != SCAMD_OK) return rc;
   SCAMD_HIP_CHECK(hipStreamSynchronize(stream));
-  if (info_host) {
-    info_host[0] = n_outer;
-    info_host[1] = n_gemm;
-    info_host[2] = bsz;
-    info_host[3] = n_chol;
-    memcpy(info_host + 4, &resid, sizeof(double));
-    info_host[6] = scale_bits;
-    info_host[7] = 0;
-  }
+  pack_dense_info(info_host, st, scale_bits);
   return SCAMD_OK;
 }
 
@@ -1143,25 +1059,15 @@ extern "C" int scamd_pca_csr_f32(const int64_t* indptr, const int32_t* indices, 
   Workspace sws(b.solve_ws, b.solve_ws_bytes);
   PcaSolveBuffers sb;
   pca_solve_carve(sws, g, k, &sb);
-  int n_outer = 0, n_gemm = 0, bsz = 0, n_chol = 0;
-  double resid = 0.0;
-  rc = pca_solve_gram(b.gram, gp, b.colsum, n, g, scale_bits, k, zero_center, (unsigned int)(seed ^ (seed >> 32)) * 0x9E3779B1u + 12345u,
-                      tol, components, b.v32, b.shift, variance, variance_ratio, mean, nullptr, sb, s, &n_outer, &resid, &n_gemm, &bsz,
-                      &n_chol);
+  DenseStats st;
+  const PcaModel model{components, b.v32, b.shift, variance, variance_ratio, mean, nullptr};
+  rc = pca_solve_gram(b.gram, gp, b.colsum, n, g, scale_bits, k, zero_center, eigensolver_seed(seed, 12345u), tol, model, sb, s, st);
   if (rc != SCAMD_OK) return rc;
   // 6. scores = X V - 1 shift^T
   rc = scamd_spmm_csr_f32(indptr, indices, data, n, g, b.v32, k, zero_center ? b.shift : nullptr, scores, s);
   if (rc != SCAMD_OK) return rc;
   SCAMD_HIP_CHECK(hipStreamSynchronize(s));
-  if (info_host) {
-    info_host[0] = n_outer;
-    info_host[1] = n_gemm;
-    info_host[2] = bsz;
-    info_host[3] = n_chol;
-    memcpy(info_host + 4, &resid, sizeof(double));
-    info_host[6] = scale_bits;
-    info_host[7] = 0;
-  }
+  pack_dense_info(info_host, st, scale_bits);
   return SCAMD_OK;
 }
 
@@ -1286,9 +1192,6 @@ __global__ __launch_bounds__(256) void sp_resid_kernel(const double* __restrict_
     if (j < dim) part[(int64_t)blockIdx.x * dim + j] = s;
   }
 }
-__global__ void sp_zero_i32_kernel(int* __restrict__ p, int n) {
-  if ((int)threadIdx.x < n) p[threadIdx.x] = 0;
-}
 // out[row][j] = v[row][j], j < dim (row stride b -> dim)
 __global__ void sp_take_kernel(const double* __restrict__ v, int64_t n, int b, int dim, double* __restrict__ out) {
   const int64_t e = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
@@ -1299,7 +1202,7 @@ __global__ void sp_take_kernel(const double* __restrict__ v, int64_t n, int b, i
 
 struct SpectralBuffers {
   double* deg; double* t0; float* s; double* pan[7]; float* y32; float* sy32; double* part;
-  double* gm; double* smat; double* tmat; double* ymat; double* theta; double* cvec; double* nrm2; double* rnorm; int* flags;
+  SubspaceScratch w; double* cvec; double* nrm2; double* rnorm;
 };
 static void spectral_carve(Workspace& ws, int64_t n, int64_t nnz, int b, SpectralBuffers* sb) {
   sb->deg = ws.take<double>((size_t)n);
@@ -1309,109 +1212,62 @@ static void spectral_carve(Workspace& ws, int64_t n, int64_t nnz, int b, Spectra
   sb->y32 = ws.take<float>((size_t)n * b);
   sb->sy32 = ws.take<float>((size_t)n * b);
   sb->part = ws.take<double>((size_t)SP_GRID * SP_MAXB * SP_MAXB);
-  sb->gm = ws.take<double>(SP_MAXB * SP_MAXB);
-  sb->smat = ws.take<double>(SP_MAXB * SP_MAXB);
-  sb->tmat = ws.take<double>(SP_MAXB * SP_MAXB);
-  sb->ymat = ws.take<double>(SP_MAXB * SP_MAXB);
-  sb->theta = ws.take<double>(SP_MAXB);
+  sb->w.gm = ws.take<double>(SP_MAXB * SP_MAXB);
+  sb->w.smat = ws.take<double>(SP_MAXB * SP_MAXB);
+  sb->w.tmat = ws.take<double>(SP_MAXB * SP_MAXB);
+  sb->w.ymat = ws.take<double>(SP_MAXB * SP_MAXB);
+  sb->w.theta = ws.take<double>(SP_MAXB);
   sb->cvec = ws.take<double>(SP_MAXB);
   sb->nrm2 = ws.take<double>(8);
   sb->rnorm = ws.take<double>(SP_MAXB);
-  sb->flags = ws.take<int>(8);
+  sb->w.flags = ws.take<int>(8);
 }
 
-struct SpectralCtx {
+// the spectral operator: M = (S + I) / 2 on n x b panels, S = D^-1/2 A D^-1/2 as the float32 SpMM of pca.hip; every reduction
+// over the n rows is a two-stage sum in a fixed order
+struct SpectralOp {
   hipStream_t s;
   const int64_t* indptr;
   const int32_t* indices;
   int64_t n;
   int b, dim;
   SpectralBuffers sb;
-  int n_apply = 0;
+  SubspaceScratch w;
+  const char* who = "spectral init";
+  int n_apply = 0, n_chol_retry = 0;
+  int64_t rows() const { return n; }
   int grid_rows() const { return (int)std::min<int64_t>(SP_GRID, (n + 63) / 64); }
   unsigned egrid() const { return (unsigned)((n * b + 255) / 256); }
-};
-// out[bp x bq] = p^T q over the n rows
-static int sp_gram(SpectralCtx& cx, const double* p, int bp, const double* q, int bq, double* out) {
-  const int g = cx.grid_rows();
-  hipLaunchKernelGGL(sp_tall_gram_kernel, dim3(g), dim3(256), 0, cx.s, p, bp, q, bq, cx.n, cx.sb.part);
-  SCAMD_LAUNCH_CHECK();
-  hipLaunchKernelGGL(sp_reduce_kernel, dim3(1), dim3(256), 0, cx.s, cx.sb.part, g, bp * bq, out);
-  SCAMD_LAUNCH_CHECK();
-  return SCAMD_OK;
-}
-// y <- y - t0 (t0^T y) / |t0|^2
-static int sp_deflate(SpectralCtx& cx, double* y) {
-  int rc = sp_gram(cx, cx.sb.t0, 1, y, cx.b, cx.sb.cvec);
-  if (rc != SCAMD_OK) return rc;
-  hipLaunchKernelGGL(sp_deflate_kernel, dim3(cx.egrid()), dim3(256), 0, cx.s, y, cx.sb.t0, cx.sb.cvec, cx.sb.nrm2, cx.n, cx.b);
-  SCAMD_LAUNCH_CHECK();
-  return SCAMD_OK;
-}
-// out = a (M y - center y) - bcoef yprev
-static int sp_apply(SpectralCtx& cx, const double* y, const double* yprev, double a, double center, double bcoef, double* out) {
-  const int64_t cnt = cx.n * cx.b;
-  hipLaunchKernelGGL(sp_to_f32_kernel, dim3(cx.egrid()), dim3(256), 0, cx.s, y, cnt, cx.sb.y32);
-  SCAMD_LAUNCH_CHECK();
-  int rc = scamd_spmm_csr_f32(cx.indptr, cx.indices, cx.sb.s, cx.n, cx.n, cx.sb.y32, cx.b, nullptr, cx.sb.sy32, cx.s);
-  if (rc != SCAMD_OK) return rc;
-  hipLaunchKernelGGL(sp_cheb_kernel, dim3(cx.egrid()), dim3(256), 0, cx.s, cnt, (const float*)cx.sb.sy32, y, yprev, a, center, bcoef, out);
-  SCAMD_LAUNCH_CHECK();
-  ++cx.n_apply;
-  return SCAMD_OK;
-}
-// CholeskyQR2 of the n x b block `cur` (overwritten) with scratch `other`; the orthonormal block ends in *result (one of the two)
-static int sp_cholqr2(SpectralCtx& cx, double* cur, double* other, double** result) {
-  const int b = cx.b;
-  int plain_ok = 0, shifted_rounds = 0;
-  const double s0 = 11.0 * ((double)cx.n * b + (double)b * (b + 1)) * 2.220446049250313e-16 * b;
-  while (plain_ok < 2) {
-    int rc = sp_gram(cx, cur, b, cur, b, cx.sb.gm);
-    if (rc != SCAMD_OK) return rc;
-    double shift = 0.0;
-    for (int attempt = 0;; ++attempt) {
-      int bad = 0;
-      hipLaunchKernelGGL(chol_factor_kernel, dim3(1), dim3(1024), CHOL_LDS, cx.s, cx.sb.gm, b, shift, cx.sb.smat, cx.sb.flags);
-      SCAMD_LAUNCH_CHECK();
-      SCAMD_READBACK_NOW(&bad, cx.sb.flags, sizeof(int), cx.s);
-      if (!bad) break;
-      SCAMD_REQUIRE(attempt < 4 && shifted_rounds < 8, SCAMD_EUNSUPPORTED,
-                    "spectral init: CholeskyQR gave up on the block (%d shifted rounds, attempt %d)", shifted_rounds, attempt);
-      shift = attempt == 0 ? s0 : shift * 1e3;
-      hipLaunchKernelGGL(sp_zero_i32_kernel, dim3(1), dim3(64), 0, cx.s, cx.sb.flags, 1);  // (chol_factor_kernel only RAISES the flag)
-      SCAMD_LAUNCH_CHECK();
-    }
-    hipLaunchKernelGGL(panel_small_kernel, dim3((unsigned)((cx.n + 7) / 8)), dim3(256), 0, cx.s, cur, cx.sb.smat, (int)cx.n, b, b, other);
+  // out[bp x bq] = p^T q over the n rows
+  int gram(const double* p, int bp, const double* q, int bq, double* out) {
+    const int g = grid_rows();
+    hipLaunchKernelGGL(sp_tall_gram_kernel, dim3(g), dim3(256), 0, s, p, bp, q, bq, n, sb.part);
     SCAMD_LAUNCH_CHECK();
-    std::swap(cur, other);
-    if (shift > 0.0) {
-      plain_ok = 0;
-      ++shifted_rounds;
-    } else {
-      ++plain_ok;
-    }
+    hipLaunchKernelGGL(sp_reduce_kernel, dim3(1), dim3(256), 0, s, sb.part, g, bp * bq, out);
+    SCAMD_LAUNCH_CHECK();
+    return SCAMD_OK;
   }
-  *result = cur;
-  return SCAMD_OK;
-}
-// Rayleigh-Ritz on the orthonormal block z: mz = M z, T = z^T mz = Y diag(theta) Y^T, v = z Y, mv = mz Y; theta -> host
-static int sp_rayleigh_ritz(SpectralCtx& cx, const double* z, double* mz, double* v, double* mv, double* h_theta) {
-  const int b = cx.b;
-  int rc = sp_apply(cx, z, nullptr, 1.0, 0.0, 0.0, mz);
-  if (rc != SCAMD_OK) return rc;
-  rc = sp_gram(cx, z, b, mz, b, cx.sb.tmat);
-  if (rc != SCAMD_OK) return rc;
-  hipLaunchKernelGGL(symmetrize_kernel, dim3(1), dim3(256), 0, cx.s, cx.sb.tmat, b);
-  SCAMD_LAUNCH_CHECK();
-  hipLaunchKernelGGL(jacobi_eigh_kernel, dim3(1), dim3(512), JAC_LDS, cx.s, cx.sb.tmat, b, cx.sb.theta, cx.sb.ymat, cx.sb.flags + 1);
-  SCAMD_LAUNCH_CHECK();
-  hipLaunchKernelGGL(panel_small_kernel, dim3((unsigned)((cx.n + 7) / 8)), dim3(256), 0, cx.s, z, cx.sb.ymat, (int)cx.n, b, b, v);
-  SCAMD_LAUNCH_CHECK();
-  hipLaunchKernelGGL(panel_small_kernel, dim3((unsigned)((cx.n + 7) / 8)), dim3(256), 0, cx.s, mz, cx.sb.ymat, (int)cx.n, b, b, mv);
-  SCAMD_LAUNCH_CHECK();
-  SCAMD_READBACK_NOW(h_theta, cx.sb.theta, sizeof(double) * b, cx.s);
-  return SCAMD_OK;
-}
+  // y <- y - t0 (t0^T y) / |t0|^2
+  int deflate(double* y) {
+    int rc = gram(sb.t0, 1, y, b, sb.cvec);
+    if (rc != SCAMD_OK) return rc;
+    hipLaunchKernelGGL(sp_deflate_kernel, dim3(egrid()), dim3(256), 0, s, y, sb.t0, sb.cvec, sb.nrm2, n, b);
+    SCAMD_LAUNCH_CHECK();
+    return SCAMD_OK;
+  }
+  // out = a (M y - center y) - bcoef yprev
+  int apply(const double* y, const double* yprev, double a, double center, double bcoef, double* out) {
+    const int64_t cnt = n * b;
+    hipLaunchKernelGGL(sp_to_f32_kernel, dim3(egrid()), dim3(256), 0, s, y, cnt, sb.y32);
+    SCAMD_LAUNCH_CHECK();
+    int rc = scamd_spmm_csr_f32(indptr, indices, sb.s, n, n, sb.y32, b, nullptr, sb.sy32, s);
+    if (rc != SCAMD_OK) return rc;
+    hipLaunchKernelGGL(sp_cheb_kernel, dim3(egrid()), dim3(256), 0, s, cnt, (const float*)sb.sy32, y, yprev, a, center, bcoef, out);
+    SCAMD_LAUNCH_CHECK();
+    ++n_apply;
+    return SCAMD_OK;
+  }
+};
 }  // namespace scamd
 
 extern "C" size_t scamd_spectral_embedding_workspace_bytes(int64_t n, int64_t nnz, int dim) {
@@ -1430,7 +1286,7 @@ extern "C" int scamd_spectral_embedding_f32(const int64_t* indptr, const int32_t
   SCAMD_REQUIRE(dim >= 1 && dim + 6 <= SP_MAXB, SCAMD_EUNSUPPORTED, "spectral init: %d components (at most %d)", dim, SP_MAXB - 6);
   SCAMD_REQUIRE(n > dim + 6 && n < ((int64_t)1 << 31) && nnz >= 1, SCAMD_EINVAL, "spectral init: bad shape n=%lld nnz=%lld",
                 (long long)n, (long long)nnz);
-  SpectralCtx cx;
+  SpectralOp cx;
   cx.s = stream;
   cx.indptr = indptr;
   cx.indices = indices;
@@ -1440,101 +1296,73 @@ extern "C" int scamd_spectral_embedding_f32(const int64_t* indptr, const int32_t
   const int b = cx.b;
   Workspace ws(workspace, workspace_bytes);
   spectral_carve(ws, n, nnz, b, &cx.sb);
+  cx.w = cx.sb.w;
   SCAMD_REQUIRE(workspace && ws.ok, SCAMD_EWORKSPACE, "spectral init: workspace %zu < required %zu", workspace_bytes, ws.used());
-  SCAMD_HIP_CHECK(hipFuncSetAttribute(reinterpret_cast<const void*>(chol_factor_kernel),
-                                      hipFuncAttributeMaxDynamicSharedMemorySize, (int)CHOL_LDS));
-  SCAMD_HIP_CHECK(hipFuncSetAttribute(reinterpret_cast<const void*>(jacobi_eigh_kernel),
-                                      hipFuncAttributeMaxDynamicSharedMemorySize, (int)JAC_LDS));
+  int rc = prepare_lds_kernels();
+  if (rc != SCAMD_OK) return rc;
+  HostReadbackScope readback_scope;  // (h_theta is the destination of a fetch handed out one synchronisation later)
+  double h_theta[SP_MAXB];
   SpectralBuffers& sb = cx.sb;
   hipStream_t s = stream;
-  // the flag words, then the operator: degrees, S = D^-1/2 A D^-1/2 in float32, the trivial eigenvector sqrt(deg)
-  hipLaunchKernelGGL(sp_zero_i32_kernel, dim3(1), dim3(64), 0, s, sb.flags, 8);
-  SCAMD_LAUNCH_CHECK();
+  // the operator: degrees, S = D^-1/2 A D^-1/2 in float32, the trivial eigenvector sqrt(deg)
   hipLaunchKernelGGL(sp_degree_kernel, dim3((unsigned)((n + 3) / 4)), dim3(256), 0, s, indptr, weights, n, sb.deg);
   SCAMD_LAUNCH_CHECK();
   hipLaunchKernelGGL(sp_scale_kernel, dim3((unsigned)((n + 3) / 4)), dim3(256), 0, s, indptr, indices, weights, n,
                      (const double*)sb.deg, sb.s, sb.t0);
   SCAMD_LAUNCH_CHECK();
-  int rc = sp_gram(cx, sb.t0, 1, sb.t0, 1, sb.nrm2);
+  rc = cx.gram(sb.t0, 1, sb.t0, 1, sb.nrm2);
   if (rc != SCAMD_OK) return rc;
   double *z = sb.pan[0], *tmp = sb.pan[1], *mz = sb.pan[2], *v = sb.pan[3], *mv = sb.pan[4], *y0 = sb.pan[5], *y1 = sb.pan[6];
   const int64_t cnt = n * b;
-  hipLaunchKernelGGL(randn_kernel, dim3(cx.egrid()), dim3(256), 0, s, z, cnt,
-                     (unsigned int)(seed ^ (seed >> 32)) * 0x9E3779B1u + 0x5bd1e995u);
+  hipLaunchKernelGGL(randn_kernel, dim3(cx.egrid()), dim3(256), 0, s, z, cnt, eigensolver_seed(seed, 0x5bd1e995u));
   SCAMD_LAUNCH_CHECK();
-  rc = sp_deflate(cx, z);
+  rc = cx.deflate(z);
   if (rc != SCAMD_OK) return rc;
-  double* zq = nullptr;
-  rc = sp_cholqr2(cx, z, tmp, &zq);
+  rc = cholqr2(cx, z, tmp, y0, false, 2);
   if (rc != SCAMD_OK) return rc;
-  double h_theta[SP_MAXB];
-  rc = sp_rayleigh_ritz(cx, zq, mz, v, mv, h_theta);
+  rc = rayleigh_ritz(cx, y0, mz, v, mv, h_theta);
   if (rc != SCAMD_OK) return rc;
   double resid = INFINITY;
   int outer = 0;
   for (outer = 1; outer <= max_outer; ++outer) {
     // residual of the wanted Ritz pairs (|M| = 1: absolute = relative)
     const int g = cx.grid_rows();
-    hipLaunchKernelGGL(sp_resid_kernel, dim3(g), dim3(256), 0, s, (const double*)v, (const double*)mv, (const double*)sb.theta, n, b, dim, sb.part);
+    hipLaunchKernelGGL(sp_resid_kernel, dim3(g), dim3(256), 0, s, (const double*)v, (const double*)mv, (const double*)cx.w.theta, n, b, dim, sb.part);
     SCAMD_LAUNCH_CHECK();
     hipLaunchKernelGGL(sp_reduce_kernel, dim3(1), dim3(256), 0, s, (const double*)sb.part, g, dim, sb.rnorm);
     SCAMD_LAUNCH_CHECK();
     double h_r[SP_MAXB];
-    SCAMD_READBACK_NOW(h_r, sb.rnorm, sizeof(double) * dim, s);
+    SCAMD_READBACK(h_r, sb.rnorm, sizeof(double) * dim, s);
+    SCAMD_READBACK_SYNC(s);  // (also completes the copy of theta)
     resid = 0.0;
     for (int j = 0; j < dim; ++j) resid = std::max(resid, std::sqrt(std::max(h_r[j], 0.0)));
     if (resid < tol) break;
     const double c = h_theta[b - 1];
-    double* blk = nullptr;  // the block that is deflated and orthonormalised next
-    if (!(c > 0.0 && c < 1.0)) {  // a degenerate block: one plain step keeps it simple
-      blk = mv;
-    } else {
-      const double e = 0.5 * c, center = 0.5 * c;
-      // the degree: as high as the amplification SPREAD inside the wanted set allows (beyond ~1e9 every column is the
-      // leading wanted vector plus rounding noise); the spectrum's upper end is 1
-      const double x1 = (1.0 - center) / e, xk = std::max((h_theta[dim - 1] - center) / e, 1.0);
-      const double spread = std::acosh(x1) - std::acosh(xk);
-      const int m = spread <= 0.0 ? max_degree : std::max(4, std::min(max_degree, (int)std::floor(20.7 / spread)));
-      double sigma = e / (1.0 - center);
-      const double sigma1 = sigma;
-      // y = (mv - center v) sigma1 / e = (sigma1 / e) mv - (center sigma1 / e) v
-      hipLaunchKernelGGL(axpby_kernel, dim3(cx.egrid()), dim3(256), 0, s, cnt, sigma1 / e, (const double*)mv, -center * sigma1 / e,
-                         (const double*)v, y0);
-      SCAMD_LAUNCH_CHECK();
-      const double* yprev = v;
-      double* ycur = y0;
-      double* ynew = y1;
-      for (int it = 2; it <= m; ++it) {
-        const double sigma2 = 1.0 / (2.0 / sigma1 - sigma);
-        rc = sp_apply(cx, ycur, yprev, 2.0 * sigma2 / e, center, sigma * sigma2, ynew);
-        if (rc != SCAMD_OK) return rc;
-        double* old = (yprev == v) ? z : const_cast<double*>(yprev);  // v is never written: z joins the rotation
-        yprev = ycur;
-        ycur = ynew;
-        ynew = old;
-        sigma = sigma2;
-      }
-      blk = ycur;
-    }
-    rc = sp_deflate(cx, blk);
-    if (rc != SCAMD_OK) return rc;
-    // scratch for the orthonormalisation: any panel that is neither the block nor v / mv / mz (those are rewritten below)
-    double* scratch = (blk == tmp) ? z : tmp;
-    if (scratch == blk) scratch = y1;
-    if (blk == mv) {  // (the plain step orthonormalises a COPY: mv is an output of the Rayleigh-Ritz that follows)
+    double* blk = nullptr;  // the block that is orthonormalised next
+    if (!(c > 0.0 && c < 1.0)) {
+      // a degenerate block: one plain step, on a COPY (mv is an output of the Rayleigh-Ritz that follows)
+      rc = cx.deflate(mv);
+      if (rc != SCAMD_OK) return rc;
       hipLaunchKernelGGL(axpby_kernel, dim3(cx.egrid()), dim3(256), 0, s, cnt, 1.0, (const double*)mv, 0.0, (const double*)mv, y0);
       SCAMD_LAUNCH_CHECK();
       blk = y0;
-      scratch = y1;
+    } else {
+      // the degree: as high as the amplification spread inside the wanted set allows; the spectrum's upper end is 1
+      const int m = chebyshev_degree(c, 1.0, h_theta[dim - 1], max_degree);
+      rc = chebyshev_filter(cx, v, mv, c, 1.0, m, y0, y1, z, &blk);
+      if (rc != SCAMD_OK) return rc;
+      rc = cx.deflate(blk);
+      if (rc != SCAMD_OK) return rc;
     }
-    rc = sp_cholqr2(cx, blk, scratch, &zq);
+    double* zq = blk == y0 ? y1 : y0;  // (tmp never joins the filter's rotation)
+    rc = cholqr2(cx, blk, tmp, zq, false, 2);
     if (rc != SCAMD_OK) return rc;
-    rc = sp_rayleigh_ritz(cx, zq, mz, v, mv, h_theta);
+    rc = rayleigh_ritz(cx, zq, mz, v, mv, h_theta);
     if (rc != SCAMD_OK) return rc;
   }
   hipLaunchKernelGGL(sp_take_kernel, dim3((unsigned)((n * dim + 255) / 256)), dim3(256), 0, s, (const double*)v, n, b, dim, out);
   SCAMD_LAUNCH_CHECK();
-  SCAMD_HIP_CHECK(hipStreamSynchronize(s));
+  SCAMD_READBACK_SYNC(s);  // (a loop that ends by max_outer leaves the last theta queued)
   if (info_host) {
     info_host[0] = (double)std::min(outer, max_outer);
     info_host[1] = (double)cx.n_apply;

@@ -18,11 +18,12 @@ from scanpy_amd._lib import SIGNATURES, leiden_stat_names  # noqa: E402
 
 
 @lru_cache(maxsize=2)
-def load(asan: bool = False) -> C.CDLL:
+def load(asan: bool = False, path: str | None = None) -> C.CDLL:
+    """path: an emulator library built elsewhere (an A/B of two builds), instead of this tree's"""
     sys.path.insert(0, str(HERE))
     import build as emu_build
 
-    lib = C.CDLL(str(emu_build.build(asan=asan)))
+    lib = C.CDLL(str(path or emu_build.build(asan=asan)))
     for name, (res, args) in SIGNATURES.items():
         fn = getattr(lib, name)
         fn.restype, fn.argtypes = res, args
@@ -155,6 +156,43 @@ def pca_csr(lib, x, n_comps, *, zero_center=True, seed=0, tol=2e-8):
                                _p(scores), _p(comps), _p(var), _p(ratio), _p(mean), _p(info), _p(ws), ws.size, None)
     _check(lib, rc, "pca_csr")
     return dict(scores=scores, components=comps, variance=var, variance_ratio=ratio, mean=mean, info=info)
+
+
+def dense_info(info):
+    return {"n_outer": int(info[0]), "n_gemm": int(info[1]), "block_size": int(info[2]), "chol_retries": int(info[3]),
+            "residual": float(info[4:6].view(np.float64)[0])}
+
+
+def eigh_topk(lib, a, k, *, seed=0, tol=2e-8):
+    """scamd_eigh_topk_f64 -> (lam [k], v [g, k], info dict as scanpy_amd._kernels.eigh_topk, raw info words)"""
+    a = np.ascontiguousarray(a, dtype=np.float64)
+    g = a.shape[0]
+    lam = np.full(k, np.nan)
+    v = np.full((g, k), np.nan)
+    info = np.zeros(12, dtype=np.int32)
+    ws = _ws(lib.scamd_eigh_topk_workspace_bytes(g, k))
+    rc = lib.scamd_eigh_topk_f64(_p(a), g, g, k, int(seed), float(tol), _p(lam), _p(v), _p(info), _p(ws), ws.size, None)
+    _check(lib, rc, "eigh_topk")
+    return lam, v, dense_info(info), info
+
+
+def spectral_embedding(lib, a, dim, *, seed=0, tol=2e-6, max_outer=60, max_degree=64):
+    """scamd_spectral_embedding_f32 on a scipy CSR graph -> (v [n, dim], info dict as scanpy_amd._kernels.spectral_embedding,
+    raw info doubles)"""
+    a = a.tocsr()
+    a.sort_indices()
+    n = a.shape[0]
+    indptr = np.ascontiguousarray(a.indptr, dtype=np.int64)
+    indices = np.ascontiguousarray(a.indices, dtype=np.int32)
+    w = np.ascontiguousarray(a.data, dtype=np.float32)
+    out = np.full((n, dim), np.nan)
+    info = np.zeros(8, dtype=np.float64)
+    ws = _ws(lib.scamd_spectral_embedding_workspace_bytes(n, a.nnz, dim))
+    rc = lib.scamd_spectral_embedding_f32(_p(indptr), _p(indices), _p(w), n, a.nnz, dim, int(seed), float(tol), int(max_outer),
+                                          int(max_degree), _p(out), info.ctypes.data_as(C.POINTER(C.c_double)), _p(ws), ws.size, None)
+    _check(lib, rc, "spectral_embedding")
+    return out, {"outer_iterations": int(info[0]), "operator_applications": int(info[1]), "residual": float(info[2]),
+                 "converged": bool(info[3] > 0.5), "ritz_values": [float(info[4 + j]) for j in range(min(dim, 4))]}, info
 
 
 def csr_gram(lib, x, scale_bits=None):

@@ -86,16 +86,6 @@ def test_eigh_topk(K, g, k):
     assert np.abs(v.T @ v - np.eye(k)).max() < 1e-10
 
 
-def test_eigh_topk_unsupported_shapes(K):
-    from scanpy_amd._lib import ScamdError
-
-    a = _dev(np.eye(150))
-    with pytest.raises(ScamdError):
-        K.eigh_topk(a, 50)  # 128 < g < 2 * block (block = k + 32 rounded up to 16 = 96)
-    with pytest.raises(ScamdError):
-        K.eigh_topk(_dev(np.eye(1000)), 110)  # k beyond the block
-
-
 @pytest.mark.parametrize("zero_center", [True, False])
 def test_pca_csr_entry_vs_sklearn(K, zero_center):
     """`scamd_pca_csr_f32` (one C call) against the reference's own sklearn call on the planted synthetic matrix"""
