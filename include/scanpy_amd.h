@@ -230,7 +230,9 @@ int scamd_eigh_topk_f64(const double* a, int64_t g, int64_t lda, int k, uint64_t
 /* Building blocks of the above on caller buffers (tests): op 1: out0[m x n] = in0^T in1 with in0 [kdim x m], in1 [kdim x n];
  * op 2: out0[m x m] = CholeskyQR factor S of the Gram matrix in0 [m x m] (Z S orthonormal when in0 = Z^T Z), *flag_host =
  * 1 on a non-positive pivot; op 3: out0[m] = eigenvalues (descending), out1[m x m] = eigenvectors (columns) of the
- * symmetric PSD in0 [m x m], *flag_host = Jacobi sweeps.  m <= 128 for ops 2 and 3. */
+ * symmetric PSD in0 [m x m], *flag_host = Jacobi sweeps.  m <= 128 for ops 2 and 3; op 4: out0[m x n] = in0 [m x kdim]
+ * in1 [kdim x n], the panel product (kdim, n <= 128, kdim <= n rounded up to a power of two that is at least 4); op 5: the same
+ * for two panels stacked in in0 [2 m x kdim] in one launch (out0, out1 [m x n]); op 6: op 3 on (in0 + in0^T) / 2, formed on load. */
 int scamd_dense_debug_f64(int op, const double* in0, const double* in1, int m, int n, int kdim, double* out0, double* out1,
                           int32_t* flag_host, scamd_stream_t stream);
 /* sc.pp.pca(svd_solver='arpack' accuracy) on a resident CSR float32 matrix in ONE call (the `pca_csr_f32` entry of the

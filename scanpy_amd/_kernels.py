@@ -324,7 +324,9 @@ def spmm_f64acc(indptr, indices, data, n_rows: int, b: torch.Tensor, scale: torc
 
 def dense_debug(op: int, in0: torch.Tensor, in1: torch.Tensor | None = None):
     """building blocks of the dense eigensolver on caller buffers (csrc/dense.hip; tests).  op 1: in0^T in1;
-    op 2: CholeskyQR factor of a Gram matrix -> (S, pivot_failed); op 3: Jacobi eigh -> (theta, Y, sweeps)."""
+    op 2: CholeskyQR factor of a Gram matrix -> (S, pivot_failed); op 3: Jacobi eigh -> (theta, Y, sweeps);
+    op 4: the panel product in0 [m, b] @ in1 [b, n] (b, n <= 128); op 5: two panels stacked in in0 [2 m, b] by the same in1 in one
+    launch -> (out0, out1); op 6: op 3 on the symmetrised in0, (in0 + in0^T) / 2 formed by the kernel's load."""
     dev = require_gpu()
     lib = _lib.load()
     in0 = in0.to(torch.float64).contiguous()
@@ -337,6 +339,22 @@ def dense_debug(op: int, in0: torch.Tensor, in1: torch.Tensor | None = None):
         rc = lib.scamd_dense_debug_f64(1, ptr(in0), ptr(in1), m, n, kdim, ptr(out), None, C.byref(flag), stream_ptr())
         _check(rc, "scamd_dense_debug_f64")
         return out
+    if op == 4:
+        in1 = in1.to(torch.float64).contiguous()
+        m, kdim = in0.shape
+        n = in1.shape[1]
+        out = _empty((m, n), dtype=torch.float64, device=dev)
+        rc = lib.scamd_dense_debug_f64(4, ptr(in0), ptr(in1), m, n, kdim, ptr(out), None, C.byref(flag), stream_ptr())
+        _check(rc, "scamd_dense_debug_f64")
+        return out
+    if op == 5:
+        in1 = in1.to(torch.float64).contiguous()
+        m, kdim = in0.shape[0] // 2, in0.shape[1]
+        n = in1.shape[1]
+        out0, out1 = (_empty((m, n), dtype=torch.float64, device=dev) for _ in range(2))
+        rc = lib.scamd_dense_debug_f64(5, ptr(in0), ptr(in1), m, n, kdim, ptr(out0), ptr(out1), C.byref(flag), stream_ptr())
+        _check(rc, "scamd_dense_debug_f64")
+        return out0, out1
     m = in0.shape[0]
     out0 = _empty((m, m) if op == 2 else (m,), dtype=torch.float64, device=dev)
     out1 = _empty((m, m), dtype=torch.float64, device=dev)

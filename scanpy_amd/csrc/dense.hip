@@ -36,6 +36,7 @@ using f64x4 = __attribute__((ext_vector_type(4))) double;
 constexpr int DB_MAX = 128;      // largest block size / Jacobi dimension
 constexpr int DB_LD = DB_MAX + 2;  // LDS column stride (doubles): 1040 B, not a multiple of the 256-B bank period
 constexpr int DENSE_BATCH_HOST = DB_MAX - 32;  // eigenpairs per batch of the deflated solve (dense_topk_batched)
+constexpr int GEMM_KB = 8;       // k-steps (of 4) whose operands a GEMM wave fetches in one batch
 
 __device__ __forceinline__ unsigned int dhash32(unsigned int x) {
   x ^= x >> 16;
@@ -100,20 +101,61 @@ __global__ __launch_bounds__(512) void dgemm_tn_kernel(const double* __restrict_
       for (int v = 0; v < 4; ++v) acc[a][b][v] = 0.0;
   const bool mv0 = m0 + l15 < M, mv1 = m0 + 16 + l15 < M;
   const bool nv0 = n0 + l15 < N, nv1 = n0 + 16 + l15 < N;
-  const double* pp = P + m0 + l15;
-  const double* qq = Q + n0 + l15;
-#pragma unroll 4
-  for (int k0 = kb; k0 < ke; k0 += 4) {
-    const int kk = k0 + kq;
-    const bool kv = kk < ke;
-    const double a0 = (kv && mv0) ? pp[(int64_t)kk * ldp] : 0.0;
-    const double a1 = (kv && mv1) ? pp[(int64_t)kk * ldp + 16] : 0.0;
-    const double b0 = (kv && nv0) ? qq[(int64_t)kk * ldq] : 0.0;
-    const double b1 = (kv && nv1) ? qq[(int64_t)kk * ldq + 16] : 0.0;
-    acc[0][0] = __builtin_amdgcn_mfma_f64_16x16x4f64(a0, b0, acc[0][0], 0, 0, 0);
-    acc[0][1] = __builtin_amdgcn_mfma_f64_16x16x4f64(a0, b1, acc[0][1], 0, 0, 0);
-    acc[1][0] = __builtin_amdgcn_mfma_f64_16x16x4f64(a1, b0, acc[1][0], 0, 0, 0);
-    acc[1][1] = __builtin_amdgcn_mfma_f64_16x16x4f64(a1, b1, acc[1][1], 0, 0, 0);
+  // Every load is unconditional, on an address clamped into the matrix; a lane outside the tile or the K range gets its zero
+  // where the operand is USED.  The raw operands of GEMM_KB k-steps are fetched together and the next batch is requested before
+  // this one is consumed: K / 32 / GEMM_KB memory round trips per wave instead of K / 32 (one load per wait).
+  const double* pp0 = P + min(m0 + l15, M - 1);
+  const double* pp1 = P + min(m0 + 16 + l15, M - 1);
+  const double* qq0 = Q + min(n0 + l15, N - 1);
+  const double* qq1 = Q + min(n0 + 16 + l15, N - 1);
+  const int nsteps = ke > kb ? (ke - kb + 3) >> 2 : 0;
+  double ca0[GEMM_KB], ca1[GEMM_KB], cb0[GEMM_KB], cb1[GEMM_KB];
+  double na0[GEMM_KB], na1[GEMM_KB], nb0[GEMM_KB], nb1[GEMM_KB];
+  if (nsteps > 0) {
+#pragma unroll
+    for (int j = 0; j < GEMM_KB; ++j) {
+      const int64_t kk = min(kb + 4 * j + kq, K - 1);
+      ca0[j] = pp0[kk * ldp];
+      ca1[j] = pp1[kk * ldp];
+      cb0[j] = qq0[kk * ldq];
+      cb1[j] = qq1[kk * ldq];
+    }
+  }
+  for (int s0 = 0; s0 < nsteps; s0 += GEMM_KB) {
+    const bool more = s0 + GEMM_KB < nsteps;
+    if (more) {
+#pragma unroll
+      for (int j = 0; j < GEMM_KB; ++j) {
+        const int64_t kk = min(kb + 4 * (s0 + GEMM_KB + j) + kq, K - 1);
+        na0[j] = pp0[kk * ldp];
+        na1[j] = pp1[kk * ldp];
+        nb0[j] = qq0[kk * ldq];
+        nb1[j] = qq1[kk * ldq];
+      }
+    }
+#pragma unroll
+    for (int j = 0; j < GEMM_KB; ++j) {
+      if (s0 + j < nsteps) {  // (uniform; a skipped step adds nothing, not a zero: the sums keep their bits)
+        const bool kv = kb + 4 * (s0 + j) + kq < ke;
+        const double a0 = (kv && mv0) ? ca0[j] : 0.0;
+        const double a1 = (kv && mv1) ? ca1[j] : 0.0;
+        const double b0 = (kv && nv0) ? cb0[j] : 0.0;
+        const double b1 = (kv && nv1) ? cb1[j] : 0.0;
+        acc[0][0] = __builtin_amdgcn_mfma_f64_16x16x4f64(a0, b0, acc[0][0], 0, 0, 0);
+        acc[0][1] = __builtin_amdgcn_mfma_f64_16x16x4f64(a0, b1, acc[0][1], 0, 0, 0);
+        acc[1][0] = __builtin_amdgcn_mfma_f64_16x16x4f64(a1, b0, acc[1][0], 0, 0, 0);
+        acc[1][1] = __builtin_amdgcn_mfma_f64_16x16x4f64(a1, b1, acc[1][1], 0, 0, 0);
+      }
+    }
+    if (more) {
+#pragma unroll
+      for (int j = 0; j < GEMM_KB; ++j) {
+        ca0[j] = na0[j];
+        ca1[j] = na1[j];
+        cb0[j] = nb0[j];
+        cb1[j] = nb1[j];
+      }
+    }
   }
 #pragma unroll
   for (int a = 0; a < 2; ++a)
@@ -173,24 +215,46 @@ __global__ __launch_bounds__(1024) void chol_factor_kernel(const double* __restr
   }
   __syncthreads();
   // left-looking Cholesky, column j from the finished columns: L[i][j] = (A[i][j] - sum_{k<j} L[i][k] L[j][k]) / L[j][j];
-  // the dot products of all rows i >= j run at once, eight lanes each (reduced through DPP)
+  // the dot products of all rows i >= j run at once, eight lanes each (reduced through DPP).  A lane reads four elements of
+  // either row per wait (index clamped to k < j, the term dropped where it is not part of the sum) and adds them in the order k = part,
+  // part + 8, ... as a one-read-per-wait loop would.
   bool bad = false;
-  __shared__ double sh_piv[2];
+  __shared__ double sh_piv[2], sh_root[2];
   for (int j = 0; j < b; ++j) {
     double acc = 0.0;
     const bool mine = row >= j && row < b;
-    if (mine)
-      for (int k = part; k < j; k += 8) acc = fma(L[row * DB_LD + k], L[j * DB_LD + k], acc);
+    double ljj = 0.0;
+    if (mine) {
+      const double* lr = L + row * DB_LD;
+      const double* lj = L + j * DB_LD;
+      ljj = lr[j];
+      for (int k0 = part; k0 < j; k0 += 32) {
+        double x[4], y[4];
+#pragma unroll
+        for (int t = 0; t < 4; ++t) {
+          const int kk = min(k0 + 8 * t, j - 1);  // (inside the finished columns: nothing this step writes is read)
+          x[t] = lr[kk];
+          y[t] = lj[kk];
+        }
+#pragma unroll
+        for (int t = 0; t < 4; ++t)
+          if (k0 + 8 * t < j) acc = fma(x[t], y[t], acc);
+      }
+    }
     acc = oct_sum(acc);
-    const double v = mine ? L[row * DB_LD + j] - acc : 0.0;
-    if (row == j && part == 0) sh_piv[j & 1] = v;
+    const double v = mine ? ljj - acc : 0.0;
+    if (row == j && part == 0) {  // the pivot's owner takes its root once, for everybody
+      sh_piv[j & 1] = v;
+      sh_root[j & 1] = sqrt(v);
+    }
     __syncthreads();
     const double piv = sh_piv[j & 1];
     if (!(piv > 0.0)) {  // uniform: every thread reads the same pivot
       bad = true;
       break;
     }
-    if (mine && part == 0) L[row * DB_LD + j] = (row == j) ? sqrt(piv) : v / sqrt(piv);
+    const double root = sh_root[j & 1];
+    if (mine && part == 0) L[row * DB_LD + j] = (row == j) ? root : v / root;
     __syncthreads();  // column j is final before the next column's dot products read it
   }
   if (tid == 0) *flag = bad ? 1 : 0;  // (written either way: no clear in front of the launch)
@@ -202,13 +266,28 @@ __global__ __launch_bounds__(1024) void chol_factor_kernel(const double* __restr
     const int c = row;
     const double xcc = c < b ? 1.0 / L[c * DB_LD + c] : 0.0;
     for (int j = 1; j < b; ++j) {
-      double acc = 0.0;
+      double acc = 0.0, pivot = 1.0;
       if (c < j) {
-        for (int k = c + 1 + part; k < j; k += 8) acc = fma(L[j * DB_LD + k], L[c * DB_LD + k], acc);
-        if (part == 0) acc = fma(L[j * DB_LD + c], xcc, acc);
+        const double* lj = L + j * DB_LD;
+        const double* lc = L + c * DB_LD;
+        const double ljc = lj[c], ljj = lj[j];
+        for (int k0 = c + 1 + part; k0 < j; k0 += 32) {
+          double x[4], y[4];
+#pragma unroll
+          for (int t = 0; t < 4; ++t) {
+            const int kk = min(k0 + 8 * t, j - 1);  // (never L[c][j], which this step writes)
+            x[t] = lj[kk];
+            y[t] = lc[kk];
+          }
+#pragma unroll
+          for (int t = 0; t < 4; ++t)
+            if (k0 + 8 * t < j) acc = fma(x[t], y[t], acc);
+        }
+        if (part == 0) acc = fma(ljc, xcc, acc);
+        pivot = ljj;
       }
       acc = oct_sum(acc);
-      if (c < j && part == 0) L[c * DB_LD + j] = -acc / L[j * DB_LD + j];
+      if (c < j && part == 0) L[c * DB_LD + j] = -acc / pivot;
       __syncthreads();
     }
   }
@@ -222,30 +301,95 @@ __global__ __launch_bounds__(1024) void chol_factor_kernel(const double* __restr
   }
 }
 
-// C[g x b] = Z[g x b] S[b x b] (plain FMA: O(g b^2), 1/16 of a GEMM application); 256 threads = 8 rows x 32 column quads
-__global__ __launch_bounds__(256) void panel_small_kernel(const double* __restrict__ Z, const double* __restrict__ S, int g,
-                                                          int b, int bo /* columns of S / C */, double* __restrict__ C) {
-  __shared__ double zrow[8][DB_MAX];
-  const int r = threadIdx.x >> 5, cq = threadIdx.x & 31;
-  const int m = blockIdx.x * 8 + r;
-  for (int k = cq; k < b; k += 32) zrow[r][k] = (m < g) ? Z[(int64_t)m * b + k] : 0.0;
-  __syncthreads();
-  if (m >= g) return;
-  for (int n0 = cq * 4; n0 < bo; n0 += 128) {
-    double c0 = 0.0, c1 = 0.0, c2 = 0.0, c3 = 0.0;
-    for (int k = 0; k < b; ++k) {
-      const double z = zrow[r][k];
-      const double* sp = S + (int64_t)k * bo + n0;
-      c0 = fma(z, sp[0], c0);
-      if (n0 + 1 < bo) c1 = fma(z, sp[1], c1);
-      if (n0 + 2 < bo) c2 = fma(z, sp[2], c2);
-      if (n0 + 3 < bo) c3 = fma(z, sp[3], c3);
+// C[g x bo] = Z[g x b] S[b x bo] (plain FMA: O(g b^2), 1/16 of a GEMM application), and with gridDim.y = 2 a second panel by the
+// same S (C1 = Z1 S: the two products of a Rayleigh-Ritz).  S is staged in LDS ONCE per workgroup, row stride W = 4 << cq_shift
+// >= bo with zeros beyond bo, by loads issued PANEL_SB at a time with the next batch requested before this one is stored; the k
+// loop then reads LDS only (it read S from global memory behind three bounds guards, one L2 round trip per k).  256 threads =
+// (256 >> cq_shift) row groups x (1 << cq_shift) column quads, two rows per thread: 16 rows per workgroup at bo = 128, 256 at
+// bo = 8 (the spectral caller: 1M rows, where 8 rows per workgroup left 16 of 256 threads with work).  Every output element is
+// still fma(z_k, s_k, c) over k = 0 .. b-1 from c = 0.  Needs b <= W (the Z tile is sized for it) and bo <= DB_MAX.
+constexpr int PANEL_SB = 8;  // S elements per thread and batch
+constexpr int panel_lds_doubles(int b, int cq_shift) {
+  return b * (4 << cq_shift) + 2 * (256 >> cq_shift) * (b | 1);
+}
+__global__ __launch_bounds__(256) void panel_small_kernel(const double* __restrict__ Z0, const double* __restrict__ Z1,
+                                                          const double* __restrict__ S, int g, int b, int bo, int cq_shift,
+                                                          double* __restrict__ C0, double* __restrict__ C1) {
+  extern __shared__ __attribute__((aligned(16))) double sm[];  // S [b][W], then the Z rows [rows][zld]
+  const int tid = threadIdx.x;
+  const int W = 4 << cq_shift, rpp = 256 >> cq_shift, rows = 2 * rpp;
+  const int zld = b | 1;  // odd: the row groups of a wave read different banks
+  double* Ss = sm;
+  double* Zs = sm + b * W;
+  const double* __restrict__ Z = blockIdx.y ? Z1 : Z0;
+  double* __restrict__ C = blockIdx.y ? C1 : C0;
+  const int m0 = blockIdx.x * rows;
+  // the Z rows of this workgroup: contiguous in memory, rows * b <= 2048 elements, one batch
+  {
+    double zv[8];
+    const int zcount = rows * b;
+    const int64_t zlast = (int64_t)g * b - 1;
+#pragma unroll
+    for (int u = 0; u < 8; ++u) zv[u] = Z[min((int64_t)m0 * b + tid + 256 * u, zlast)];
+    const int scount = b * W;
+    const int wmask = W - 1, wshift = cq_shift + 2;
+    double cur[PANEL_SB], nxt[PANEL_SB];
+#pragma unroll
+    for (int u = 0; u < PANEL_SB; ++u) {
+      const int e = tid + 256 * u;
+      cur[u] = S[min(e >> wshift, b - 1) * bo + min(e & wmask, bo - 1)];
     }
-    double* cp = C + (int64_t)m * bo + n0;
-    cp[0] = c0;
-    if (n0 + 1 < bo) cp[1] = c1;
-    if (n0 + 2 < bo) cp[2] = c2;
-    if (n0 + 3 < bo) cp[3] = c3;
+#pragma unroll
+    for (int u = 0; u < 8; ++u) {
+      const int e = tid + 256 * u;
+      if (e < zcount) {
+        const int r = e / b;
+        Zs[r * zld + (e - r * b)] = (m0 + r < g) ? zv[u] : 0.0;
+      }
+    }
+    for (int e0 = 0; e0 < scount; e0 += 256 * PANEL_SB) {
+      const bool more = e0 + 256 * PANEL_SB < scount;
+      if (more) {
+#pragma unroll
+        for (int u = 0; u < PANEL_SB; ++u) {
+          const int e = e0 + 256 * PANEL_SB + tid + 256 * u;
+          nxt[u] = S[min(e >> wshift, b - 1) * bo + min(e & wmask, bo - 1)];
+        }
+      }
+#pragma unroll
+      for (int u = 0; u < PANEL_SB; ++u) {
+        const int e = e0 + tid + 256 * u;
+        if (e < scount) Ss[e] = ((e & wmask) < bo) ? cur[u] : 0.0;
+      }
+      if (more) {
+#pragma unroll
+        for (int u = 0; u < PANEL_SB; ++u) cur[u] = nxt[u];
+      }
+    }
+  }
+  __syncthreads();
+  const int cq = tid & ((1 << cq_shift) - 1), rg = tid >> cq_shift;
+  const double* sp = Ss + 4 * cq;
+  const double* z0 = Zs + rg * zld;
+  const double* z1 = Zs + (rg + rpp) * zld;
+  double c0[4] = {0.0, 0.0, 0.0, 0.0}, c1[4] = {0.0, 0.0, 0.0, 0.0};
+#pragma unroll 8
+  for (int k = 0; k < b; ++k) {
+    const double za = z0[k], zb = z1[k];
+#pragma unroll
+    for (int j = 0; j < 4; ++j) {
+      const double sv = sp[k * W + j];
+      c0[j] = fma(za, sv, c0[j]);
+      c1[j] = fma(zb, sv, c1[j]);
+    }
+  }
+  const int n0 = 4 * cq;
+#pragma unroll
+  for (int j = 0; j < 4; ++j) {
+    if (n0 + j < bo) {
+      if (m0 + rg < g) C[(int64_t)(m0 + rg) * bo + n0 + j] = c0[j];
+      if (m0 + rg + rpp < g) C[(int64_t)(m0 + rg + rpp) * bo + n0 + j] = c1[j];
+    }
   }
 }
 
@@ -255,25 +399,18 @@ __global__ __launch_bounds__(256) void panel_small_kernel(const double* __restri
 // theta_i y_i.  64 disjoint pairs per step (round-robin tournament), 8 lanes per pair.  Output: theta[b] descending by
 // |theta| (the sign is recovered from y^T T y = sign * |W_i|), Y [b x b] row-major, column j = eigenvector j.
 // ---------------------------------------------------------------------------------------------------------------------
-__global__ __launch_bounds__(512) void jacobi_eigh_kernel(const double* __restrict__ T, int b, double* __restrict__ theta,
-                                                          double* __restrict__ Y, int* __restrict__ sweeps_out) {
-  extern __shared__ __attribute__((aligned(16))) double sm[];  // W [n2][DB_LD] column-major: W[c * DB_LD + i]
-  double* W = sm;
-  double* nrm = sm + DB_MAX * DB_LD;  // [DB_MAX]
-  __shared__ float off_arr[64];  // per group: largest |cos| between two columns it met in the sweep
-  __shared__ int rank_of[DB_MAX];
-  const int tid = threadIdx.x;
-  const int n2 = (b + 1) & ~1;  // even number of players (a padding column of zeros never rotates)
-  for (int e = tid; e < n2 * DB_LD; e += 512) {
-    const int c = e / DB_LD, i = e - c * DB_LD;
-    W[e] = (c < b && i < b) ? T[(int64_t)i * b + c] : 0.0;
-  }
-  __syncthreads();
+// The sweeps of the kernel below for b in (8 NJ - 8, 8 NJ]: a lane holds its NJ elements of both columns of its pair in
+// registers for the whole step -- every LDS read of the step is issued at once, the three dot products and the rotation work on
+// registers, the rotated values are written back (a loop over b read two elements per wait, twice per step, 2 x b / 8 serial LDS
+// round trips).  Only the last element of a lane can lie beyond b; its terms are left out of the sums, as before.
+template <int NJ>
+__device__ __forceinline__ int jacobi_sweeps(double* W, float* off_arr, int b, int n2, int tid) {
   // 64 groups of 8 lanes, one column pair each.  The kernel is bound by the instruction THROUGHPUT of its one CU (every
   // lane of a group repeats the rotation's scalar arithmetic): eight lanes per pair instead of sixteen halves the
   // redundant work per SIMD, the rotation is computed with two rsqrt and no division, the reductions run on DPP.
   const int grp = tid >> 3, t8 = tid & 7;
   const int nm1 = n2 - 1;
+  const bool last_in = t8 + 8 * (NJ - 1) < b;
   int sweep = 0;
   for (; sweep < 30; ++sweep) {
     float my_off = 0.f;  // (no shared counter inside the step loop: 64 same-address LDS atomics per step serialise)
@@ -283,14 +420,22 @@ __global__ __launch_bounds__(512) void jacobi_eigh_kernel(const double* __restri
     for (int step = 0; step < nm1; ++step) {
       const bool act = grp < n2 / 2 && p < b && q < b;
       if (act) {
-        double* wp = W + p * DB_LD;
-        double* wq = W + q * DB_LD;
+        double* wp = W + p * DB_LD + t8;
+        double* wq = W + q * DB_LD + t8;
+        double x[NJ], y[NJ];
+#pragma unroll
+        for (int j = 0; j < NJ; ++j) {  // (t8 + 8 j < 8 NJ <= DB_MAX < DB_LD: inside the column)
+          x[j] = wp[8 * j];
+          y[j] = wq[8 * j];
+        }
         double a = 0.0, bb = 0.0, c = 0.0;
-        for (int i = t8; i < b; i += 8) {
-          const double x = wp[i], y = wq[i];
-          a = fma(x, x, a);
-          bb = fma(y, y, bb);
-          c = fma(x, y, c);
+#pragma unroll
+        for (int j = 0; j < NJ; ++j) {
+          if (j < NJ - 1 || last_in) {
+            a = fma(x[j], x[j], a);
+            bb = fma(y[j], y[j], bb);
+            c = fma(x[j], y[j], c);
+          }
         }
         a = oct_sum(a);
         bb = oct_sum(bb);
@@ -304,10 +449,12 @@ __global__ __launch_bounds__(512) void jacobi_eigh_kernel(const double* __restri
           const double inv_cs = rsqrt(h);
           const double cs = h * inv_cs;
           const double sn = (d >= 0.0 ? 0.5 : -0.5) * tau * inv_r * inv_cs;
-          for (int i = t8; i < b; i += 8) {
-            const double x = wp[i], y = wq[i];
-            wp[i] = cs * x - sn * y;
-            wq[i] = sn * x + cs * y;
+#pragma unroll
+          for (int j = 0; j < NJ; ++j) {
+            if (j < NJ - 1 || last_in) {
+              wp[8 * j] = cs * x[j] - sn * y[j];
+              wq[8 * j] = sn * x[j] + cs * y[j];
+            }
           }
           my_off = fmaxf(my_off, (float)(fabs(c) * rsqrt(ab)));
         }
@@ -333,9 +480,55 @@ __global__ __launch_bounds__(512) void jacobi_eigh_kernel(const double* __restri
       break;
     }
   }
+  return sweep;
+}
+
+// `symmetrize`: W is loaded as (T + T^T) / 2 (the Rayleigh-Ritz matrix is symmetric up to rounding; a launch of its own did this)
+__global__ __launch_bounds__(512) void jacobi_eigh_kernel(const double* __restrict__ T, int b, int symmetrize,
+                                                          double* __restrict__ theta, double* __restrict__ Y,
+                                                          int* __restrict__ sweeps_out) {
+  extern __shared__ __attribute__((aligned(16))) double sm[];  // W [n2][DB_LD] column-major: W[c * DB_LD + i]
+  double* W = sm;
+  double* nrm = sm + DB_MAX * DB_LD;  // [DB_MAX]
+  __shared__ float off_arr[64];  // per group: largest |cos| between two columns it met in the sweep
+  __shared__ int rank_of[DB_MAX];
+  const int tid = threadIdx.x;
+  const int n2 = (b + 1) & ~1;  // even number of players (a padding column of zeros never rotates)
+  for (int e0 = tid; e0 < n2 * DB_LD; e0 += 512 * 4) {  // (four elements per wait, clamped addresses)
+    double t1[4], t2[4];
+#pragma unroll
+    for (int u = 0; u < 4; ++u) {
+      const int e = e0 + 512 * u;
+      const int c = min(e / DB_LD, b - 1), i = min(e % DB_LD, b - 1);
+      t1[u] = T[(int64_t)i * b + c];
+      t2[u] = T[(int64_t)(symmetrize ? c : i) * b + (symmetrize ? i : c)];
+    }
+#pragma unroll
+    for (int u = 0; u < 4; ++u) {
+      const int e = e0 + 512 * u;
+      const int c = e / DB_LD, i = e - c * DB_LD;
+      if (e < n2 * DB_LD) W[e] = (c < b && i < b) ? ((symmetrize && i != c) ? 0.5 * (t1[u] + t2[u]) : t1[u]) : 0.0;
+    }
+  }
+  __syncthreads();
+  const int grp = tid >> 3, t8 = tid & 7;
+  int sweep = 0;
+  // A compile-time element count per lane: the step is straight-line code on registers.  Sixteen instances make the kernel 43 KB
+  // of code; a launch runs ONE of them (2-3 KB of loop: 11 elements at b = 82, 1 at the spectral b = 8), so the instruction
+  // cache holds what runs.  b > DB_MAX has no instance and no room in LDS: the entry points refuse it before the launch.
+  switch ((b + 7) >> 3) {
+#define SCAMD_JACOBI_CASE(NJ) case NJ: sweep = jacobi_sweeps<NJ>(W, off_arr, b, n2, tid); break;
+    SCAMD_JACOBI_CASE(1) SCAMD_JACOBI_CASE(2) SCAMD_JACOBI_CASE(3) SCAMD_JACOBI_CASE(4)
+    SCAMD_JACOBI_CASE(5) SCAMD_JACOBI_CASE(6) SCAMD_JACOBI_CASE(7) SCAMD_JACOBI_CASE(8)
+    SCAMD_JACOBI_CASE(9) SCAMD_JACOBI_CASE(10) SCAMD_JACOBI_CASE(11) SCAMD_JACOBI_CASE(12)
+    SCAMD_JACOBI_CASE(13) SCAMD_JACOBI_CASE(14) SCAMD_JACOBI_CASE(15) SCAMD_JACOBI_CASE(16)
+#undef SCAMD_JACOBI_CASE
+    default: break;
+  }
   // column norms, ranks (descending norm, ties by index)
   if (tid < n2) {
     double a = 0.0;
+#pragma unroll 8
     for (int i = 0; i < b; ++i) a = fma(W[tid * DB_LD + i], W[tid * DB_LD + i], a);
     nrm[tid] = tid < b ? sqrt(a) : -1.0;
   }
@@ -377,18 +570,6 @@ __global__ void axpby_kernel(int64_t count, double a, const double* __restrict__
                              const double* __restrict__ x2, double* __restrict__ y) {
   const int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
   if (i < count) y[i] = a * x1[i] + b * x2[i];
-}
-
-// T <- (T + T^T) / 2 in place (b x b)
-__global__ void symmetrize_kernel(double* __restrict__ t, int b) {
-  const int e = blockIdx.x * blockDim.x + threadIdx.x;
-  if (e >= b * b) return;
-  const int i = e / b, j = e - i * b;
-  if (j > i) {
-    const double v = 0.5 * (t[(int64_t)i * b + j] + t[(int64_t)j * b + i]);
-    t[(int64_t)i * b + j] = v;
-    t[(int64_t)j * b + i] = v;
-  }
 }
 
 // Rayleigh quotients t_j = z_j^T (A z_j) of an orthonormal block: out[1] = min_j t_j, out[2] = max_j t_j (one workgroup)
@@ -773,7 +954,10 @@ extern "C" int scamd_eigh_topk_f64(const double* a, int64_t g, int64_t lda, int 
 }
 
 // debug / test entry: the building blocks on caller buffers.  op 1: C[M x N] = P^T Q (P [K x M], Q [K x N]);
-// op 2: S = CholeskyQR factor of G [b x b] (flag_host = pivot failure); op 3: (theta, Y) = eigh(T [b x b]).
+// op 2: S = CholeskyQR factor of G [b x b] (flag_host = pivot failure); op 3: (theta, Y) = eigh(T [b x b]);
+// op 4: C[M x N] = Z S (Z [M x kdim], S [kdim x N], kdim and N up to 128): the panel product; op 5: the same for the two
+// panels stacked in in0 [2 M x kdim] in ONE launch (out0, out1), as a Rayleigh-Ritz does; op 6: op 3 on (T + T^T) / 2, formed
+// while the kernel loads T.
 extern "C" int scamd_dense_debug_f64(int op, const double* in0, const double* in1, int m, int n, int kdim, double* out0,
                                      double* out1, int32_t* flag_host, scamd_stream_t stream) {
   SCAMD_REQUIRE(in0 && out0, SCAMD_EINVAL, "dense_debug: null pointer");
@@ -781,7 +965,7 @@ extern "C" int scamd_dense_debug_f64(int op, const double* in0, const double* in
     SCAMD_REQUIRE(in1, SCAMD_EINVAL, "dense_debug: null pointer");
     int rc = dgemm_tn(stream, in0, m, in1, n, m, n, kdim, 1.0, nullptr, 0, 0.0, nullptr, 0, 0.0, out0, n);
     if (rc != SCAMD_OK) return rc;
-  } else if (op == 2 || op == 3) {
+  } else if (op == 2 || op == 3 || op == 6) {
     const int b = m;
     SCAMD_REQUIRE(b >= 1 && b <= DB_MAX, SCAMD_EINVAL, "dense_debug: b=%d", b);
     int* dflag = nullptr;
@@ -793,7 +977,7 @@ extern "C" int scamd_dense_debug_f64(int op, const double* in0, const double* in
       hipLaunchKernelGGL(chol_factor_kernel, dim3(1), dim3(1024), CHOL_LDS, stream, in0, b, 0.0, out0, dflag);
     } else {
       SCAMD_REQUIRE(out1, SCAMD_EINVAL, "dense_debug: null pointer");
-      hipLaunchKernelGGL(jacobi_eigh_kernel, dim3(1), dim3(512), JAC_LDS, stream, in0, b, out0, out1, dflag + 1);
+      hipLaunchKernelGGL(jacobi_eigh_kernel, dim3(1), dim3(512), JAC_LDS, stream, in0, b, op == 6 ? 1 : 0, out0, out1, dflag + 1);
     }
     SCAMD_LAUNCH_CHECK();
     int h[2] = {0, 0};
@@ -802,6 +986,12 @@ extern "C" int scamd_dense_debug_f64(int op, const double* in0, const double* in
     SCAMD_HIP_CHECK(hipFree(dflag));
     if (flag_host) *flag_host = op == 2 ? h[0] : h[1];
     return SCAMD_OK;
+  } else if (op == 4 || op == 5) {  // out0 [m x n] = in0 [m x kdim] in1 [kdim x n]; op 5: and out1 = (in0 + m kdim) in1, same launch
+    SCAMD_REQUIRE(in1 && (op == 4 || out1), SCAMD_EINVAL, "dense_debug: null pointer");
+    int rc = prepare_lds_kernels();
+    if (rc != SCAMD_OK) return rc;
+    rc = panel_small(stream, in0, op == 5 ? in0 + (int64_t)m * kdim : nullptr, in1, m, kdim, n, out0, op == 5 ? out1 : nullptr);
+    if (rc != SCAMD_OK) return rc;
   } else {
     SCAMD_REQUIRE(false, SCAMD_EINVAL, "dense_debug: op=%d", op);
   }

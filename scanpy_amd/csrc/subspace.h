@@ -6,7 +6,7 @@
 // rules and degenerate-block steps differ, and a shared loop would need a hook for each.
 //
 // Included by dense.hip AFTER the kernels these steps launch (chol_factor_kernel, panel_small_kernel, jacobi_eigh_kernel,
-// symmetrize_kernel, axpby_kernel); it is not a stand-alone header.
+// axpby_kernel); it is not a stand-alone header.
 //
 // An operator `Op` has
 //   int64_t rows() const        rows of a panel (panels are rows x b, row-major)
@@ -31,13 +31,16 @@ struct SubspaceScratch {
 
 static constexpr size_t CHOL_LDS = (size_t)(DB_MAX * DB_LD + DB_MAX) * sizeof(double);
 static constexpr size_t JAC_LDS = (size_t)(DB_MAX * DB_LD + DB_MAX) * sizeof(double);
+static constexpr size_t PANEL_LDS_MAX = (size_t)panel_lds_doubles(DB_MAX, 5) * sizeof(double);
 
-// the two LDS-resident kernels take more dynamic LDS than the default limit: once per entry, before the first launch
+// the LDS-resident kernels take more dynamic LDS than the default limit: once per entry, before the first launch
 static int prepare_lds_kernels() {
   SCAMD_HIP_CHECK(hipFuncSetAttribute(reinterpret_cast<const void*>(chol_factor_kernel),
                                       hipFuncAttributeMaxDynamicSharedMemorySize, (int)CHOL_LDS));
   SCAMD_HIP_CHECK(hipFuncSetAttribute(reinterpret_cast<const void*>(jacobi_eigh_kernel),
                                       hipFuncAttributeMaxDynamicSharedMemorySize, (int)JAC_LDS));
+  SCAMD_HIP_CHECK(hipFuncSetAttribute(reinterpret_cast<const void*>(panel_small_kernel),
+                                      hipFuncAttributeMaxDynamicSharedMemorySize, (int)PANEL_LDS_MAX));
   return SCAMD_OK;
 }
 
@@ -46,12 +49,22 @@ static unsigned int eigensolver_seed(uint64_t seed, unsigned int salt) {
   return (unsigned int)(seed ^ (seed >> 32)) * 0x9E3779B1u + salt;
 }
 
-template <class Op>
-static int panel_times_small(Op& op, const double* z, const double* small, double* out) {
-  hipLaunchKernelGGL(panel_small_kernel, dim3((unsigned)((op.rows() + 7) / 8)), dim3(256), 0, op.s, z, small, (int)op.rows(), op.b,
-                     op.b, out);
+// c0 [rows x bo] = z0 [rows x b] small [b x bo]; with z1: also c1 = z1 small, in the same launch (after prepare_lds_kernels)
+static int panel_small(hipStream_t s, const double* z0, const double* z1, const double* small, int64_t rows, int b, int bo,
+                       double* c0, double* c1) {
+  int cq_shift = 0;
+  while ((4 << cq_shift) < bo) ++cq_shift;  // column quads per row group, a power of two
+  SCAMD_REQUIRE(rows >= 1 && rows < ((int64_t)1 << 31) && b >= 1 && bo >= 1 && bo <= DB_MAX && b <= (4 << cq_shift), SCAMD_EINVAL,
+                "panel product: bad shape rows=%lld b=%d bo=%d", (long long)rows, b, bo);
+  const int rows_per = 2 * (256 >> cq_shift);
+  hipLaunchKernelGGL(panel_small_kernel, dim3((unsigned)((rows + rows_per - 1) / rows_per), z1 ? 2 : 1), dim3(256),
+                     (size_t)panel_lds_doubles(b, cq_shift) * sizeof(double), s, z0, z1, small, (int)rows, b, bo, cq_shift, c0, c1);
   SCAMD_LAUNCH_CHECK();
   return SCAMD_OK;
+}
+template <class Op>
+static int panel_times_small(Op& op, const double* z, const double* small, double* out) {
+  return panel_small(op.s, z, nullptr, small, op.rows(), op.b, op.b, out, nullptr);
 }
 
 // zout = orthonormal basis of span(zin) by CholeskyQR2: `plain_rounds` rounds of (Gram matrix, Cholesky factor, block times
@@ -110,13 +123,10 @@ static int rayleigh_ritz(Op& op, const double* z, double* az, double* v, double*
   if (rc != SCAMD_OK) return rc;
   rc = op.gram(z, b, az, b, op.w.tmat);
   if (rc != SCAMD_OK) return rc;
-  hipLaunchKernelGGL(symmetrize_kernel, dim3((b * b + 255) / 256), dim3(256), 0, op.s, op.w.tmat, b);
+  // (T is symmetrised as the Jacobi kernel loads it; v and av come out of one launch)
+  hipLaunchKernelGGL(jacobi_eigh_kernel, dim3(1), dim3(512), JAC_LDS, op.s, op.w.tmat, b, 1, op.w.theta, op.w.ymat, op.w.flags + 1);
   SCAMD_LAUNCH_CHECK();
-  hipLaunchKernelGGL(jacobi_eigh_kernel, dim3(1), dim3(512), JAC_LDS, op.s, op.w.tmat, b, op.w.theta, op.w.ymat, op.w.flags + 1);
-  SCAMD_LAUNCH_CHECK();
-  rc = panel_times_small(op, z, op.w.ymat, v);
-  if (rc != SCAMD_OK) return rc;
-  rc = panel_times_small(op, az, op.w.ymat, av);
+  rc = panel_small(op.s, z, az, op.w.ymat, op.rows(), b, b, v, av);
   if (rc != SCAMD_OK) return rc;
   SCAMD_READBACK(h_theta, op.w.theta, sizeof(double) * b, op.s);
   return SCAMD_OK;
