@@ -350,11 +350,17 @@ int scamd_leiden_csr_nw_f32(const int64_t* indptr, const int32_t* indices, const
  *       otherwise) ended an n_iterations < 0 run instead of convergence -- `tl.leiden` turns it into a UserWarning;
  *   device_fills: launches of the multi-region clear kernel;
  *   levels_reused / quiet_reuse_iterations: levels that took their coarse graph from the stored hierarchy / iterations that
- *       ran on it to its end without a move; overflow_pass_vertices / hub_pass_vertices: vertices the 64-lane overflow pass
- *       took over from a 16- / 32-lane decide launch / handed to the hub pass. */
+ *       ran on it to its end without a move; overflow_pass_vertices / hub_pass_vertices: rows too long for the main tier of
+ *       a 16- / 32-lane decide launch / rows longer than the wave table (block and giant tier together; see
+ *       scamd_leiden_tier_bounds). */
 void scamd_leiden_last_stats(int32_t* out, int n);
 /* Key of statistics slot `slot` (a static string); NULL for the unused slot 14 and outside [0, 20). */
 const char* scamd_leiden_stat_name(int slot);
+/* The longest rows the tiers of a Leiden decide step take when its main tier gives a vertex `lanes` (16, 32 or 64) lanes: up
+ * to *main_max entries the main tier, up to *wave_max a wave per row, up to *block_max a 256-thread workgroup per row inside
+ * the same launch, longer ones the 1024-thread launch of their own.  Read-only, no device needed; SCAMD_EINVAL for another
+ * `lanes`.  Read by the tests that build rows at these lengths (tests/leiden_tier_cases.py). */
+int scamd_leiden_tier_bounds(int lanes, int* main_max, int* wave_max, int* block_max);
 /* Test entry: the component split the polish applies after its moves -- every connected component (over the stored
  * entries) of a community of `membership` (ids in [0, n), device, rewritten in place) becomes a community of its own, id =
  * its smallest vertex; *n_split_host = components - communities (0: membership untouched).  Workspace:

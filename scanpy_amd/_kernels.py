@@ -518,6 +518,13 @@ def leiden_last_stats() -> dict:
     return {k: int(v) for k, v in zip(keys, out) if k is not None}
 
 
+def leiden_tier_bounds(lanes: int):
+    """longest rows (main_max, wave_max, block_max) of the tiers of a Leiden decide step at `lanes` lanes per vertex"""
+    a, b, c = C.c_int32(0), C.c_int32(0), C.c_int32(0)
+    _check(_lib.load().scamd_leiden_tier_bounds(int(lanes), C.byref(a), C.byref(b), C.byref(c)), "scamd_leiden_tier_bounds")
+    return a.value, b.value, c.value
+
+
 def modularity(indptr: torch.Tensor, indices: torch.Tensor, weights: torch.Tensor, n: int, membership: torch.Tensor,
                *, resolution: float = 1.0) -> float:
     dev = require_gpu()

@@ -41,9 +41,10 @@ namespace scamd {
 //   ST_LEVELS_REUSED               levels that took their coarse graph from the stored hierarchy (StoredLevel) instead of
 //                                   refining and aggregating
 //   ST_QUIET_REUSE_ITERS           iterations that ran on the stored hierarchy to its end without a move at any level
-//   ST_OVERFLOW_VERTICES / ST_HUB_VERTICES  vertices the 64-lane overflow pass took over from a 16- / 32-lane decide launch /
-//                                   handed to the hub pass (decide_tiers: local moving, polish and refinement together; the list
-//                                   builders' counts, so no read-back of their own)
+//   ST_OVERFLOW_VERTICES / ST_HUB_VERTICES  rows too long for the main tier of a 16- / 32-lane decide launch (the wave-per-row
+//                                   tier takes them, or a workgroup tier) / rows longer than the wave table: block tier and
+//                                   giant tier together (decide_tiers: local moving, polish and refinement together; the
+//                                   list builders' counts, so no read-back of their own)
 enum LdStat : int {
   ST_ITERATIONS = 0, ST_LAUNCHES, ST_ROUND_TRIPS, ST_POLISH_FULL_SWEEPS, ST_POLISH_ROUNDS, ST_POLISH_MOVES,
   ST_POLISH_SKIPPED_PROVEN, ST_LEVELS_FIRST_ITER, ST_LM_SWEEPS, ST_LM_SWEEP_MB, ST_POLISH_SPLITS, ST_ENDED_BY_ITER_CAP,
@@ -108,10 +109,10 @@ constexpr int LM_DIR_AFTER = 32;  // sweeps after which the direction rule (term
 constexpr int MAX_CLASSES = 32;   // most class sub-rounds per sweep (local moving) / per refinement
 constexpr int DEF_CLASSES = 8;    // default
 constexpr int CTR_STRIDE = 16;    // ints per sub-round counter block:
-// [CTR_JOINED] joiners of the sub-round (refinement); filled by the decide kernels: [CTR_HUB] rows handed to the hub kernel,
-// [CTR_OVF] rows handed to the 64-lane overflow pass; counted while the class lists are built (count_long_rows): [CTR_N_MID] /
-// [CTR_N_HUB] rows of the class longer than the lanes-per-vertex table / than the wave table
-constexpr int CTR_JOINED = 0, CTR_HUB = 4, CTR_OVF = 5, CTR_N_MID = 8, CTR_N_HUB = 9;
+// [CTR_JOINED] joiners of the sub-round (refinement); the lengths of the class's tier lists, counted while the class lists
+// are built (list_long_rows): [CTR_N_MID] rows of the wave-per-row tier (longer than the lanes-per-vertex table), [CTR_N_BLK] of
+// the block tier (longer than the wave table), [CTR_N_GIANT] of the giant tier (longer than the block tier's table)
+constexpr int CTR_JOINED = 0, CTR_N_MID = 8, CTR_N_BLK = 9, CTR_N_GIANT = 10;
 // Phase counters (LeidenBuffers::counters, 16 ints), by the phase that owns a slot.  Slots [0, PH_PER_PHASE) are cleared when a
 // phase begins (local_moving, polish_level0, refinement, aggregate / reuse_level: one after the other, never overlapping).
 // The component split runs INSIDE a polish pass and clears its own three slots only: it must leave PH_MOVED, PH_BLOCKED and
@@ -415,8 +416,9 @@ struct WaveHash {
 
 // ---- high-degree vertices: one workgroup per vertex, 8192-slot LDS table ---------------------------------
 // kNN graphs have hubs (in-degree in the thousands) and aggregated graphs are dense: the wave-per-vertex kernels
-// hand every vertex with more than WH_MAX_DEG neighbours to these block-per-vertex kernels (hub list filled
-// through counters[CTR_HUB]) instead of letting ONE wave grind through an O(deg^2) compare while the grid waits.
+// leave every vertex with more than WH_MAX_DEG neighbours to a workgroup per vertex (the block tier of the fused decide
+// launch up to BLK_MAX_DEG entries, these kernels beyond; lists written by list_long_rows) instead of letting ONE wave
+// grind through an O(deg^2) compare while the grid waits.
 constexpr int BHUB_SLOTS = 8192;
 constexpr int BHUB_MAX_DEG = 6000;  // longest row one pass of the table takes (load <= 0.73)
 // Longer rows (the coarse levels of a weakly clustered graph are nearly dense: 20k vertices with up to 18k
@@ -439,10 +441,11 @@ constexpr int HUB_TRY_PROBES = 64;
 struct BlockHash {
   int* keys;
   unsigned long long* vals;
-  int nslots;  // power of two >= 2 * deg (256 .. BHUB_SLOTS): clearing and scanning cost O(deg), not O(table)
+  int nslots;  // power of two >= 2 * deg (256 .. cap): clearing and scanning cost O(deg), not O(table)
+  int cap = BHUB_SLOTS;  // slots behind keys / vals (the block tier of the fused decide kernels: BLK_SLOTS)
   __device__ __forceinline__ void size_for(int deg) {
     int s = 256;
-    while (s < 2 * deg && s < BHUB_SLOTS) s <<= 1;
+    while (s < 2 * deg && s < cap) s <<= 1;
     nslots = s;
   }
   __device__ __forceinline__ void clear() {
@@ -516,12 +519,12 @@ __device__ __forceinline__ Cand block_best(Cand x, long long& w_own, Cand* sh_c,
 
 // G lanes per ACTIVE vertex (list[0..n_act)): decision[w] = community to move to, -1 = stay,
 // -2 = wants to move but the direction rule forbids it this round (stays active).
-//   G = 64: one wave per vertex, table of up to 512 slots (deg <= 384); hubs go to hub_list (counters[CTR_HUB]).
+//   G = 64: one wave per vertex, table of up to 512 slots (deg <= 384); longer rows are skipped: a workgroup tier has them.
 //   G = 16: FOUR vertices per wave, 128 slots each (deg <= 96) -- a kNN graph's rows are ~2k long, and the kernel
 //           is bound by its chain of dependent gathers (list -> indptr -> indices -> comm -> Ktot), so four
-//           vertices per wave put four times as many gathers in flight per wave slot.  Longer rows go to
-//           ovf_list (counters[CTR_OVF]) and are decided by the G = 64 instantiation in indirect mode
-//           (sub_list / sub_count = positions in `list`, grid-strided).
+//           vertices per wave put four times as many gathers in flight per wave slot.  Longer rows are
+//           skipped: the G = 64 instantiation decides them in indirect mode (sub_list = the class's wave-tier list:
+//           positions in `list`, grid-strided), or a workgroup tier.
 // THE move rule, shared by the wave and the hub kernel.  Score of moving v (weight kv) into community c, to which it has
 // weight `sum` and whose total is Kc:
 __device__ __forceinline__ Cand move_cand(int c, long long sum, unsigned long long Kc, double g, double kv, unsigned int seed) {
@@ -550,11 +553,24 @@ __device__ __forceinline__ int move_verdict(const Cand& best, long long w_own, d
   return (wants && allowed) ? target : (wants ? -2 : -1);
 }
 
+// The long rows of a class list, as its builder left them (list_long_rows), and how the fused decide launch divides its
+// workgroups among the tiers.  Entries are positions in the class list.
+struct TierLists {
+  const int* mid;       // wave-per-row tier: mid[0 .. n_mid)
+  const int* blk_last;  // block tier, written downwards from the end of the class's region: blk_last[0], blk_last[-1], ...
+  const int* giant;     // giant tier (ld_move_hub_kernel / ld_refine_propose_hub_kernel): giant[0 .. n_giant)
+  int n_mid, n_blk, n_giant;
+  int nb_main, nb_wave, nb_blk;  // workgroups of the main, the wave-per-row and the block tier in the fused launch
+};
+// the block tier's table lives in the 24 KB of LDS the main tier has anyway (2048 slots of 12 bytes): rows up to BLK_MAX_DEG
+// entries in one pass at a load of 3/4
+constexpr int BLK_SLOTS = 2048;
+constexpr int BLK_MAX_DEG = BLK_SLOTS * 3 / 4;
+constexpr int BLK_GRID = 4096;  // most workgroups of the block tier (one row each; beyond that they loop)
+
 struct MoveArgs {
   int n_act;
   const int* list;
-  const int* sub_list;
-  const int* sub_count;
   const int64_t* indptr;
   const int* indices;
   const long long* wq;
@@ -566,18 +582,15 @@ struct MoveArgs {
   int round;
   unsigned int seed;
   int* decision;
-  int* ovf_list;
-  int* hub_list;
-  int* counters;
+  TierLists tl;
 };
-// (the body takes its workgroup number and the number of workgroups as arguments: ld_requeue_move_kernel runs it on the
-// tail of a grid whose head re-queues the previous sub-round's movers)
+// (the body takes its workgroup number and the number of workgroups as arguments: it runs on a block range of the fused
+// launch, ld_move_tiers; sub_list != nullptr: indirect mode, the n_items positions listed there; hkeys / hvals: the
+// workgroup's 2048 table slots, 256 / G tables of GSLOTS)
 template <int G>
-__device__ __forceinline__ void ld_move_body(int bid, int nblk, const MoveArgs& ma) {
-  const int n_act = ma.n_act;
+__device__ __forceinline__ void ld_move_body(int bid, int nblk, const MoveArgs& ma, const int* __restrict__ sub_list, int n_items,
+                                             int* __restrict__ hkeys, unsigned long long* __restrict__ hvals) {
   const int* __restrict__ list = ma.list;
-  const int* __restrict__ sub_list = ma.sub_list;
-  const int* __restrict__ sub_count = ma.sub_count;
   const int64_t* __restrict__ indptr = ma.indptr;
   const int* __restrict__ indices = ma.indices;
   const long long* __restrict__ wq = ma.wq;
@@ -589,17 +602,12 @@ __device__ __forceinline__ void ld_move_body(int bid, int nblk, const MoveArgs& 
   const int round = ma.round;
   const unsigned int seed = ma.seed;
   int* __restrict__ decision = ma.decision;
-  int* __restrict__ ovf_list = ma.ovf_list;
-  int* __restrict__ hub_list = ma.hub_list;
-  int* __restrict__ counters = ma.counters;
   constexpr int GROUPS = 256 / G;            // vertices per workgroup
   constexpr int GSLOTS = G == 16 ? G16_SLOTS : WH_SLOTS * G / 64;  // table slots per vertex
   constexpr int GMAX = GSLOTS * 3 / 4;       // longest row the table takes
-  __shared__ int hkeys[GROUPS][GSLOTS];
-  __shared__ unsigned long long hvals[GROUPS][GSLOTS];
+  static_assert(GROUPS * GSLOTS == BLK_SLOTS, "the tiers share one table area");
   const int sub = threadIdx.x % G;
   const int grp = threadIdx.x / G;
-  const int n_items = sub_list ? *sub_count : n_act;
   for (int item = bid * GROUPS + grp; item < n_items; item += nblk * GROUPS) {
     // The decision of one vertex is a chain of dependent gathers (list -> indptr -> indices -> comm -> Ktot) and the
     // kernel is bound by its length: everything that depends on the same address is requested together, before the
@@ -625,72 +633,62 @@ __device__ __forceinline__ void ld_move_body(int bid, int nblk, const MoveArgs& 
     int c_pre[2];
 #pragma unroll
     for (int t = 0; t < 2; ++t) c_pre[t] = comm[u_pre[t]];
-    if (G < 64) {
-      if (deg > GMAX) {  // decided by the wave-per-vertex instantiation
-        if (sub == 0) ovf_list[atomicAdd(&counters[CTR_OVF], 1)] = w;
-        continue;
-      }
-    } else if (deg > WH_MAX_DEG) {  // hub: decided by ld_move_hub_kernel (any length: multi-pass table)
-      if (sub == 0) hub_list[atomicAdd(&counters[CTR_HUB], 1)] = w;
-      continue;
-    }
+    if (deg > GMAX) continue;  // a long row: on the list of another tier (list_long_rows)
     const double kv = (double)kq;
     const double Ka_wo = (double)(long long)(Ka - (unsigned long long)kq);  // own community without v
     Cand best = cand_none();
     long long w_own = 0;
-    if (deg <= GMAX) {
-      int* keys = hkeys[grp];
-      unsigned long long* vals = hvals[grp];
-      int nslots = 64;  // smallest power of two with load <= 3/4 (deg <= GMAX guarantees nslots <= GSLOTS)
-      while (nslots * 3 / 4 < deg) nslots <<= 1;
-      for (int i = sub; i < nslots; i += G) {
-        keys[i] = WH_EMPTY;
-        vals[i] = 0ull;
+    int* keys = hkeys + grp * GSLOTS;
+    unsigned long long* vals = hvals + grp * GSLOTS;
+    int nslots = 64;  // smallest power of two with load <= 3/4 (deg <= GMAX guarantees nslots <= GSLOTS)
+    while (nslots * 3 / 4 < deg) nslots <<= 1;
+    for (int i = sub; i < nslots; i += G) {
+      keys[i] = WH_EMPTY;
+      vals[i] = 0ull;
+    }
+    auto insert = [&](int c, long long wt) {
+      unsigned int slot = hash32((unsigned int)c) & (nslots - 1);
+      for (;;) {
+        const int prev = atomicCAS(&keys[slot], WH_EMPTY, c);
+        if (prev == WH_EMPTY || prev == c) break;
+        slot = (slot + 1) & (nslots - 1);
       }
-      auto insert = [&](int c, long long wt) {
-        unsigned int slot = hash32((unsigned int)c) & (nslots - 1);
-        for (;;) {
-          const int prev = atomicCAS(&keys[slot], WH_EMPTY, c);
-          if (prev == WH_EMPTY || prev == c) break;
-          slot = (slot + 1) & (nslots - 1);
-        }
-        atomicAdd(&vals[slot], (unsigned long long)wt);
-      };
+      atomicAdd(&vals[slot], (unsigned long long)wt);
+    };
 #pragma unroll
-      for (int t = 0; t < 2; ++t)
-        if (sub + t * G < deg && u_pre[t] != v) insert(c_pre[t], w_pre[t]);
-      for (int e = sub + 2 * G; e < deg; e += G) {
-        const int u = indices[beg + e];
-        if (u != v) insert(comm[u], wq[beg + e]);
+    for (int t = 0; t < 2; ++t)
+      if (sub + t * G < deg && u_pre[t] != v) insert(c_pre[t], w_pre[t]);
+    for (int e = sub + 2 * G; e < deg; e += G) {
+      const int u = indices[beg + e];
+      if (u != v) insert(comm[u], wq[beg + e]);
+    }
+    // candidates: the community totals of all occupied slots of this lane are requested before the first is used
+    constexpr int MAXSL = GSLOTS / G;
+    // (no per-lane branch around the gather and no constant merged into its result: either makes the compiler wait
+    // for the load where it is issued; empty slots read Ktot[a], the wave skips slot ranges none of its tables has)
+    int cs[MAXSL];
+    unsigned long long kt[MAXSL];
+#pragma unroll
+    for (int t = 0; t < MAXSL; ++t) cs[t] = WH_EMPTY;
+#pragma unroll
+    for (int t = 0; t < MAXSL; ++t) {
+      const int sl = sub + t * G;
+      if (__ballot(sl < nslots)) {
+        cs[t] = sl < nslots ? __hip_atomic_load(&keys[sl], __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WORKGROUP) : WH_EMPTY;
+        kt[t] = Ktot[cs[t] != WH_EMPTY ? cs[t] : a];
       }
-      // candidates: the community totals of all occupied slots of this lane are requested before the first is used
-      constexpr int MAXSL = GSLOTS / G;
-      // (no per-lane branch around the gather and no constant merged into its result: either makes the compiler wait
-      // for the load where it is issued; empty slots read Ktot[a], the wave skips slot ranges none of its tables has)
-      int cs[MAXSL];
-      unsigned long long kt[MAXSL];
+    }
 #pragma unroll
-      for (int t = 0; t < MAXSL; ++t) cs[t] = WH_EMPTY;
-#pragma unroll
-      for (int t = 0; t < MAXSL; ++t) {
-        const int sl = sub + t * G;
-        if (__ballot(sl < nslots)) {
-          cs[t] = sl < nslots ? __hip_atomic_load(&keys[sl], __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WORKGROUP) : WH_EMPTY;
-          kt[t] = Ktot[cs[t] != WH_EMPTY ? cs[t] : a];
-        }
-      }
-#pragma unroll
-      for (int t = 0; t < MAXSL; ++t) {
-        const int c = cs[t];
-        if (c != WH_EMPTY) {
-          const long long sum =
-              (long long)__hip_atomic_load(&vals[sub + t * G], __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WORKGROUP);
-          if (c == a) {
-            w_own = sum;
-          } else {
-            const Cand x = move_cand(c, sum, kt[t], g, kv, seed);
-            if (cand_better(x, best)) best = x;
-          }
+    for (int t = 0; t < MAXSL; ++t) {
+      const int c = cs[t];
+      if (c != WH_EMPTY) {
+        const long long sum =
+            (long long)__hip_atomic_load(&vals[sub + t * G], __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WORKGROUP);
+        if (c == a) {
+          w_own = sum;
+        } else {
+          const Cand x = move_cand(c, sum, kt[t], g, kv, seed);
+          if (cand_better(x, best)) best = x;
         }
       }
     }
@@ -700,11 +698,6 @@ __device__ __forceinline__ void ld_move_body(int bid, int nblk, const MoveArgs& 
     if (sub == 0) decision[w] = verdict;
   }
 }
-template <int G>
-__global__ __launch_bounds__(256) void ld_move_kernel(MoveArgs ma) {
-  ld_move_body<G>((int)blockIdx.x, (int)gridDim.x, ma);
-}
-
 // HUB_THREADS = 1024 (round 3; 256 before): a launch lasts as long as its longest row -- up to 20k entries on the coarse
 // levels of unstructured graphs, swept in 7 hash-class passes -- and the row is walked blockDim entries at a time.
 constexpr int HUB_THREADS = 1024;
@@ -758,43 +751,80 @@ __device__ __forceinline__ void hub_row(BlockHash& bh, int deg, const long long*
   }
 }
 
-// Hub vertices of the active list (positions in hub_list[0 .. counters[CTR_HUB])): one workgroup each.
+// The decision of the row at position w of the active list by a whole workgroup (block tier: 256 threads, giant tier: 1024).
+__device__ __forceinline__ void ld_move_hub_row(const MoveArgs& ma, int w, BlockHash& bh, const HubTry& ht, Cand* sh_c,
+                                                long long* sh_w, int* sh_fail) {
+  const int v = ma.list[w];
+  const int a = ma.comm[v];
+  const double kv = (double)ma.k[v];
+  const int64_t beg = ma.indptr[v];
+  const int deg = (int)(ma.indptr[v + 1] - beg);
+  const double Ka_wo = (double)(long long)(ma.Ktot[a] - (unsigned long long)ma.k[v]);
+  const int* __restrict__ urow = ma.indices + beg;
+  Cand best = cand_none();
+  long long w_own = 0;
+  hub_row(
+      bh, deg, ma.wq + beg, ht, sh_fail,
+      [&](int e) {
+        const int u = urow[e];
+        return u == v ? WH_EMPTY : ma.comm[u];
+      },
+      [&](int c, long long sum) {
+        if (c == a) {
+          w_own = sum;
+        } else {
+          const Cand x = move_cand(c, sum, ma.Ktot[c], ma.g, kv, ma.seed);
+          if (cand_better(x, best)) best = x;
+        }
+      });
+  best = block_best(best, w_own, sh_c, sh_w);
+  if (threadIdx.x == 0) ma.decision[w] = move_verdict(best, w_own, ma.g, kv, Ka_wo, a, v, ma.round, ma.seed, ma.csize);
+  __syncthreads();
+}
+// Giant tier: the rows beyond the block tier's table (positions in tl.giant), one 1024-thread workgroup each.
 __global__ __launch_bounds__(HUB_THREADS) void ld_move_hub_kernel(MoveArgs ma, HubTry ht) {
   extern __shared__ __attribute__((aligned(16))) unsigned long long hub_smem[];
   BlockHash bh{reinterpret_cast<int*>(hub_smem + BHUB_SLOTS), hub_smem, BHUB_SLOTS};
   __shared__ Cand sh_c[HUB_THREADS / 64];
   __shared__ long long sh_w[HUB_THREADS / 64];
   __shared__ int sh_fail;
-  const int n_hub = ma.counters[CTR_HUB];
-  for (int i = blockIdx.x; i < n_hub; i += gridDim.x) {
-    const int w = ma.hub_list[i];
-    const int v = ma.list[w];
-    const int a = ma.comm[v];
-    const double kv = (double)ma.k[v];
-    const int64_t beg = ma.indptr[v];
-    const int deg = (int)(ma.indptr[v + 1] - beg);
-    const double Ka_wo = (double)(long long)(ma.Ktot[a] - (unsigned long long)ma.k[v]);
-    const int* __restrict__ urow = ma.indices + beg;
-    Cand best = cand_none();
-    long long w_own = 0;
-    hub_row(
-        bh, deg, ma.wq + beg, ht, &sh_fail,
-        [&](int e) {
-          const int u = urow[e];
-          return u == v ? WH_EMPTY : ma.comm[u];
-        },
-        [&](int c, long long sum) {
-          if (c == a) {
-            w_own = sum;
-          } else {
-            const Cand x = move_cand(c, sum, ma.Ktot[c], ma.g, kv, ma.seed);
-            if (cand_better(x, best)) best = x;
-          }
-        });
-    best = block_best(best, w_own, sh_c, sh_w);
-    if (threadIdx.x == 0) ma.decision[w] = move_verdict(best, w_own, ma.g, kv, Ka_wo, a, v, ma.round, ma.seed, ma.csize);
-    __syncthreads();
+  for (int i = blockIdx.x; i < ma.tl.n_giant; i += gridDim.x) ld_move_hub_row(ma, ma.tl.giant[i], bh, ht, sh_c, sh_w, &sh_fail);
+}
+
+// The static LDS of a fused decide kernel: the 2048 table slots its tiers share (main tier: 256 / G tables, wave-per-row tier:
+// four, block tier: one) and the block tier's reduction scratch.
+struct TierLds {
+  unsigned long long hvals[BLK_SLOTS];
+  int hkeys[BLK_SLOTS];
+  Cand sh_c[256 / 64];
+  long long sh_w[256 / 64];
+  int sh_fail;
+};
+// ALL tiers of a decide step that a 256-thread workgroup can take, as block ranges of one grid: they read the same snapshot
+// and write different vertices' decisions.  bid: the workgroup's number among the ma.tl.nb_main + nb_wave + nb_blk of them.
+template <int G>
+__device__ __forceinline__ void ld_move_tiers(int bid, const MoveArgs& ma, TierLds& lds) {
+  const TierLists& tl = ma.tl;
+  if (bid < tl.nb_main) {
+    ld_move_body<G>(bid, tl.nb_main, ma, nullptr, ma.n_act, lds.hkeys, lds.hvals);
+    return;
   }
+  bid -= tl.nb_main;
+  if constexpr (G < 64) {
+    if (bid < tl.nb_wave) {
+      ld_move_body<64>(bid, tl.nb_wave, ma, tl.mid, tl.n_mid, lds.hkeys, lds.hvals);
+      return;
+    }
+  }
+  bid -= tl.nb_wave;
+  BlockHash bh{lds.hkeys, lds.hvals, BLK_SLOTS, BLK_SLOTS};
+  const HubTry no_try{nullptr, 0};  // (one pass: a row of this tier is no longer than BLK_MAX_DEG <= BHUB_MAX_DEG)
+  for (int i = bid; i < tl.n_blk; i += tl.nb_blk) ld_move_hub_row(ma, tl.blk_last[-i], bh, no_try, lds.sh_c, lds.sh_w, &lds.sh_fail);
+}
+template <int G>
+__global__ __launch_bounds__(256) void ld_move_kernel(MoveArgs ma) {
+  __shared__ TierLds lds;
+  ld_move_tiers<G>((int)blockIdx.x, ma, lds);
 }
 
 // One thread per active vertex: apply the decided moves in place (integer atomics on the community totals); vertices
@@ -888,15 +918,16 @@ __global__ __launch_bounds__(256) void ld_requeue_kernel(int n_act, const int* _
 // reads the decisions of class c (their own buffer: `decision` alternates between two buffers from sub-round to
 // sub-round) and the communities after apply(c), and writes flags; the decisions of class c + 1 read the same state and
 // write their own buffer and lists.  The first nb_rq workgroups re-queue, the rest decide.  One launch of ~16 us less per
-// sub-round (152 per call at 1M cells).
+// sub-round (152 per call at 1M cells).  The decide blocks are ALL tiers of the sub-round (ld_move_tiers).
 template <int G>
 __global__ __launch_bounds__(256) void ld_requeue_move_kernel(int nb_rq, int rq_n_act, const int* __restrict__ rq_list,
                                                               const int* __restrict__ rq_decision,
                                                               const int64_t* __restrict__ indptr,
                                                               const int* __restrict__ indices, const int* __restrict__ comm,
                                                               int* __restrict__ flag, MoveArgs ma) {
+  __shared__ TierLds lds;
   if ((int)blockIdx.x < nb_rq) ld_requeue_body((int)blockIdx.x, rq_n_act, rq_list, rq_decision, indptr, indices, comm, flag);
-  else ld_move_body<G>((int)blockIdx.x - nb_rq, (int)gridDim.x - nb_rq, ma);
+  else ld_move_tiers<G>((int)blockIdx.x - nb_rq, ma, lds);
 }
 
 // ---- final polish (n_iterations < 0): strictly monotone single-vertex moves ----------------------------------------
@@ -1014,30 +1045,50 @@ __device__ __forceinline__ int lm_class(int v, unsigned int salt, int n_cls) {
 // flags -> n_cls class lists (lists[c * n ..]), counts in cls_count[0 .. n_cls); clears the flags.  flag == nullptr:
 // every vertex is active (first sweep of a level).  The order inside a list is irrelevant (every decision of a
 // sub-round reads the same snapshot).  One atomic per class and 1024-vertex block.
-// Long rows of a class, counted while its list is built (round 4): sub-round c's counter block gets the number of its
-// vertices whose rows the main decision kernel hands on -- longer than thr_mid (the lanes-per-vertex table) / longer than
-// thr_hub (the wave table) -- so that the host launches the overflow / hub kernels of a sub-round only when it has any
-// (they were launched blind: ~300 near-empty launches of ~10 us per call at 1M cells).  thr_mid < 0: no such tier.
-// tier of a vertex's row: bit 0 = longer than thr_mid, bit 1 = longer than thr_hub (0 for inactive vertices)
-__device__ __forceinline__ int long_row_tier(int cls, int v, const int64_t* __restrict__ indptr, int thr_mid, int thr_hub) {
-  if (cls < 0 || !indptr) return 0;
-  const int deg = (int)(indptr[v + 1] - indptr[v]);
-  return ((thr_mid >= 0 && deg > thr_mid) ? 1 : 0) | (deg > thr_hub ? 2 : 0);
+// Long rows of a class, listed while its list is built: the tier of a row is known from its length, so the decide step of
+// a sub-round finds the rows of every tier on a list of their own and runs the tiers side by side in one launch (until
+// then the main decide kernel appended them at run time, and the tiers ran one launch behind the other).  The list lengths
+// double as the host's launch sizes: a tier without rows gets no workgroups, the giant tier no launch.
+struct TierDst {
+  const int64_t* indptr;  // of the level (nullptr: no tier lists)
+  int* lists;             // class c: lists[c * n ..]: its wave-tier positions upwards from [0], its block-tier positions
+                          // downwards from [n - 1] (both tiers together are at most the n_act <= n rows of the class)
+  int* giant;             // class c: giant[c * giant_stride ..]
+  int giant_stride;       // > entries of the level / (BLK_MAX_DEG + 1): more giant rows do not exist
+  int thr_mid;            // longest row of the main tier (the lanes-per-vertex table); < 0: the main tier IS the wave tier
+};
+// tier of a vertex's row: 0 main (and inactive vertices), 1 wave-per-row, 2 block, 3 giant
+__device__ __forceinline__ int long_row_tier(int cls, int v, const TierDst& d) {
+  if (cls < 0 || !d.indptr) return 0;
+  const int deg = (int)(d.indptr[v + 1] - d.indptr[v]);
+  return deg > BLK_MAX_DEG ? 3 : (deg > WH_MAX_DEG ? 2 : ((d.thr_mid >= 0 && deg > d.thr_mid) ? 1 : 0));
 }
-// one atomic per wave, class and tier (inside the class loop of the list builders; every lane of the wave calls it)
-__device__ __forceinline__ void count_long_rows(int c, int cls, int tier, int lane, int* __restrict__ cls_count) {
-  const unsigned long long mm = __ballot(cls == c && (tier & 1)), mh = __ballot(cls == c && (tier & 2));
-  if (lane == 0) {
-    int* ctr = cls_count + MAX_CLASSES + CTR_STRIDE * c;
-    if (mm) atomicAdd(&ctr[CTR_N_MID], __popcll(mm));
-    if (mh) atomicAdd(&ctr[CTR_N_HUB], __popcll(mh));
+// w: the vertex's position in the list of its class.  One atomic per wave, class and tier (coarse levels of unstructured
+// graphs are mostly long rows); waves without long rows -- nearly all of a kNN graph's -- pay three ballots.  Every lane of
+// the wave calls it.
+__device__ __forceinline__ void list_long_rows(int cls, int tier, int w, int n, int lane, int* __restrict__ cls_count, const TierDst& d) {
+  for (int t = 1; t <= 3; ++t) {
+    unsigned long long todo = __ballot(tier == t);
+    while (todo) {  // (the same for every lane)
+      const int c = __shfl(cls, __ffsll((long long)todo) - 1);
+      const unsigned long long m = __ballot(tier == t && cls == c);
+      todo &= ~m;
+      int base = 0;
+      if (lane == 0) base = atomicAdd(&cls_count[MAX_CLASSES + CTR_STRIDE * c + (t == 1 ? CTR_N_MID : (t == 2 ? CTR_N_BLK : CTR_N_GIANT))], __popcll(m));
+      base = __shfl(base, 0);
+      if (tier == t && cls == c) {
+        const int pos = base + __popcll(m & ((1ull << lane) - 1ull));
+        if (t == 1) d.lists[(size_t)c * n + pos] = w;
+        else if (t == 2) d.lists[(size_t)c * n + (n - 1 - pos)] = w;
+        else d.giant[(size_t)c * d.giant_stride + pos] = w;
+      }
+    }
   }
 }
 
 __global__ __launch_bounds__(1024) void ld_compact_cls_kernel(int n, int* __restrict__ flag, int* __restrict__ lists,
                                                               int* __restrict__ cls_count, int n_cls, unsigned int salt,
-                                                              const int64_t* __restrict__ indptr, int thr_mid, int thr_hub,
-                                                              int* __restrict__ clear_next, int clear_words) {
+                                                              TierDst tiers, int* __restrict__ clear_next, int clear_words) {
   __shared__ int wcnt[16][MAX_CLASSES];
   __shared__ int base[MAX_CLASSES];
   // (the counter block the NEXT sweep will count into: its last users were the sub-rounds of the sweep before this one)
@@ -1054,13 +1105,12 @@ __global__ __launch_bounds__(1024) void ld_compact_cls_kernel(int n, int* __rest
     }
     if (f) cls = lm_class(v, salt, n_cls);
   }
-  const int tier = long_row_tier(cls, v, indptr, thr_mid, thr_hub);
+  const int tier = long_row_tier(cls, v, tiers);
   int rank = 0;
   for (int c = 0; c < n_cls; ++c) {
     const unsigned long long m = __ballot(cls == c);
     if (cls == c) rank = __popcll(m & ((1ull << lane) - 1ull));
     if (lane == 0) wcnt[wv][c] = __popcll(m);
-    count_long_rows(c, cls, tier, lane, cls_count);
   }
   __syncthreads();
   if ((int)threadIdx.x < n_cls) {
@@ -1074,7 +1124,9 @@ __global__ __launch_bounds__(1024) void ld_compact_cls_kernel(int n, int* __rest
     base[c] = tot ? atomicAdd(&cls_count[c], tot) : 0;
   }
   __syncthreads();
-  if (cls >= 0) lists[(size_t)cls * n + base[cls] + wcnt[wv][cls] + rank] = v;
+  const int w = cls >= 0 ? base[cls] + wcnt[wv][cls] + rank : 0;
+  if (cls >= 0) lists[(size_t)cls * n + w] = v;
+  list_long_rows(cls, tier, w, n, lane, cls_count, tiers);
 }
 
 // Packed mirrors of the refinement's state (round 4).  Counters of the decision kernels (profiles/r04n_leiden_kernels_pmc*.csv):
@@ -1135,7 +1187,7 @@ __global__ __launch_bounds__(256) void ld_within_kernel(int n, const int64_t* __
 __global__ __launch_bounds__(1024) void ld_refine_candidates_kernel(
     int n, const long long* __restrict__ k, const int* __restrict__ comm, const unsigned long long* __restrict__ Ktot,
     const long long* __restrict__ a_in, double g, int* __restrict__ lists, int* __restrict__ cls_count, int n_cls,
-    unsigned int salt, const int64_t* __restrict__ indptr, int thr_mid, int thr_hub) {
+    unsigned int salt, TierDst tiers) {
   __shared__ int wcnt[16][MAX_CLASSES];
   __shared__ int base[MAX_CLASSES];
   const int v = blockIdx.x * 1024 + threadIdx.x;
@@ -1146,13 +1198,12 @@ __global__ __launch_bounds__(1024) void ld_refine_candidates_kernel(
     const double KC = (double)(long long)Ktot[comm[v]];
     if ((double)a_in[v] >= g * kv * (KC - kv)) cls = lm_class(v, salt, n_cls);
   }
-  const int tier = long_row_tier(cls, v, indptr, thr_mid, thr_hub);
+  const int tier = long_row_tier(cls, v, tiers);
   int rank = 0;
   for (int c = 0; c < n_cls; ++c) {
     const unsigned long long m = __ballot(cls == c);
     if (cls == c) rank = __popcll(m & ((1ull << lane) - 1ull));
     if (lane == 0) wcnt[wv][c] = __popcll(m);
-    count_long_rows(c, cls, tier, lane, cls_count);
   }
   __syncthreads();
   if ((int)threadIdx.x < n_cls) {
@@ -1166,7 +1217,9 @@ __global__ __launch_bounds__(1024) void ld_refine_candidates_kernel(
     base[c] = tot ? atomicAdd(&cls_count[c], tot) : 0;
   }
   __syncthreads();
-  if (cls >= 0) lists[(size_t)cls * n + base[cls] + wcnt[wv][cls] + rank] = v;
+  const int w = cls >= 0 ? base[cls] + wcnt[wv][cls] + rank : 0;
+  if (cls >= 0) lists[(size_t)cls * n + w] = v;
+  list_long_rows(cls, tier, w, n, lane, cls_count, tiers);
 }
 
 // Exact incremental update of w(r, C - r) after a round of merges.  For a vertex v that joined t this round
@@ -1269,8 +1322,6 @@ __device__ __forceinline__ int refine_verdict(const RefineRule& r, int v, const 
 struct ProposeArgs {
   int n_act;        // length of ...
   const int* list;  // ... the candidates of class rule.round
-  const int* sub_list;
-  const int* sub_count;
   const int64_t* indptr;
   const int* indices;
   const long long* wq;
@@ -1283,18 +1334,16 @@ struct ProposeArgs {
   const TargRec* tr;
   RefineRule rule;
   int* target;
-  int* ovf_list;
-  int* hub_list;
-  int* counters;
+  TierLists tl;
 };
-// G lanes per candidate (see ld_move_kernel: G = 16 puts four candidates in a wave on short-rowed levels, rows longer
-// than the 128-slot table go to ovf_list / counters[CTR_OVF] and are proposed by the G = 64 instantiation in indirect
-// mode).  target[v] = refined community to join, -1 = no admissible target, -2 = no longer a singleton (somebody joined
-// it) or "stay" was drawn.
+// G lanes per candidate (see ld_move_body: G = 16 puts four candidates in a wave on short-rowed levels, rows longer
+// than the table are on the list of another tier and proposed there: by the G = 64 instantiation in indirect mode, or by
+// a workgroup).  target[v] = refined community to join, -1 = no admissible target, -2 = no longer a singleton (somebody
+// joined it) or "stay" was drawn.
 template <int G>
-__global__ __launch_bounds__(256) void ld_refine_propose_kernel(ProposeArgs pa) {
+__device__ __forceinline__ void ld_refine_propose_body(int bid, int nblk, const ProposeArgs& pa, const int* __restrict__ sub_list,
+                                                       int n_items, int* __restrict__ hkeys, unsigned long long* __restrict__ hvals) {
   const int* __restrict__ list = pa.list;
-  const int* __restrict__ sub_list = pa.sub_list;
   const int64_t* __restrict__ indptr = pa.indptr;
   const int* __restrict__ indices = pa.indices;
   const long long* __restrict__ wq = pa.wq;
@@ -1309,12 +1358,10 @@ __global__ __launch_bounds__(256) void ld_refine_propose_kernel(ProposeArgs pa) 
   constexpr int GROUPS = 256 / G;
   constexpr int GSLOTS = G == 16 ? G16_SLOTS : WH_SLOTS * G / 64;
   constexpr int GMAX = GSLOTS * 3 / 4;
-  __shared__ int hkeys[GROUPS][GSLOTS];
-  __shared__ unsigned long long hvals[GROUPS][GSLOTS];
+  static_assert(GROUPS * GSLOTS == BLK_SLOTS, "the tiers share one table area");
   const int sub = threadIdx.x % G;
   const int grp = threadIdx.x / G;
-  const int n_items = sub_list ? *pa.sub_count : pa.n_act;
-  for (int item = blockIdx.x * GROUPS + grp; item < n_items; item += gridDim.x * GROUPS) {
+  for (int item = bid * GROUPS + grp; item < n_items; item += nblk * GROUPS) {
     // (gathers grouped by what they depend on, as in ld_move_kernel: list -> {refsize, ref, k, comm, indptr}[v] ->
     // {Ktot[a], indices, wq} -> {comm, ref}[u] -> {Kref, refsize, Eref}[c]; most launches of a refinement are short
     // lists whose time IS the length of this chain)
@@ -1325,11 +1372,12 @@ __global__ __launch_bounds__(256) void ld_refine_propose_kernel(ProposeArgs pa) 
     const int a = comm[v];
     const int64_t beg = indptr[v];
     const int64_t end = indptr[v + 1];
+    const int deg = (int)(end - beg);
+    if (deg > GMAX) continue;  // a long row: on the list of another tier (list_long_rows), which writes target[v]
     int tgt = -1;
     if (rs_v != 1 || ref_v != v) {
       tgt = -2;
     } else {
-      const int deg = (int)(end - beg);
       int u_pre[2];
       long long w_pre[2];
 #pragma unroll
@@ -1347,69 +1395,58 @@ __global__ __launch_bounds__(256) void ld_refine_propose_kernel(ProposeArgs pa) 
         rf_pre[t] = r.ref;
       }
       const double kv = (double)kq;
-      if (G < 64) {
-        if (deg > GMAX) {  // proposed by the wave-per-candidate instantiation
-          if (sub == 0) pa.ovf_list[atomicAdd(&pa.counters[CTR_OVF], 1)] = w;
-          continue;
-        }
-      } else if (deg > WH_MAX_DEG) {  // hub: proposed by ld_refine_propose_hub_kernel (any length)
-        if (sub == 0) pa.hub_list[atomicAdd(&pa.counters[CTR_HUB], 1)] = v;
-        continue;
-      }
       Cand best = cand_none();
-      if (deg <= GMAX) {
-        int* keys = hkeys[grp];
-        unsigned long long* vals = hvals[grp];
-        const int nslots = G < 64 ? (deg <= 48 ? 64 : 128) : (deg <= 96 ? 128 : (deg <= 192 ? 256 : 512));
-        for (int i = sub; i < nslots; i += G) {
-          keys[i] = WH_EMPTY;
-          vals[i] = 0ull;
+      int* keys = hkeys + grp * GSLOTS;
+      unsigned long long* vals = hvals + grp * GSLOTS;
+      const int nslots = G < 64 ? (deg <= 48 ? 64 : 128) : (deg <= 96 ? 128 : (deg <= 192 ? 256 : 512));
+      for (int i = sub; i < nslots; i += G) {
+        keys[i] = WH_EMPTY;
+        vals[i] = 0ull;
+      }
+      auto insert = [&](int c, long long wt) {
+        unsigned int slot = hash32((unsigned int)c) & (nslots - 1);
+        for (;;) {
+          const int prev = atomicCAS(&keys[slot], WH_EMPTY, c);
+          if (prev == WH_EMPTY || prev == c) break;
+          slot = (slot + 1) & (nslots - 1);
         }
-        auto insert = [&](int c, long long wt) {
-          unsigned int slot = hash32((unsigned int)c) & (nslots - 1);
-          for (;;) {
-            const int prev = atomicCAS(&keys[slot], WH_EMPTY, c);
-            if (prev == WH_EMPTY || prev == c) break;
-            slot = (slot + 1) & (nslots - 1);
-          }
-          atomicAdd(&vals[slot], (unsigned long long)wt);
-        };
+        atomicAdd(&vals[slot], (unsigned long long)wt);
+      };
 #pragma unroll
-        for (int t = 0; t < 2; ++t)
-          if (sub + t * G < deg && u_pre[t] != v && cm_pre[t] == a) insert(rf_pre[t], w_pre[t]);
-        for (int e = sub + 2 * G; e < deg; e += G) {
-          const int u = indices[beg + e];
-          const VertRec r = vr[u];
-          if (u != v && r.comm == a) insert(r.ref, wq[beg + e]);
+      for (int t = 0; t < 2; ++t)
+        if (sub + t * G < deg && u_pre[t] != v && cm_pre[t] == a) insert(rf_pre[t], w_pre[t]);
+      for (int e = sub + 2 * G; e < deg; e += G) {
+        const int u = indices[beg + e];
+        const VertRec r = vr[u];
+        if (u != v && r.comm == a) insert(r.ref, wq[beg + e]);
+      }
+      constexpr int MAXSL = GSLOTS / G;
+      int cs[MAXSL], rsz[MAXSL];
+      unsigned long long kr[MAXSL], er[MAXSL];
+#pragma unroll
+      for (int t = 0; t < MAXSL; ++t) cs[t] = WH_EMPTY;
+#pragma unroll
+      for (int t = 0; t < MAXSL; ++t) {
+        const int sl = sub + t * G;
+        if (__ballot(sl < nslots)) {  // (see ld_move_kernel: uniform skip, no per-lane branch around the gathers)
+          int c = sl < nslots ? __hip_atomic_load(&keys[sl], __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WORKGROUP) : WH_EMPTY;
+          if (c == v) c = WH_EMPTY;
+          cs[t] = c;
+          const int ci = c != WH_EMPTY ? c : v;
+          const TargRec x = tr[ci];  // one 32-byte record per target instead of three gathers
+          kr[t] = x.Kref;
+          rsz[t] = x.refsize;
+          er[t] = x.Eref;
         }
-        constexpr int MAXSL = GSLOTS / G;
-        int cs[MAXSL], rsz[MAXSL];
-        unsigned long long kr[MAXSL], er[MAXSL];
+      }
 #pragma unroll
-        for (int t = 0; t < MAXSL; ++t) cs[t] = WH_EMPTY;
-#pragma unroll
-        for (int t = 0; t < MAXSL; ++t) {
-          const int sl = sub + t * G;
-          if (__ballot(sl < nslots)) {  // (see ld_move_kernel: uniform skip, no per-lane branch around the gathers)
-            int c = sl < nslots ? __hip_atomic_load(&keys[sl], __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WORKGROUP) : WH_EMPTY;
-            if (c == v) c = WH_EMPTY;
-            cs[t] = c;
-            const int ci = c != WH_EMPTY ? c : v;
-            const TargRec x = tr[ci];  // one 32-byte record per target instead of three gathers
-            kr[t] = x.Kref;
-            rsz[t] = x.refsize;
-            er[t] = x.Eref;
-          }
-        }
-#pragma unroll
-        for (int t = 0; t < MAXSL; ++t) {
-          const int c = cs[t];
-          if (c != WH_EMPTY) {
-            const long long sum =
-                (long long)__hip_atomic_load(&vals[sub + t * G], __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WORKGROUP);
-            Cand x;
-            if (refine_cand(rule, v, kv, KC, c, sum, kr[t], rsz[t], er[t], &x) && cand_better(x, best)) best = x;
-          }
+      for (int t = 0; t < MAXSL; ++t) {
+        const int c = cs[t];
+        if (c != WH_EMPTY) {
+          const long long sum =
+              (long long)__hip_atomic_load(&vals[sub + t * G], __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WORKGROUP);
+          Cand x;
+          if (refine_cand(rule, v, kv, KC, c, sum, kr[t], rsz[t], er[t], &x) && cand_better(x, best)) best = x;
         }
       }
       best = group_best<G>(best);
@@ -1419,41 +1456,71 @@ __global__ __launch_bounds__(256) void ld_refine_propose_kernel(ProposeArgs pa) 
   }
 }
 
-// Hub candidates (vertex ids in hub_list[0 .. counters[CTR_HUB])): one workgroup each.
+// The proposal of the candidate at position w of the class list by a whole workgroup (block tier: 256 threads, giant: 1024).
+__device__ __forceinline__ void ld_refine_propose_hub_row(const ProposeArgs& pa, int w, BlockHash& bh, const HubTry& ht,
+                                                          Cand* sh_c, long long* sh_w, int* sh_fail) {
+  const int v = pa.list[w];
+  if (pa.refsize[v] != 1 || pa.ref[v] != v) {  // no longer a singleton (the same for every thread: no barrier is skipped by some)
+    if (threadIdx.x == 0) pa.target[v] = -2;
+    return;
+  }
+  const double kv = (double)pa.k[v];
+  const int a = pa.comm[v];
+  const double KC = (double)(long long)pa.Ktot[a];
+  const int64_t beg = pa.indptr[v];
+  const int deg = (int)(pa.indptr[v + 1] - beg);
+  const int* __restrict__ urow = pa.indices + beg;
+  Cand best = cand_none();
+  long long dummy = 0;
+  hub_row(
+      bh, deg, pa.wq + beg, ht, sh_fail,
+      [&](int e) {
+        const int u = urow[e];
+        const VertRec r = pa.vr[u];
+        return (u == v || r.comm != a) ? WH_EMPTY : r.ref;
+      },
+      [&](int c, long long sum) {
+        if (c == v) return;
+        const TargRec t = pa.tr[c];
+        Cand x;
+        if (refine_cand(pa.rule, v, kv, KC, c, sum, t.Kref, t.refsize, t.Eref, &x) && cand_better(x, best)) best = x;
+      });
+  best = block_best(best, dummy, sh_c, sh_w);
+  if (threadIdx.x == 0) pa.target[v] = refine_verdict(pa.rule, v, best);
+  __syncthreads();
+}
+// Giant tier of the refinement (see ld_move_hub_kernel)
 __global__ __launch_bounds__(HUB_THREADS) void ld_refine_propose_hub_kernel(ProposeArgs pa, HubTry ht) {
   extern __shared__ __attribute__((aligned(16))) unsigned long long hub_smem[];
   BlockHash bh{reinterpret_cast<int*>(hub_smem + BHUB_SLOTS), hub_smem, BHUB_SLOTS};
   __shared__ Cand sh_c[HUB_THREADS / 64];
   __shared__ long long sh_w[HUB_THREADS / 64];
   __shared__ int sh_fail;
-  const int n_hub = pa.counters[CTR_HUB];
-  for (int i = blockIdx.x; i < n_hub; i += gridDim.x) {
-    const int v = pa.hub_list[i];
-    const double kv = (double)pa.k[v];
-    const int a = pa.comm[v];
-    const double KC = (double)(long long)pa.Ktot[a];
-    const int64_t beg = pa.indptr[v];
-    const int deg = (int)(pa.indptr[v + 1] - beg);
-    const int* __restrict__ urow = pa.indices + beg;
-    Cand best = cand_none();
-    long long dummy = 0;
-    hub_row(
-        bh, deg, pa.wq + beg, ht, &sh_fail,
-        [&](int e) {
-          const int u = urow[e];
-          const VertRec r = pa.vr[u];
-          return (u == v || r.comm != a) ? WH_EMPTY : r.ref;
-        },
-        [&](int c, long long sum) {
-          if (c == v) return;
-          const TargRec t = pa.tr[c];
-          Cand x;
-          if (refine_cand(pa.rule, v, kv, KC, c, sum, t.Kref, t.refsize, t.Eref, &x) && cand_better(x, best)) best = x;
-        });
-    best = block_best(best, dummy, sh_c, sh_w);
-    if (threadIdx.x == 0) pa.target[v] = refine_verdict(pa.rule, v, best);
-    __syncthreads();
+  for (int i = blockIdx.x; i < pa.tl.n_giant; i += gridDim.x)
+    ld_refine_propose_hub_row(pa, pa.tl.giant[i], bh, ht, sh_c, sh_w, &sh_fail);
+}
+// All tiers of a sub-round's proposals that a 256-thread workgroup can take, as block ranges of one grid (see ld_move_tiers)
+template <int G>
+__global__ __launch_bounds__(256) void ld_refine_propose_kernel(ProposeArgs pa) {
+  __shared__ TierLds lds;
+  const TierLists& tl = pa.tl;
+  int bid = (int)blockIdx.x;
+  if (bid < tl.nb_main) {
+    ld_refine_propose_body<G>(bid, tl.nb_main, pa, nullptr, pa.n_act, lds.hkeys, lds.hvals);
+    return;
   }
+  bid -= tl.nb_main;
+  if constexpr (G < 64) {
+    if (bid < tl.nb_wave) {
+      ld_refine_propose_body<64>(bid, tl.nb_wave, pa, tl.mid, tl.n_mid, lds.hkeys, lds.hvals);
+      return;
+    }
+  }
+  bid -= tl.nb_wave;
+  BlockHash bh{lds.hkeys, lds.hvals, BLK_SLOTS, BLK_SLOTS};
+  const HubTry no_try{nullptr, 0};
+  for (int i = bid; i < tl.n_blk; i += tl.nb_blk)
+    ld_refine_propose_hub_row(pa, tl.blk_last[-i], bh, no_try, lds.sh_c, lds.sh_w, &lds.sh_fail);
 }
 
 // counters: the sub-round's counter block; [CTR_JOINED] merges of this sub-round (= joiner list length)
@@ -2599,6 +2666,7 @@ struct LeidenBuffers {
   int* sm_ix[2]; long long* sm_w[2];  // coarse levels of ld_small_levels_kernel (SMALL_NNZ entries each): it leaves the pool alone
   int* comm; int* csize; unsigned long long* Ktot;
   int* cls_lists; int* rlist; int* touched; int* hub_list;
+  int* tier_lists; int* giant_lists;  // per class: the long rows of its list, by decide tier (TierDst)
   int* ref; int* target; int* target2; int* refsize; unsigned long long* Kref; unsigned long long* Eref; long long* a_in;
   VertRec* vrec; TargRec* trec;  // packed mirrors of {comm, ref, stamp} and {Kref, Eref, refsize} for the refinement's gathers
   int* flag; int64_t* newid; int64_t* scan_tmp; int* cid; int* rep; int* comm_tmp;
@@ -2634,7 +2702,12 @@ static void leiden_carve(Workspace& ws, int64_t n, int64_t nnz, LeidenBuffers* b
   // class lists of a sweep (local moving) / of the refinement: lists[c * n_level ..].  Levels above 4096 vertices use at
   // most DEF_CLASSES lists; only levels of <= 4096 vertices take MAX_CLASSES refinement sub-rounds.  (Round 3 carved
   // MAX_CLASSES x N: 1.28 GB at 10M cells for lists of which 8 were ever used)
-  b->cls_lists = ws.take<int>(std::max((size_t)DEF_CLASSES * N, (size_t)MAX_CLASSES * std::min<size_t>(N, 4096)));
+  const size_t cls_ints = std::max((size_t)DEF_CLASSES * N, (size_t)MAX_CLASSES * std::min<size_t>(N, 4096));
+  b->cls_lists = ws.take<int>(cls_ints);
+  // tier lists of the classes (TierDst): a region per class like cls_lists for the wave tier (upwards) and the block tier
+  // (downwards); a giant row has more than BLK_MAX_DEG entries, so a level has fewer than E / (BLK_MAX_DEG + 1) + 1 of them
+  b->tier_lists = ws.take<int>(cls_ints);
+  b->giant_lists = ws.take<int>((size_t)MAX_CLASSES * (E / (BLK_MAX_DEG + 1) + 1));
   b->rlist = ws.take<int>(N);
   b->hub_list = ws.take<int>(N);
   b->touched = ws.take<int>(N);
@@ -2903,59 +2976,72 @@ static int refine_lanes(const LeidenCtx& cx, const LevelGraph& g) { return level
 // (-1: no such tier, the launch is the 64-lane one)
 static int lanes_thr_mid(int lanes) { return lanes == 16 ? (int)G16_MAX : (lanes == 32 ? (int)(WH_SLOTS / 2 * 3 / 4) : -1); }
 
-// One decide step of a class sub-round, in its three tiers: the main launch (`lanes` lanes per vertex, the whole list), the
-// 64-lane pass over the rows the main launch handed on (indirect mode: positions in ovf_list, their number in the counter
-// block), the workgroup-per-row pass over the hubs.  hctr: the host's copy of the sub-round's counter block as the list
-// builder left it -- a tier without rows is not launched.  main = false: the main launch has been made already (by
-// ld_requeue_move_kernel).  The two flavours, by the argument struct: MoveArgs (local moving, polish) and ProposeArgs
-// (refinement).
-static void launch_main_tier(LeidenCtx& cx, int lanes, const MoveArgs& a) {
+// where the list builders of a level write its tier lists (list_long_rows)
+static int giant_stride(const LevelGraph& g) { return (int)(g.nnz / (BLK_MAX_DEG + 1)) + 1; }
+static TierDst tier_dst(LeidenCtx& cx, const LevelGraph& g, int lanes) {
+  return TierDst{g.indptr, cx.b.tier_lists, cx.b.giant_lists, giant_stride(g), lanes_thr_mid(lanes)};
+}
+
+// One decide step of a class sub-round: ONE launch for every tier a 256-thread workgroup can take -- the main tier (`lanes`
+// lanes per vertex, the whole class list, long rows skipped), the wave-per-row tier and the block tier over the lists the
+// class's builder left (TierLists), as block ranges of one grid -- and, only when the class has such a row, the 1024-thread
+// launch of the giant tier.  rq: the sub-round before this one, whose movers re-queue their neighbours in the head of the
+// same launch (local moving; nullptr: nothing to re-queue).  hctr: the host's copy of the sub-round's counter block as the
+// list builder left it: the tiers' rows, from which the block ranges are sized -- a tier without rows gets no workgroups.
+// The two flavours, by the argument struct: MoveArgs (local moving, polish) and ProposeArgs (refinement).
+struct RequeueHead {
+  int n_act;
+  const int* list;
+  const int* decision;
+};
+static int main_grid_cap(const MoveArgs&) { return 1 << 30; }
+static int main_grid_cap(const ProposeArgs&) { return 32768; }
+static void launch_fused_tiers(LeidenCtx& cx, const LevelGraph& g, int lanes, unsigned grid, const RequeueHead* rq, int nb_rq, const MoveArgs& a) {
   with_lanes<true>(lanes, [&](auto G) {
     constexpr int L = decltype(G)::value;
-    hipLaunchKernelGGL(ld_move_kernel<L>, dim3((unsigned)blocks_for(L, a.n_act)), dim3(256), 0, cx.s, a);
+    if (rq)
+      hipLaunchKernelGGL(ld_requeue_move_kernel<L>, dim3(grid), dim3(256), 0, cx.s, nb_rq, rq->n_act, rq->list, rq->decision, g.indptr,
+                         g.indices, (const int*)cx.b.comm, cx.b.flag, a);
+    else
+      hipLaunchKernelGGL(ld_move_kernel<L>, dim3(grid), dim3(256), 0, cx.s, a);
   });
 }
-static void launch_main_tier(LeidenCtx& cx, int lanes, const ProposeArgs& a) {
+static void launch_fused_tiers(LeidenCtx& cx, const LevelGraph&, int lanes, unsigned grid, const RequeueHead*, int, const ProposeArgs& a) {
   with_lanes<false>(lanes, [&](auto G) {
-    constexpr int L = decltype(G)::value;
-    hipLaunchKernelGGL(ld_refine_propose_kernel<L>, dim3((unsigned)std::min(32768, blocks_for(L, a.n_act))), dim3(256), 0, cx.s, a);
+    hipLaunchKernelGGL(ld_refine_propose_kernel<decltype(G)::value>, dim3(grid), dim3(256), 0, cx.s, a);
   });
 }
-static void launch_overflow_tier(LeidenCtx& cx, unsigned grid, const MoveArgs& a) {
-  hipLaunchKernelGGL(ld_move_kernel<64>, dim3(grid), dim3(256), 0, cx.s, a);
-}
-static void launch_overflow_tier(LeidenCtx& cx, unsigned grid, const ProposeArgs& a) {
-  hipLaunchKernelGGL(ld_refine_propose_kernel<64>, dim3(grid), dim3(256), 0, cx.s, a);
-}
-static void launch_hub_tier(LeidenCtx& cx, unsigned grid, const MoveArgs& a, HubTry ht) {
+static void launch_giant_tier(LeidenCtx& cx, unsigned grid, const MoveArgs& a, HubTry ht) {
   hipLaunchKernelGGL(ld_move_hub_kernel, dim3(grid), dim3(HUB_THREADS), HUB_LDS, cx.s, a, ht);
 }
-static void launch_hub_tier(LeidenCtx& cx, unsigned grid, const ProposeArgs& a, HubTry ht) {
+static void launch_giant_tier(LeidenCtx& cx, unsigned grid, const ProposeArgs& a, HubTry ht) {
   hipLaunchKernelGGL(ld_refine_propose_hub_kernel, dim3(grid), dim3(HUB_THREADS), HUB_LDS, cx.s, a, ht);
 }
 template <typename Args>
-static int decide_tiers(LeidenCtx& cx, const char* what, int n, int cls, int lanes, bool main, const int* hctr, const Args& a) {
-  const int n_mid = lanes != 64 ? hctr[CTR_N_MID] : 0, n_hub = hctr[CTR_N_HUB];
-  if (main) {
-    launch_main_tier(cx, lanes, a);
+static int decide_tiers(LeidenCtx& cx, const char* what, const LevelGraph& g, int cls, int lanes, const RequeueHead* rq, const int* hctr,
+                        Args a) {
+  const int n_mid = hctr[CTR_N_MID], n_blk = hctr[CTR_N_BLK], n_giant = hctr[CTR_N_GIANT];
+  const int n_main = a.n_act - n_mid - n_blk - n_giant;
+  const int* region = cx.b.tier_lists + (size_t)cls * g.n;
+  a.tl = TierLists{region, region + (g.n - 1), cx.b.giant_lists + (size_t)cls * giant_stride(g), n_mid, n_blk, n_giant,
+                   n_main > 0 ? std::min(main_grid_cap(a), blocks_for(lanes, a.n_act)) : 0,
+                   n_mid > 0 ? std::min(2048, blocks_for(64, n_mid)) : 0, std::min(BLK_GRID, n_blk)};
+  const int nb_rq = rq ? ceil_div(rq->n_act, 256) : 0;
+  const int grid = nb_rq + a.tl.nb_main + a.tl.nb_wave + a.tl.nb_blk;
+  if (grid > 0) {
+    launch_fused_tiers(cx, g, lanes, (unsigned)grid, rq, nb_rq, a);
     SCAMD_LAUNCH_CHECK();
-    LD_DBG_SYNC(cx, "%s<%d> n=%d class=%d cnt=%d", what, lanes, n, cls, a.n_act);
+    LD_DBG_SYNC(cx, "%s<%d> n=%d class=%d cnt=%d workgroups: re-queue %d main %d wave %d (%d rows) block %d (%d rows)", what, lanes, g.n,
+                cls, a.n_act, nb_rq, a.tl.nb_main, a.tl.nb_wave, n_mid, a.tl.nb_blk, n_blk);
   }
-  if (n_mid > 0) {
-    Args ovf = a;
-    ovf.sub_list = a.ovf_list;
-    ovf.sub_count = a.counters + CTR_OVF;
-    launch_overflow_tier(cx, (unsigned)std::min(2048, blocks_for(64, n_mid)), ovf);
+  if (n_giant > 0) {
+    launch_giant_tier(cx, (unsigned)std::min(HUB_GRID, n_giant), a, HubTry{cx.b.counters + PHASE_ERR, cx.hub_try_probes});
     SCAMD_LAUNCH_CHECK();
-    LD_DBG_SYNC(cx, "%s<64> overflow n=%d class=%d", what, n, cls);
-    g_ld_stats[ST_OVERFLOW_VERTICES] += n_mid;
+    LD_DBG_SYNC(cx, "%s giant tier n=%d class=%d rows=%d", what, g.n, cls, n_giant);
   }
-  if (n_hub > 0) {
-    launch_hub_tier(cx, (unsigned)std::min(HUB_GRID, n_hub), a, HubTry{cx.b.counters + PHASE_ERR, cx.hub_try_probes});
-    SCAMD_LAUNCH_CHECK();
-    LD_DBG_SYNC(cx, "%s hub n=%d class=%d", what, n, cls);
-    g_ld_stats[ST_HUB_VERTICES] += n_hub;
-  }
+  // (a 16- / 32-lane launch hands on every row beyond its table, whichever tier decides it)
+  if (lanes != 64) g_ld_stats[ST_OVERFLOW_VERTICES] += n_mid + n_blk + n_giant;
+  g_ld_stats[ST_HUB_VERTICES] += n_blk + n_giant;
   return SCAMD_OK;
 }
 
@@ -2990,7 +3076,6 @@ static int local_moving(LeidenCtx& cx, const LevelGraph& g, int* total_moves) {
   int rc = compute_totals(cx, g, b.comm, Filler().add(b.flag, sizeof(int) * n).add(b.counters, sizeof(int) * PH_PER_PHASE).add(b.rcounters, sizeof(int) * CTR_AREA));
   if (rc != SCAMD_OK) return rc;
   const int lanes = level_lanes(cx, g);
-  const int thr_mid = lanes_thr_mid(lanes);
   const int n_cls = lm_classes(cx, g.n);
   int moved_before = 0, quiet = 0, moved_prev2 = 0;
   for (int sweep = 0; sweep < MAX_LM_SWEEPS; ++sweep) {
@@ -2998,10 +3083,10 @@ static int local_moving(LeidenCtx& cx, const LevelGraph& g, int* total_moves) {
     int* sw = b.rcounters + (sweep & 1) * CTR_AREA;
     const unsigned int salt = hash32(cx.seed + 0x85EBCA77u * (unsigned int)(sweep + 1) + 0xC2B2AE3Du * (unsigned int)cx.iter);
     hipLaunchKernelGGL(ld_compact_cls_kernel, dim3((unsigned)ceil_div(g.n, 1024)), dim3(1024), 0, cx.s, g.n,
-                       sweep == 0 ? (int*)nullptr : b.flag, b.cls_lists, sw, n_cls, salt, g.indptr, thr_mid, (int)WH_MAX_DEG,
+                       sweep == 0 ? (int*)nullptr : b.flag, b.cls_lists, sw, n_cls, salt, tier_dst(cx, g, lanes),
                        b.rcounters + ((sweep + 1) & 1) * CTR_AREA, (int)CTR_AREA);
     SCAMD_LAUNCH_CHECK();
-    int hc[CTR_AREA], ht[PH_PER_PHASE];  // class list lengths, then per sub-round [CTR_N_MID] / [CTR_N_HUB]: long rows of the class
+    int hc[CTR_AREA], ht[PH_PER_PHASE];  // class list lengths, then per sub-round [CTR_N_MID] / [CTR_N_BLK] / [CTR_N_GIANT]: long rows of the class
     LD_FETCH(hc, sw, sizeof(int) * (MAX_CLASSES + CTR_STRIDE * n_cls), cx.s);
     LD_FETCH(ht, b.counters, sizeof(ht), cx.s);
     LD_SYNC(cx.s);
@@ -3012,10 +3097,11 @@ static int local_moving(LeidenCtx& cx, const LevelGraph& g, int* total_moves) {
     moved_before = ht[PH_MOVED];
     *total_moves = ht[PH_MOVED];
     if (cx.debug) {
-      int tot_mid = 0, tot_hub = 0;
-      for (int c = 0; c < n_cls; ++c) tot_mid += hc[MAX_CLASSES + CTR_STRIDE * c + CTR_N_MID], tot_hub += hc[MAX_CLASSES + CTR_STRIDE * c + CTR_N_HUB];
-      fprintf(stderr, "[leiden] lm n=%d sweep=%d classes=%d act=%d moved_prev=%d blocked_total=%d long rows: mid %d hub %d\n", g.n, sweep,
-              n_cls, n_act, moved_last, ht[PH_BLOCKED], tot_mid, tot_hub);
+      int tot[3] = {0, 0, 0};
+      for (int c = 0; c < n_cls; ++c)
+        for (int t = 0; t < 3; ++t) tot[t] += hc[MAX_CLASSES + CTR_STRIDE * c + CTR_N_MID + t];
+      fprintf(stderr, "[leiden] lm n=%d sweep=%d classes=%d act=%d moved_prev=%d blocked_total=%d long rows: wave %d block %d giant %d\n", g.n,
+              sweep, n_cls, n_act, moved_last, ht[PH_BLOCKED], tot[0], tot[1], tot[2]);
     }
     if (n_act == 0) break;
     ++g_ld_stats[ST_LM_SWEEPS];
@@ -3041,42 +3127,29 @@ static int local_moving(LeidenCtx& cx, const LevelGraph& g, int* total_moves) {
     // the direction rule is the termination guarantee only: synchronous sub-rounds without it converge in a few sweeps
     // on every graph tried, with it (round 2's scheme) about half of the wanted moves of a round were blocked
     const int dir_round = sweep >= LM_DIR_AFTER ? sweep : -1;
-    // the non-empty classes of the sweep, in order; the main decision kernel of sub-round i + 1 shares a launch with the
-    // re-queue of sub-round i (ld_requeue_move_kernel), the decisions alternate between two buffers
+    // the non-empty classes of the sweep, in order: [re-queue of sub-round i - 1 + all tiers of sub-round i] -> apply; the
+    // decisions alternate between two buffers (the re-queue reads those of the sub-round before)
     int cls[MAX_CLASSES], ncl = 0;
     for (int c = 0; c < n_cls; ++c)
       if (hc[c] > 0) cls[ncl++] = c;
     int* tgt[2] = {b.target, b.target2};
-    auto move_args = [&](int c, int* decision) {
-      return MoveArgs{hc[c], b.cls_lists + (size_t)c * n, nullptr, nullptr, g.indptr, g.indices, g.wq, g.k, b.comm, b.Ktot,
-                      b.csize, gg, dir_round, cx.seed, decision, b.mid_list, b.hub_list, sw + MAX_CLASSES + CTR_STRIDE * c};
-    };
+    RequeueHead prev{0, nullptr, nullptr};
     for (int i = 0; i < ncl; ++i) {
       const int c = cls[i];
       const int cnt = hc[c];
       const int* list = b.cls_lists + (size_t)c * n;
       int* tg = tgt[i & 1];
-      // (sub-rounds after the first: their main launch was the one that re-queued the sub-round before)
-      rc = decide_tiers(cx, "lm move", g.n, c, lanes, i == 0, hc + MAX_CLASSES + CTR_STRIDE * c, move_args(c, tg));
+      rc = decide_tiers(cx, "lm move", g, c, lanes, i > 0 ? &prev : nullptr, hc + MAX_CLASSES + CTR_STRIDE * c,
+                        MoveArgs{cnt, list, g.indptr, g.indices, g.wq, g.k, b.comm, b.Ktot, b.csize, gg, dir_round, cx.seed, tg, TierLists{}});
       if (rc != SCAMD_OK) return rc;
       hipLaunchKernelGGL(ld_apply_kernel, GRID1(cnt), 0, cx.s, cnt, list, tg, g.k, b.comm, b.Ktot, b.csize, b.flag,
                          b.counters);
       SCAMD_LAUNCH_CHECK();
-      if (i + 1 < ncl) {
-        const int cn = cls[i + 1];
-        const MoveArgs ma = move_args(cn, tgt[(i + 1) & 1]);
-        const int nb_rq = ceil_div(cnt, 256);
-        const dim3 grid((unsigned)(nb_rq + blocks_for(lanes, hc[cn])));
-        with_lanes<true>(lanes, [&](auto G) {
-          hipLaunchKernelGGL(ld_requeue_move_kernel<decltype(G)::value>, grid, dim3(256), 0, cx.s, nb_rq, cnt, list, (const int*)tg,
-                             g.indptr, g.indices, (const int*)b.comm, b.flag, ma);
-        });
-        SCAMD_LAUNCH_CHECK();
-      } else {
-        hipLaunchKernelGGL(ld_requeue_kernel, GRID1(cnt), 0, cx.s, cnt, list, tg, g.indptr, g.indices, b.comm, b.flag);
-        SCAMD_LAUNCH_CHECK();
-      }
+      prev = RequeueHead{cnt, list, tg};
     }
+    // (the last sub-round's movers: a launch of their own)
+    hipLaunchKernelGGL(ld_requeue_kernel, GRID1(prev.n_act), 0, cx.s, prev.n_act, prev.list, prev.decision, g.indptr, g.indices, b.comm, b.flag);
+    SCAMD_LAUNCH_CHECK();
   }
   return SCAMD_OK;
 }
@@ -3142,16 +3215,14 @@ static int polish_level0(LeidenCtx& cx, const LevelGraph& g, PolishPass* out) {
                                               .add(b.rcounters, sizeof(int) * CTR_AREA));
   if (rc != SCAMD_OK) return rc;  // (cx.b lives for this call only: an error return need not swap back)
   const int lanes = level_lanes(cx, g);
-  const int thr_mid = lanes_thr_mid(lanes);
   unsigned int round = 0, area = 0;  // (the rounds alternate between the two counter areas, as the sweeps of the local moving do)
   int moved_before = 0, moved_at_full = 0;
   int checked_at = 0;  // moves + splits when the communities were last known to be connected (the input is: an iteration's result)
   bool full = true;  // the next round decides for every vertex (else: for the flagged ones)
   for (;;) {
     int* sw = b.rcounters + (area & 1u) * CTR_AREA;
-    int* ctr = sw + MAX_CLASSES;  // counter block of the one class
     hipLaunchKernelGGL(ld_compact_cls_kernel, dim3((unsigned)ceil_div(g.n, 1024)), dim3(1024), 0, cx.s, g.n,
-                       full ? (int*)nullptr : b.flag, b.cls_lists, sw, 1, 0u, g.indptr, thr_mid, (int)WH_MAX_DEG,
+                       full ? (int*)nullptr : b.flag, b.cls_lists, sw, 1, 0u, tier_dst(cx, g, lanes),
                        b.rcounters + ((area + 1u) & 1u) * CTR_AREA, (int)(MAX_CLASSES + CTR_STRIDE));
     SCAMD_LAUNCH_CHECK();
     ++area;
@@ -3197,9 +3268,8 @@ static int polish_level0(LeidenCtx& cx, const LevelGraph& g, PolishPass* out) {
     ++round;
     ++ps.rounds;
     const int* list = b.cls_lists;
-    rc = decide_tiers(cx, "polish move", g.n, 0, lanes, true, hc + MAX_CLASSES,
-                      MoveArgs{cnt, list, nullptr, nullptr, g.indptr, g.indices, g.wq, g.k, b.comm, b.Ktot, b.csize, gg, -1, cx.seed,
-                               b.target, b.mid_list, b.hub_list, ctr});
+    rc = decide_tiers(cx, "polish move", g, 0, lanes, nullptr, hc + MAX_CLASSES,
+                      MoveArgs{cnt, list, g.indptr, g.indices, g.wq, g.k, b.comm, b.Ktot, b.csize, gg, -1, cx.seed, b.target, TierLists{}});
     if (rc != SCAMD_OK) return rc;
     hipLaunchKernelGGL(ld_polish_lock_kernel, GRID1(cnt), 0, cx.s, cnt, list, (const int*)b.target, (const int*)b.comm, lock, round);
     SCAMD_LAUNCH_CHECK();
@@ -3229,17 +3299,16 @@ static int refinement(LeidenCtx& cx, const LevelGraph& g, int* n_merged) {
   });
   SCAMD_LAUNCH_CHECK();
   const int n_cls = rf_classes(g.n);
-  int* rc0 = b.rcounters;  // [0, MAX_CLASSES): class list lengths; then per sub-round c: [CTR_JOINED], [CTR_HUB], [CTR_OVF]
+  int* rc0 = b.rcounters;  // [0, MAX_CLASSES): class list lengths; then per sub-round c: [CTR_JOINED], [CTR_N_MID], [CTR_N_BLK], [CTR_N_GIANT]
   // (also clears rc0, the phase counters and the join stamps b.touched: three memsets until round 6)
   hipLaunchKernelGGL(ld_refine_init_kernel, GRID1(g.n), 0, cx.s, g.n, g.k, b.a_in, b.comm, b.ref, b.refsize, b.Kref,
                      b.Eref, b.vrec, b.trec, b.touched, rc0, (int)(MAX_CLASSES + CTR_STRIDE * n_cls), b.counters);
   SCAMD_LAUNCH_CHECK();
   hipLaunchKernelGGL(ld_refine_candidates_kernel, dim3((unsigned)ceil_div(g.n, 1024)), dim3(1024), 0, cx.s, g.n, g.k,
-                     b.comm, b.Ktot, b.a_in, gg, b.cls_lists, rc0, n_cls, salt, g.indptr,
-                     lanes_thr_mid(lanes), (int)WH_MAX_DEG);
+                     b.comm, b.Ktot, b.a_in, gg, b.cls_lists, rc0, n_cls, salt, tier_dst(cx, g, lanes));
   SCAMD_LAUNCH_CHECK();
   LD_DBG_SYNC(cx, "rf candidates n=%d classes=%d", g.n, n_cls);
-  int hc[CTR_AREA];  // class list lengths, then per sub-round [CTR_N_MID] / [CTR_N_HUB] (ld_refine_candidates_kernel)
+  int hc[CTR_AREA];  // class list lengths, then per sub-round [CTR_N_MID] / [CTR_N_BLK] / [CTR_N_GIANT] (ld_refine_candidates_kernel)
   LD_FETCH(hc, rc0, sizeof(int) * (MAX_CLASSES + CTR_STRIDE * n_cls), cx.s);
   LD_SYNC(cx.s);
   *n_merged = 0;
@@ -3252,10 +3321,9 @@ static int refinement(LeidenCtx& cx, const LevelGraph& g, int* n_merged) {
     int* ctr = rc0 + MAX_CLASSES + CTR_STRIDE * c;
     const unsigned tgrid = (unsigned)std::min(32768, ceil_div(cnt, 256));
     const unsigned lgrid = (unsigned)std::min(32768, blocks_for(lanes, cnt));
-    int rc = decide_tiers(cx, "rf propose", g.n, c, lanes, true, hc + MAX_CLASSES + CTR_STRIDE * c,
-                          ProposeArgs{cnt, list, nullptr, nullptr, g.indptr, g.indices, g.wq, g.k, b.comm, b.Ktot, b.ref, b.refsize,
-                                      b.vrec, b.trec, RefineRule{gg, cx.inv_beta, c, n_cls, salt, rseed}, b.target, b.mid_list,
-                                      b.hub_list, ctr});
+    int rc = decide_tiers(cx, "rf propose", g, c, lanes, nullptr, hc + MAX_CLASSES + CTR_STRIDE * c,
+                          ProposeArgs{cnt, list, g.indptr, g.indices, g.wq, g.k, b.comm, b.Ktot, b.ref, b.refsize, b.vrec, b.trec,
+                                      RefineRule{gg, cx.inv_beta, c, n_cls, salt, rseed}, b.target, TierLists{}});
     if (rc != SCAMD_OK) return rc;
     hipLaunchKernelGGL(ld_refine_apply_kernel, dim3(tgrid), dim3(256), 0, cx.s, cnt, list, b.target, g.k, b.ref,
                        b.refsize, b.Kref, b.Eref, b.touched, c, b.rlist, ctr, b.vrec, b.trec);
@@ -3954,6 +4022,16 @@ extern "C" int scamd_leiden_debug_split_f32(const int64_t* indptr, const int32_t
 extern "C" void scamd_leiden_last_stats(int32_t* out, int n) {
   g_ld_stats[ST_LM_SWEEP_MB] = (int)std::min(2.0e9, g_ld_sweep_bytes / 1.0e6);
   for (int i = 0; i < n && i < LD_NSTATS; ++i) out[i] = g_ld_stats[i];
+}
+
+// the longest rows of the decide tiers at `lanes` lanes per vertex (long_row_tier), for the tests that build rows at them
+extern "C" int scamd_leiden_tier_bounds(int lanes, int* main_max, int* wave_max, int* block_max) {
+  SCAMD_REQUIRE(lanes == 16 || lanes == 32 || lanes == 64, SCAMD_EINVAL, "leiden tier bounds: lanes must be 16, 32 or 64");
+  const int thr_mid = lanes_thr_mid(lanes);
+  if (main_max) *main_max = thr_mid >= 0 ? thr_mid : (int)WH_MAX_DEG;
+  if (wave_max) *wave_max = WH_MAX_DEG;
+  if (block_max) *block_max = BLK_MAX_DEG;
+  return SCAMD_OK;
 }
 
 // key of a statistics slot (LD_STAT_NAMES); NULL: no such slot, or the unused one
