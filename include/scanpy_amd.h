@@ -281,6 +281,52 @@ int scamd_spectral_embedding_f32(const int64_t* indptr, const int32_t* indices, 
                                  int64_t nnz, int dim, uint64_t seed, double tol, int max_outer, int max_degree,
                                  double* out, double* info_host, void* workspace, size_t workspace_bytes,
                                  scamd_stream_t stream);
+/* The symmetrised transition matrix of diffusion maps, `Neighbors.compute_transitions`
+ * (src/scanpy/neighbors/__init__.py:805-827): dens = column sums of the symmetric graph, K_ij = A_ij / (dens_i dens_j)
+ * (density_normalize != 0; K = A otherwise), z_i = sqrt(sum_j K_ij), T_sym_ij = K_ij / (z_i z_j).
+ *   indptr / indices / weights: the symmetric graph (device CSR, n x n, positive weights)
+ *   t_sym [nnz] float32 (device): T_sym on the same pattern, every entry computed in float64 and rounded once
+ *   z [n] float64 (device): the reference's `Z` is diag(1 / z)
+ * Sums are float64 in a fixed order (one wave per row).  SCAMD_EUNSUPPORTED when a row has no positive weight. */
+size_t scamd_transitions_sym_workspace_bytes(int64_t n, int64_t nnz);
+int scamd_transitions_sym_f32(const int64_t* indptr, const int32_t* indices, const float* weights, int64_t n,
+                              int64_t nnz, int density_normalize, float* t_sym, double* z, void* workspace,
+                              size_t workspace_bytes, scamd_stream_t stream);
+/* The n_comps leading eigenpairs of T_sym, `Neighbors.compute_eigen(sort='decrease')`
+ * (src/scanpy/neighbors/__init__.py:864-895: scipy `eigsh(which='LM')`, ARPACK on one host thread): Chebyshev-filtered
+ * subspace iteration on (T_sym + I) / 2 with a block of n_comps + 6 <= 32 columns, float32 SpMM operand, float64 elsewhere,
+ * bitwise reproducible.
+ *   indptr / indices / t_sym: T_sym (device CSR, n x n, no empty row); 1 <= n_comps <= 26; n > max(n_comps + 6, 8)
+ *   evals [n_comps] float64 (device), descending; evecs [n x n_comps] float64 (device): unit norm, mutually orthogonal,
+ *   column 0 the stationary one (z / |z|); in every column the entry of largest magnitude is positive (lowest row on ties)
+ *   info_host (optional, 8 doubles): outer iterations, operator applications, residual of the wanted Ritz pairs of
+ *             (T_sym + I) / 2 (half that of the pairs of T_sym), 1 if it is below `tol` (2e-6 is what the float32 operand
+ *             allows), the estimate of lambda_min, operator applications of its run, 1 if the guard refused, failed Cholesky
+ *             attempts
+ *   max_outer / max_degree: bounds of the iteration (60 / 64 in the Python layer)
+ * Largest magnitude against largest algebraic value: the filter finds the largest algebraic eigenvalues, ARPACK is asked for
+ * the largest magnitudes; a second run on (I - T_sym) / 2 (block of 8, one pair, tol 1e-3) estimates lambda_min, and the
+ * entry returns SCAMD_EUNSUPPORTED (info_host filled, [6] = 1) when -lambda_min >= evals[n_comps - 1].  A Ritz value bounds
+ * lambda_min from ABOVE: the guard can prove a conflict, never the absence of one.
+ * SCAMD_EUNSUPPORTED also for n_comps > 26, n too small for the block, an empty row, and a block that cannot be
+ * orthonormalised. */
+size_t scamd_diffmap_workspace_bytes(int64_t n, int64_t nnz, int n_comps);
+int scamd_diffmap_f32(const int64_t* indptr, const int32_t* indices, const float* t_sym, int64_t n, int64_t nnz,
+                      int n_comps, uint64_t seed, double tol, int max_outer, int max_degree, double* evals,
+                      double* evecs, double* info_host, void* workspace, size_t workspace_bytes,
+                      scamd_stream_t stream);
+/* Diffusion pseudotime from one root: `_get_dpt_row(iroot)` followed by `_set_pseudotime`
+ * (src/scanpy/neighbors/__init__.py:920-953): d_v = sqrt(sum_j w_j (basis[iroot][j] - basis[v][j])^2) with
+ * w_j = (lambda_j / (1 - lambda_j))^2 for lambda_j < 0.9994 and 1 otherwise, +inf outside the root's connected component,
+ * divided by the largest finite entry when scale != 0 (the pseudotime) and left as it is when scale == 0 (the row of
+ * `distances_dpt`).  Float64 accumulation (j ascending), the maximum by a two-stage reduction, the result rounded to
+ * float32 once.
+ *   evals [n_dcs] float32, basis [n x ld] float32 (ld >= n_dcs, n_dcs <= 128), labels [n] int32 component ids or NULL (one
+ *   component) -- all on the device; out [n] float32 (device) */
+size_t scamd_dpt_pseudotime_workspace_bytes(int64_t n);
+int scamd_dpt_pseudotime_f32(const float* evals, const float* basis, int64_t n, int n_dcs, int64_t ld, int64_t iroot,
+                             const int32_t* labels, int scale, float* out, void* workspace, size_t workspace_bytes,
+                             scamd_stream_t stream);
 /* colsum[l] (float64) = 1^T Y for Y [n, l] float32, fixed summation order. */
 size_t scamd_colsum_workspace_bytes(int l);
 int scamd_colsum_f32_f64(const float* y, int64_t n, int l, double* colsum,

@@ -457,6 +457,69 @@ def spectral_embedding(indptr: torch.Tensor, indices: torch.Tensor, weights: tor
                  "converged": bool(info[3] > 0.5), "ritz_values": [float(info[4 + j]) for j in range(min(dim, 4))]}
 
 
+def transitions_sym(indptr: torch.Tensor, indices: torch.Tensor, weights: torch.Tensor, n: int, *, density_normalize: bool = True):
+    """`scamd_transitions_sym_f32`: T_sym on the pattern of the symmetric graph (float32 [nnz]) and z (float64 [n]), on the device."""
+    dev = require_gpu()
+    lib = _lib.load()
+    indptr = indptr.to(torch.int64).contiguous()
+    indices = indices.to(torch.int32).contiguous()
+    weights = weights.to(torch.float32).contiguous()
+    nnz = weights.numel()
+    t_sym = _empty(nnz, dtype=torch.float32, device=dev)
+    z = _empty(n, dtype=torch.float64, device=dev)
+    ws, wsz = _ws(lib.scamd_transitions_sym_workspace_bytes(n, nnz), dev)
+    rc = lib.scamd_transitions_sym_f32(ptr(indptr), ptr(indices), ptr(weights), n, nnz, 1 if density_normalize else 0, ptr(t_sym),
+                                       ptr(z), ptr(ws), wsz, stream_ptr())
+    _check(rc, "scamd_transitions_sym_f32")
+    return t_sym, z
+
+
+def diffmap(indptr: torch.Tensor, indices: torch.Tensor, t_sym: torch.Tensor, n: int, n_comps: int, *, seed: int = 0,
+            tol: float = 2e-6, max_outer: int = 60, max_degree: int = 64):
+    """`scamd_diffmap_f32`: the `n_comps` leading eigenpairs of T_sym -> (evals float64 [n_comps], evecs float64 [n, n_comps]) on
+    the device + info (`_lib.diffmap_info`).  NotImplementedError when the largest-magnitude guard refuses the graph."""
+    dev = require_gpu()
+    lib = _lib.load()
+    indptr = indptr.to(torch.int64).contiguous()
+    indices = indices.to(torch.int32).contiguous()
+    t_sym = t_sym.to(torch.float32).contiguous()
+    nnz = t_sym.numel()
+    need = lib.scamd_diffmap_workspace_bytes(n, nnz, int(n_comps))
+    if need == 0:
+        raise _lib.ScamdError(f"diffmap: unsupported shape n={n} n_comps={n_comps} (1 to 26 components)")
+    evals = _empty(int(n_comps), dtype=torch.float64, device=dev)
+    evecs = _empty((n, int(n_comps)), dtype=torch.float64, device=dev)
+    ws, wsz = _ws(need, dev)
+    info = (C.c_double * _lib.DIFFMAP_INFO_WORDS)()
+    rc = lib.scamd_diffmap_f32(ptr(indptr), ptr(indices), ptr(t_sym), n, nnz, int(n_comps), int(seed) & (2**64 - 1), float(tol),
+                               int(max_outer), int(max_degree), ptr(evals), ptr(evecs), info, ptr(ws), wsz, stream_ptr())
+    refused = _lib.diffmap_guard_error(rc, info, int(n_comps))
+    if refused is not None:
+        _guards.clear()
+        raise refused
+    _check(rc, "scamd_diffmap_f32")
+    return evals, evecs, _lib.diffmap_info(info)
+
+
+def dpt_pseudotime(evals: torch.Tensor, basis: torch.Tensor, iroot: int, labels: torch.Tensor | None = None, *,
+                   scale: bool = True) -> torch.Tensor:
+    """`scamd_dpt_pseudotime_f32`: evals float32 [n_dcs], basis float32 [n, ld >= n_dcs], labels int32 [n] or None -> float32 [n]:
+    the DPT distances from `iroot`, divided by their largest finite value when `scale` (the pseudotime)."""
+    dev = require_gpu()
+    lib = _lib.load()
+    assert evals.dtype == torch.float32 and basis.dtype == torch.float32 and basis.dim() == 2
+    evals, basis = evals.contiguous(), basis.contiguous()
+    n, ld = basis.shape
+    if labels is not None:
+        labels = labels.to(torch.int32).contiguous()
+    out = _empty(n, dtype=torch.float32, device=dev)
+    ws, wsz = _ws(lib.scamd_dpt_pseudotime_workspace_bytes(n), dev)
+    rc = lib.scamd_dpt_pseudotime_f32(ptr(evals), ptr(basis), n, evals.numel(), ld, int(iroot), ptr(labels), 1 if scale else 0,
+                                      ptr(out), ptr(ws), wsz, stream_ptr())
+    _check(rc, "scamd_dpt_pseudotime_f32")
+    return out
+
+
 def colsum(y: torch.Tensor) -> torch.Tensor:
     dev = require_gpu()
     lib = _lib.load()

@@ -55,6 +55,12 @@ SIGNATURES = {
     "scamd_pca_solve_gram_f64": (_i32, [_vp, _i64, _vp, _i64, _i64, _i32, _i32, _i32, _u64, _f64, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _sz, _vp]),
     "scamd_spectral_embedding_workspace_bytes": (_sz, [_i64, _i64, _i32]),
     "scamd_spectral_embedding_f32": (_i32, [_vp, _vp, _vp, _i64, _i64, _i32, _u64, _f64, _i32, _i32, _vp, C.POINTER(_f64), _vp, _sz, _vp]),
+    "scamd_transitions_sym_workspace_bytes": (_sz, [_i64, _i64]),
+    "scamd_transitions_sym_f32": (_i32, [_vp, _vp, _vp, _i64, _i64, _i32, _vp, _vp, _vp, _sz, _vp]),
+    "scamd_diffmap_workspace_bytes": (_sz, [_i64, _i64, _i32]),
+    "scamd_diffmap_f32": (_i32, [_vp, _vp, _vp, _i64, _i64, _i32, _u64, _f64, _i32, _i32, _vp, _vp, C.POINTER(_f64), _vp, _sz, _vp]),
+    "scamd_dpt_pseudotime_workspace_bytes": (_sz, [_i64]),
+    "scamd_dpt_pseudotime_f32": (_i32, [_vp, _vp, _i64, _i32, _i64, _i64, _vp, _i32, _vp, _vp, _sz, _vp]),
     "scamd_colsum_workspace_bytes": (_sz, [_i32]),
     "scamd_colsum_f32_f64": (_i32, [_vp, _i64, _i32, _vp, _vp, _sz, _vp]),
     "scamd_leiden_workspace_bytes": (_sz, [_i64, _i64]),
@@ -115,6 +121,27 @@ def leiden_stat_names(lib: C.CDLL) -> list:
     while names and names[-1] is None:
         names.pop()
     return [None if k is None else k.decode() for k in names]
+
+
+EUNSUPPORTED = -4
+DIFFMAP_INFO_WORDS = 8
+
+
+def diffmap_info(info) -> dict:
+    """the 8 doubles `scamd_diffmap_f32` reports (include/scanpy_amd.h) under their names"""
+    return {"outer_iterations": int(info[0]), "operator_applications": int(info[1]), "residual": float(info[2]),
+            "converged": bool(info[3] > 0.5), "lambda_min_estimate": float(info[4]), "guard_applications": int(info[5]),
+            "guard_refused": bool(info[6] > 0.5), "chol_retries": int(info[7])}
+
+
+def diffmap_guard_error(rc: int, info, n_comps: int):
+    """-> the NotImplementedError for a run of `scamd_diffmap_f32` that its largest-magnitude guard refused, else None"""
+    if rc == EUNSUPPORTED and info[6] > 0.5:
+        return NotImplementedError(
+            f"diffmap: the graph has a negative eigenvalue (at most {float(info[4]):.4f}) of larger magnitude than the last "
+            f"requested component (n_comps={n_comps}); scipy's eigsh(which='LM') would return it, the device solver finds "
+            "the largest algebraic eigenvalues only.")
+    return None
 
 
 def check(rc: int, what: str = "") -> None:

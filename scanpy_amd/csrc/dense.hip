@@ -19,7 +19,8 @@
 // Contents, in order: the float64 kernels (GEMM, Cholesky factor, panel x small, Jacobi, residuals, model finalisation);
 // `DenseOp` + `dense_topk` (scamd_eigh_topk_f64, scamd_dense_debug_f64); the batched, deflated solve and the dense half of the
 // Gram-route PCA (scamd_pca_solve_gram_f64, scamd_pca_csr_f32); the sp_* kernels, `SpectralOp` and the spectral
-// initialisation of the UMAP layout (scamd_spectral_embedding_f32).
+// initialisation of the UMAP layout (scamd_spectral_embedding_f32); `DiffmapOp` and the diffusion-map entries
+// (scamd_transitions_sym_f32, scamd_diffmap_f32, scamd_dpt_pseudotime_f32).
 // Algorithmic work at g = 2000, b = 128: 2 g^2 b = 1.0e9 flop per operator application (~13 us at the 78.6 TFLOP/s
 // float64 matrix peak), ~11-26 applications; everything else is O(g b^2) or O(b^3).
 #include "common.h"
@@ -1272,7 +1273,8 @@ extern "C" int scamd_pca_csr_f32(const int64_t* indptr, const int32_t* indices, 
 // fixed order (bitwise reproducible).
 // =====================================================================================================================
 namespace scamd {
-constexpr int SP_MAXB = 16;
+constexpr int SP_MAXB = 16;   // the block of the spectral initialisation (dim + 6 <= 16): the narrow instantiation of the panel kernels
+constexpr int SP_WIDEB = 32;  // the block of the diffusion map (n_comps + 6 <= 32): the wide one
 constexpr int SP_GRID = 1024;
 
 // deg[v] = sum of the row (float64), one wave per row
@@ -1303,27 +1305,49 @@ __global__ __launch_bounds__(256) void sp_scale_kernel(const int64_t* __restrict
     s[e] = (float)((double)w[e] * dis_v * dis_u);
   }
 }
-// part[blk][i * bq + j] = sum over the block's rows of p[row][i] q[row][j]   (p: n x bp, q: n x bq, both <= 16 columns).
-// 256 threads = the 16 x 16 output entries; 64 rows at a time staged through LDS.
+// part[blk][i * bq + j] = sum over the block's rows of p[row][i] q[row][j]   (p: n x bp, q: n x bq, both <= W columns).
+// 256 threads = 16 x 16 thread positions, each owning the (W / 16)^2 outputs (i + 16 a, j + 16 c); 64 rows at a time staged
+// through LDS.  W = 16 is the thread map and summation order the spectral initialisation has always had (its pinned
+// iteration counts depend on it); W = 32 (the diffusion map's block, up to 32 columns) gives a thread 2 x 2 outputs: 4
+// accumulators (8 VGPRs) fed by 2 + 2 LDS reads per row -- by this count nowhere near the register budget; neither the
+// registers nor the LDS traffic of the wide instantiation were measured (the step is O(n b^2) beside the SpMM).  LDS, W = 32: 2 x 64 x 33
+// doubles = 33 KB.  The row stride of W + 1 doubles is odd, so the staging writes of a wave (consecutive e: consecutive
+// columns, then the next row) fall on consecutive banks but for the one-double pad per row; in the product loop the four
+// i of a wave read one address each (broadcast) and its 16 j read 16 consecutive doubles: no bank is asked twice.
+template <int W>
 __global__ __launch_bounds__(256) void sp_tall_gram_kernel(const double* __restrict__ p, int bp, const double* __restrict__ q,
                                                            int bq, int64_t n, double* __restrict__ part) {
-  __shared__ double sp[64][SP_MAXB + 1], sq[64][SP_MAXB + 1];
+  constexpr int R = W / 16;
+  __shared__ double sp[64][W + 1], sq[64][W + 1];
   const int i = threadIdx.x >> 4, j = threadIdx.x & 15;
   const int64_t rows_per = (n + gridDim.x - 1) / gridDim.x;
   const int64_t r0 = (int64_t)blockIdx.x * rows_per, r1 = r0 + rows_per < n ? r0 + rows_per : n;
-  double acc = 0.0;
+  double acc[R][R];
+#pragma unroll
+  for (int a = 0; a < R; ++a)
+#pragma unroll
+    for (int c = 0; c < R; ++c) acc[a][c] = 0.0;
   for (int64_t base = r0; base < r1; base += 64) {
     const int cnt = (int)(r1 - base < 64 ? r1 - base : 64);
-    for (int e = threadIdx.x; e < 64 * SP_MAXB; e += 256) {
-      const int r = e >> 4, c = e & 15;
+    for (int e = threadIdx.x; e < 64 * W; e += 256) {
+      const int r = e / W, c = e % W;
       sp[r][c] = (r < cnt && c < bp) ? p[(base + r) * bp + c] : 0.0;
       sq[r][c] = (r < cnt && c < bq) ? q[(base + r) * bq + c] : 0.0;
     }
     __syncthreads();
-    for (int r = 0; r < 64; ++r) acc = fma(sp[r][i], sq[r][j], acc);
+    for (int r = 0; r < 64; ++r) {
+#pragma unroll
+      for (int a = 0; a < R; ++a)
+#pragma unroll
+        for (int c = 0; c < R; ++c) acc[a][c] = fma(sp[r][i + 16 * a], sq[r][j + 16 * c], acc[a][c]);
+    }
     __syncthreads();
   }
-  if (i < bp && j < bq) part[(int64_t)blockIdx.x * (bp * bq) + i * bq + j] = acc;
+#pragma unroll
+  for (int a = 0; a < R; ++a)
+#pragma unroll
+    for (int c = 0; c < R; ++c)
+      if (i + 16 * a < bp && j + 16 * c < bq) part[(int64_t)blockIdx.x * (bp * bq) + (i + 16 * a) * bq + j + 16 * c] = acc[a][c];
 }
 // out[e] = sum over the blocks in index order
 __global__ void sp_reduce_kernel(const double* __restrict__ part, int nblk, int cnt, double* __restrict__ out) {
@@ -1347,29 +1371,34 @@ __global__ void sp_to_f32_kernel(const double* __restrict__ y, int64_t count, fl
   const int64_t e = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
   if (e < count) out[e] = (float)y[e];
 }
-// out = a * (M y - center y) - bcoef * yprev with M y = (S y + y) / 2; a = 1, center = 0, bcoef = 0: out = M y
+// out = a * (M y - center y) - bcoef * yprev with M y = (sgn S y + y) / 2; a = 1, center = 0, bcoef = 0: out = M y.
+// sgn = 1: the upper end of S's spectrum (multiplying by 1.0 is exact); sgn = -1: its lower end (the diffusion map's guard)
 __global__ void sp_cheb_kernel(int64_t count, const float* __restrict__ sy, const double* __restrict__ y,
-                               const double* __restrict__ yprev, double a, double center, double bcoef, double* __restrict__ out) {
+                               const double* __restrict__ yprev, double sgn, double a, double center, double bcoef,
+                               double* __restrict__ out) {
   const int64_t e = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
   if (e >= count) return;
   const double yy = y[e];
-  const double my = 0.5 * ((double)sy[e] + yy);
+  const double my = 0.5 * (sgn * (double)sy[e] + yy);
   double r = a * (my - center * yy);
   if (bcoef != 0.0) r -= bcoef * yprev[e];
   out[e] = r;
 }
-// part[blk][j] = sum over the block's rows of (mv[row][j] - theta[j] v[row][j])^2, j < dim
+// part[blk][j] = sum over the block's rows of (mv[row][j] - theta[j] v[row][j])^2, j < dim <= W
+// (256 / W row lanes x W columns; W = 16: the map the spectral initialisation has always had)
+template <int W>
 __global__ __launch_bounds__(256) void sp_resid_kernel(const double* __restrict__ v, const double* __restrict__ mv,
                                                        const double* __restrict__ theta, int64_t n, int b, int dim,
                                                        double* __restrict__ part) {
+  constexpr int RL = 256 / W;
   __shared__ double red[256];
-  const int j = threadIdx.x & 15, rl = threadIdx.x >> 4;  // 16 row lanes x 16 columns
+  const int j = threadIdx.x % W, rl = threadIdx.x / W;
   const int64_t rows_per = (n + gridDim.x - 1) / gridDim.x;
   const int64_t r0 = (int64_t)blockIdx.x * rows_per, r1 = r0 + rows_per < n ? r0 + rows_per : n;
   double acc = 0.0;
   if (j < dim) {
     const double th = theta[j];
-    for (int64_t r = r0 + rl; r < r1; r += 16) {
+    for (int64_t r = r0 + rl; r < r1; r += RL) {
       const double d = mv[r * b + j] - th * v[r * b + j];
       acc = fma(d, d, acc);
     }
@@ -1378,7 +1407,7 @@ __global__ __launch_bounds__(256) void sp_resid_kernel(const double* __restrict_
   __syncthreads();
   if (rl == 0) {
     double s = 0.0;
-    for (int k = 0; k < 16; ++k) s += red[k * 16 + j];
+    for (int k = 0; k < RL; ++k) s += red[k * W + j];
     if (j < dim) part[(int64_t)blockIdx.x * dim + j] = s;
   }
 }
@@ -1394,33 +1423,38 @@ struct SpectralBuffers {
   double* deg; double* t0; float* s; double* pan[7]; float* y32; float* sy32; double* part;
   SubspaceScratch w; double* cvec; double* nrm2; double* rnorm;
 };
+// b <= SP_MAXB: the sizes the spectral initialisation has always carved; beyond it the small matrices hold SP_WIDEB columns
 static void spectral_carve(Workspace& ws, int64_t n, int64_t nnz, int b, SpectralBuffers* sb) {
+  const int maxb = b <= SP_MAXB ? SP_MAXB : SP_WIDEB;
   sb->deg = ws.take<double>((size_t)n);
   sb->t0 = ws.take<double>((size_t)n);
   sb->s = ws.take<float>((size_t)std::max<int64_t>(nnz, 1));
   for (int i = 0; i < 7; ++i) sb->pan[i] = ws.take<double>((size_t)n * b);
   sb->y32 = ws.take<float>((size_t)n * b);
   sb->sy32 = ws.take<float>((size_t)n * b);
-  sb->part = ws.take<double>((size_t)SP_GRID * SP_MAXB * SP_MAXB);
-  sb->w.gm = ws.take<double>(SP_MAXB * SP_MAXB);
-  sb->w.smat = ws.take<double>(SP_MAXB * SP_MAXB);
-  sb->w.tmat = ws.take<double>(SP_MAXB * SP_MAXB);
-  sb->w.ymat = ws.take<double>(SP_MAXB * SP_MAXB);
-  sb->w.theta = ws.take<double>(SP_MAXB);
-  sb->cvec = ws.take<double>(SP_MAXB);
+  sb->part = ws.take<double>((size_t)SP_GRID * maxb * maxb);
+  sb->w.gm = ws.take<double>(maxb * maxb);
+  sb->w.smat = ws.take<double>(maxb * maxb);
+  sb->w.tmat = ws.take<double>(maxb * maxb);
+  sb->w.ymat = ws.take<double>(maxb * maxb);
+  sb->w.theta = ws.take<double>(maxb);
+  sb->cvec = ws.take<double>(maxb);
   sb->nrm2 = ws.take<double>(8);
-  sb->rnorm = ws.take<double>(SP_MAXB);
+  sb->rnorm = ws.take<double>(maxb);
   sb->w.flags = ws.take<int>(8);
 }
 
 // the spectral operator: M = (S + I) / 2 on n x b panels, S = D^-1/2 A D^-1/2 as the float32 SpMM of pca.hip; every reduction
-// over the n rows is a two-stage sum in a fixed order
+// over the n rows is a two-stage sum in a fixed order.  b <= SP_MAXB runs the narrow instantiation of the panel kernels,
+// b <= SP_WIDEB the wide one.
 struct SpectralOp {
   hipStream_t s;
   const int64_t* indptr;
   const int32_t* indices;
+  const float* sval;  // the entries of S (float32) on the pattern of indptr / indices
   int64_t n;
   int b, dim;
+  double sgn = 1.0;  // M = (sgn S + I) / 2
   SpectralBuffers sb;
   SubspaceScratch w;
   const char* who = "spectral init";
@@ -1431,9 +1465,24 @@ struct SpectralOp {
   // out[bp x bq] = p^T q over the n rows
   int gram(const double* p, int bp, const double* q, int bq, double* out) {
     const int g = grid_rows();
-    hipLaunchKernelGGL(sp_tall_gram_kernel, dim3(g), dim3(256), 0, s, p, bp, q, bq, n, sb.part);
+    if (bp <= SP_MAXB && bq <= SP_MAXB)
+      hipLaunchKernelGGL(sp_tall_gram_kernel<SP_MAXB>, dim3(g), dim3(256), 0, s, p, bp, q, bq, n, sb.part);
+    else
+      hipLaunchKernelGGL(sp_tall_gram_kernel<SP_WIDEB>, dim3(g), dim3(256), 0, s, p, bp, q, bq, n, sb.part);
     SCAMD_LAUNCH_CHECK();
-    hipLaunchKernelGGL(sp_reduce_kernel, dim3(1), dim3(256), 0, s, sb.part, g, bp * bq, out);
+    hipLaunchKernelGGL(sp_reduce_kernel, dim3((unsigned)((bp * bq + 255) / 256)), dim3(256), 0, s, sb.part, g, bp * bq, out);
+    SCAMD_LAUNCH_CHECK();
+    return SCAMD_OK;
+  }
+  // rnorm[j] = |mv_j - theta_j v_j|^2, j < dim
+  int residuals(const double* v, const double* mv) {
+    const int g = grid_rows();
+    if (b <= SP_MAXB)
+      hipLaunchKernelGGL(sp_resid_kernel<SP_MAXB>, dim3(g), dim3(256), 0, s, v, mv, (const double*)w.theta, n, b, dim, sb.part);
+    else
+      hipLaunchKernelGGL(sp_resid_kernel<SP_WIDEB>, dim3(g), dim3(256), 0, s, v, mv, (const double*)w.theta, n, b, dim, sb.part);
+    SCAMD_LAUNCH_CHECK();
+    hipLaunchKernelGGL(sp_reduce_kernel, dim3(1), dim3(256), 0, s, (const double*)sb.part, g, dim, sb.rnorm);
     SCAMD_LAUNCH_CHECK();
     return SCAMD_OK;
   }
@@ -1450,14 +1499,84 @@ struct SpectralOp {
     const int64_t cnt = n * b;
     hipLaunchKernelGGL(sp_to_f32_kernel, dim3(egrid()), dim3(256), 0, s, y, cnt, sb.y32);
     SCAMD_LAUNCH_CHECK();
-    int rc = scamd_spmm_csr_f32(indptr, indices, sb.s, n, n, sb.y32, b, nullptr, sb.sy32, s);
+    int rc = scamd_spmm_csr_f32(indptr, indices, sval, n, n, sb.y32, b, nullptr, sb.sy32, s);
     if (rc != SCAMD_OK) return rc;
-    hipLaunchKernelGGL(sp_cheb_kernel, dim3(egrid()), dim3(256), 0, s, cnt, (const float*)sb.sy32, y, yprev, a, center, bcoef, out);
+    hipLaunchKernelGGL(sp_cheb_kernel, dim3(egrid()), dim3(256), 0, s, cnt, (const float*)sb.sy32, y, yprev, sgn, a, center, bcoef, out);
     SCAMD_LAUNCH_CHECK();
     ++n_apply;
     return SCAMD_OK;
   }
 };
+// the diffusion map's operator: M = (sgn T_sym + I) / 2 with T_sym handed in as it is stored -- the same panels, SpMM and
+// reductions, and NO deflation: the stationary eigenvector is part of the answer (column 0 of `sc.tl.diffmap`)
+struct DiffmapOp : SpectralOp {
+  int deflate(double*) { return SCAMD_OK; }
+};
+
+struct SubspaceRun {
+  int outer = 0;
+  double resid = INFINITY;
+};
+// The outer iteration over a graph operator (SpectralOp, DiffmapOp): random start block, then Rayleigh-Ritz, residual of the
+// cx.dim wanted Ritz pairs (|M| = 1: absolute = relative), Chebyshev filter of [0, smallest Ritz value], deflation, CholeskyQR2
+// until the residual is below tol or max_outer is reached.  Leaves the Ritz vectors in pan[3], M times them in pan[4], the
+// Ritz values of M in h_theta [b] (descending) and on the device in w.theta.  The caller owns a HostReadbackScope and ends with
+// a SCAMD_READBACK_SYNC after its own last launch: a loop that ends by max_outer leaves the last theta queued.
+template <class Op>
+static int graph_subspace_iteration(Op& cx, unsigned int seed, double tol, int max_outer, int max_degree, double* h_theta,
+                                    SubspaceRun* run) {
+  SpectralBuffers& sb = cx.sb;
+  hipStream_t s = cx.s;
+  const int64_t n = cx.n;
+  const int b = cx.b, dim = cx.dim;
+  double *z = sb.pan[0], *tmp = sb.pan[1], *mz = sb.pan[2], *v = sb.pan[3], *mv = sb.pan[4], *y0 = sb.pan[5], *y1 = sb.pan[6];
+  const int64_t cnt = n * b;
+  hipLaunchKernelGGL(randn_kernel, dim3(cx.egrid()), dim3(256), 0, s, z, cnt, seed);
+  SCAMD_LAUNCH_CHECK();
+  int rc = cx.deflate(z);
+  if (rc != SCAMD_OK) return rc;
+  rc = cholqr2(cx, z, tmp, y0, false, 2);
+  if (rc != SCAMD_OK) return rc;
+  rc = rayleigh_ritz(cx, y0, mz, v, mv, h_theta);
+  if (rc != SCAMD_OK) return rc;
+  double resid = INFINITY;
+  int outer = 0;
+  for (outer = 1; outer <= max_outer; ++outer) {
+    rc = cx.residuals(v, mv);
+    if (rc != SCAMD_OK) return rc;
+    double h_r[SP_WIDEB];
+    SCAMD_READBACK(h_r, sb.rnorm, sizeof(double) * dim, s);
+    SCAMD_READBACK_SYNC(s);  // (also completes the copy of theta)
+    resid = 0.0;
+    for (int j = 0; j < dim; ++j) resid = std::max(resid, std::sqrt(std::max(h_r[j], 0.0)));
+    if (resid < tol) break;
+    const double c = h_theta[b - 1];
+    double* blk = nullptr;  // the block that is orthonormalised next
+    if (!(c > 0.0 && c < 1.0)) {
+      // a degenerate block: one plain step, on a COPY (mv is an output of the Rayleigh-Ritz that follows)
+      rc = cx.deflate(mv);
+      if (rc != SCAMD_OK) return rc;
+      hipLaunchKernelGGL(axpby_kernel, dim3(cx.egrid()), dim3(256), 0, s, cnt, 1.0, (const double*)mv, 0.0, (const double*)mv, y0);
+      SCAMD_LAUNCH_CHECK();
+      blk = y0;
+    } else {
+      // the degree: as high as the amplification spread inside the wanted set allows; the spectrum's upper end is 1
+      const int m = chebyshev_degree(c, 1.0, h_theta[dim - 1], max_degree);
+      rc = chebyshev_filter(cx, v, mv, c, 1.0, m, y0, y1, z, &blk);
+      if (rc != SCAMD_OK) return rc;
+      rc = cx.deflate(blk);
+      if (rc != SCAMD_OK) return rc;
+    }
+    double* zq = blk == y0 ? y1 : y0;  // (tmp never joins the filter's rotation)
+    rc = cholqr2(cx, blk, tmp, zq, false, 2);
+    if (rc != SCAMD_OK) return rc;
+    rc = rayleigh_ritz(cx, zq, mz, v, mv, h_theta);
+    if (rc != SCAMD_OK) return rc;
+  }
+  run->outer = std::min(outer, max_outer);
+  run->resid = resid;
+  return SCAMD_OK;
+}
 }  // namespace scamd
 
 extern "C" size_t scamd_spectral_embedding_workspace_bytes(int64_t n, int64_t nnz, int dim) {
@@ -1487,6 +1606,7 @@ extern "C" int scamd_spectral_embedding_f32(const int64_t* indptr, const int32_t
   Workspace ws(workspace, workspace_bytes);
   spectral_carve(ws, n, nnz, b, &cx.sb);
   cx.w = cx.sb.w;
+  cx.sval = cx.sb.s;
   SCAMD_REQUIRE(workspace && ws.ok, SCAMD_EWORKSPACE, "spectral init: workspace %zu < required %zu", workspace_bytes, ws.used());
   int rc = prepare_lds_kernels();
   if (rc != SCAMD_OK) return rc;
@@ -1502,63 +1622,389 @@ extern "C" int scamd_spectral_embedding_f32(const int64_t* indptr, const int32_t
   SCAMD_LAUNCH_CHECK();
   rc = cx.gram(sb.t0, 1, sb.t0, 1, sb.nrm2);
   if (rc != SCAMD_OK) return rc;
-  double *z = sb.pan[0], *tmp = sb.pan[1], *mz = sb.pan[2], *v = sb.pan[3], *mv = sb.pan[4], *y0 = sb.pan[5], *y1 = sb.pan[6];
-  const int64_t cnt = n * b;
-  hipLaunchKernelGGL(randn_kernel, dim3(cx.egrid()), dim3(256), 0, s, z, cnt, eigensolver_seed(seed, 0x5bd1e995u));
+  SubspaceRun run;
+  rc = graph_subspace_iteration(cx, eigensolver_seed(seed, 0x5bd1e995u), tol, max_outer, max_degree, h_theta, &run);
+  if (rc != SCAMD_OK) return rc;
+  hipLaunchKernelGGL(sp_take_kernel, dim3((unsigned)((n * dim + 255) / 256)), dim3(256), 0, s, (const double*)sb.pan[3], n, b, dim, out);
   SCAMD_LAUNCH_CHECK();
-  rc = cx.deflate(z);
-  if (rc != SCAMD_OK) return rc;
-  rc = cholqr2(cx, z, tmp, y0, false, 2);
-  if (rc != SCAMD_OK) return rc;
-  rc = rayleigh_ritz(cx, y0, mz, v, mv, h_theta);
-  if (rc != SCAMD_OK) return rc;
-  double resid = INFINITY;
-  int outer = 0;
-  for (outer = 1; outer <= max_outer; ++outer) {
-    // residual of the wanted Ritz pairs (|M| = 1: absolute = relative)
-    const int g = cx.grid_rows();
-    hipLaunchKernelGGL(sp_resid_kernel, dim3(g), dim3(256), 0, s, (const double*)v, (const double*)mv, (const double*)cx.w.theta, n, b, dim, sb.part);
-    SCAMD_LAUNCH_CHECK();
-    hipLaunchKernelGGL(sp_reduce_kernel, dim3(1), dim3(256), 0, s, (const double*)sb.part, g, dim, sb.rnorm);
-    SCAMD_LAUNCH_CHECK();
-    double h_r[SP_MAXB];
-    SCAMD_READBACK(h_r, sb.rnorm, sizeof(double) * dim, s);
-    SCAMD_READBACK_SYNC(s);  // (also completes the copy of theta)
-    resid = 0.0;
-    for (int j = 0; j < dim; ++j) resid = std::max(resid, std::sqrt(std::max(h_r[j], 0.0)));
-    if (resid < tol) break;
-    const double c = h_theta[b - 1];
-    double* blk = nullptr;  // the block that is orthonormalised next
-    if (!(c > 0.0 && c < 1.0)) {
-      // a degenerate block: one plain step, on a COPY (mv is an output of the Rayleigh-Ritz that follows)
-      rc = cx.deflate(mv);
-      if (rc != SCAMD_OK) return rc;
-      hipLaunchKernelGGL(axpby_kernel, dim3(cx.egrid()), dim3(256), 0, s, cnt, 1.0, (const double*)mv, 0.0, (const double*)mv, y0);
-      SCAMD_LAUNCH_CHECK();
-      blk = y0;
-    } else {
-      // the degree: as high as the amplification spread inside the wanted set allows; the spectrum's upper end is 1
-      const int m = chebyshev_degree(c, 1.0, h_theta[dim - 1], max_degree);
-      rc = chebyshev_filter(cx, v, mv, c, 1.0, m, y0, y1, z, &blk);
-      if (rc != SCAMD_OK) return rc;
-      rc = cx.deflate(blk);
-      if (rc != SCAMD_OK) return rc;
-    }
-    double* zq = blk == y0 ? y1 : y0;  // (tmp never joins the filter's rotation)
-    rc = cholqr2(cx, blk, tmp, zq, false, 2);
-    if (rc != SCAMD_OK) return rc;
-    rc = rayleigh_ritz(cx, zq, mz, v, mv, h_theta);
-    if (rc != SCAMD_OK) return rc;
-  }
-  hipLaunchKernelGGL(sp_take_kernel, dim3((unsigned)((n * dim + 255) / 256)), dim3(256), 0, s, (const double*)v, n, b, dim, out);
-  SCAMD_LAUNCH_CHECK();
-  SCAMD_READBACK_SYNC(s);  // (a loop that ends by max_outer leaves the last theta queued)
+  SCAMD_READBACK_SYNC(s);
   if (info_host) {
-    info_host[0] = (double)std::min(outer, max_outer);
+    info_host[0] = (double)run.outer;
     info_host[1] = (double)cx.n_apply;
-    info_host[2] = resid;
-    info_host[3] = resid < tol ? 1.0 : 0.0;
+    info_host[2] = run.resid;
+    info_host[3] = run.resid < tol ? 1.0 : 0.0;
     for (int j = 0; j < dim && j < 4; ++j) info_host[4 + j] = 2.0 * h_theta[j] - 1.0;  // eigenvalues of S
   }
+  return SCAMD_OK;
+}
+
+// =====================================================================================================================
+// Diffusion maps and diffusion pseudotime: `sc.tl.diffmap` / `sc.tl.dpt` (src/scanpy/neighbors/__init__.py:791-953).
+//   * scamd_transitions_sym_f32: the density-normalised, symmetrised transition matrix T_sym of `compute_transitions` on the
+//     pattern of the graph (float64 sums one wave per row, every entry rounded to float32 once);
+//   * scamd_diffmap_f32: the n_comps leading eigenpairs of T_sym (`compute_eigen`: ARPACK on one host thread) by the
+//     Chebyshev-filtered subspace iteration above on M = (T_sym + I) / 2, block b = n_comps + 6 <= 32 columns, nothing deflated:
+//     the stationary eigenvector is column 0 of the answer.  Sign rule: the entry of largest magnitude of every column is
+//     positive (lowest row on ties), applied here so that runs and machines agree.
+//     ARPACK is asked for the largest MAGNITUDES, the filter finds the largest ALGEBRAIC values; they differ only when T_sym has
+//     an eigenvalue below -lambda[n_comps - 1].  A second, cheap run of the same iteration on (I - T_sym) / 2 (block of 8, one
+//     wanted pair, tol 1e-3) estimates lambda_min, and the entry refuses (SCAMD_EUNSUPPORTED) when -lambda_min >=
+//     lambda[n_comps - 1].  A Ritz value approaches its eigenvalue from inside the spectrum, so the estimate bounds lambda_min
+//     from ABOVE: the guard can prove a conflict, never the absence of one.
+//   * scamd_dpt_pseudotime_f32: one row of the DPT distance matrix (`_get_dpt_row`), on request divided by its largest finite
+//     entry (`_set_pseudotime`), float64 accumulation, the maximum by a two-stage reduction.
+// =====================================================================================================================
+namespace scamd {
+constexpr int DM_GUARD_B = 8;      // block of the lambda_min run
+constexpr double DM_GUARD_TOL = 1e-3;
+constexpr int DPT_GRID = 1024;
+constexpr int DPT_MAXC = 128;      // most diffusion components a pseudotime takes
+
+// flag[0] |= 1 when a row stores nothing
+__global__ void dm_empty_rows_kernel(const int64_t* __restrict__ indptr, int64_t n, int* __restrict__ flag) {
+  const int64_t v = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
+  if (v < n && indptr[v + 1] <= indptr[v]) atomicOr(flag, 1);
+}
+// ksum[v] = sum over the row of K_vu = w_vu / (dens_v dens_u) (float64, the lane-strided order of sp_degree_kernel)
+__global__ __launch_bounds__(256) void dm_kernel_sum_kernel(const int64_t* __restrict__ indptr, const int32_t* __restrict__ indices,
+                                                            const float* __restrict__ w, int64_t n, const double* __restrict__ dens,
+                                                            double* __restrict__ ksum) {
+  const int lane = threadIdx.x & 63;
+  const int64_t v = (int64_t)blockIdx.x * 4 + (threadIdx.x >> 6);
+  if (v >= n) return;
+  const double dv = dens[v];
+  double s = 0.0;
+  for (int64_t e = indptr[v] + lane; e < indptr[v + 1]; e += 64) s += (double)w[e] / (dv * dens[indices[e]]);
+#pragma unroll
+  for (int o = 32; o > 0; o >>= 1) s += __shfl_xor(s, o);
+  if (lane == 0) ksum[v] = s;
+}
+// z[v] = sqrt(ksum[v]), t[e] = float(K_vu / (z_v z_u)); dens == nullptr: K = w (no density normalisation, ksum = the degrees).
+// flag[0] |= 1 for a row whose sums are not positive and finite (an empty row, non-positive weights)
+__global__ __launch_bounds__(256) void dm_transitions_kernel(const int64_t* __restrict__ indptr, const int32_t* __restrict__ indices,
+                                                             const float* __restrict__ w, int64_t n, const double* __restrict__ dens,
+                                                             const double* __restrict__ ksum, float* __restrict__ t,
+                                                             double* __restrict__ z, int* __restrict__ flag) {
+  const int lane = threadIdx.x & 63;
+  const int64_t v = (int64_t)blockIdx.x * 4 + (threadIdx.x >> 6);
+  if (v >= n) return;
+  const double kv = ksum[v], dv = dens ? dens[v] : 1.0;
+  const double zv = sqrt(kv);
+  if (lane == 0) {
+    z[v] = zv;
+    if (!(kv > 0.0 && kv < INFINITY && dv > 0.0)) atomicOr(flag, 1);
+  }
+  for (int64_t e = indptr[v] + lane; e < indptr[v + 1]; e += 64) {
+    const int u = indices[e];
+    const double k = dens ? (double)w[e] / (dv * dens[u]) : (double)w[e];
+    t[e] = (float)(k / (zv * sqrt(ksum[u])));
+  }
+}
+
+// part_v / part_i [blk][j] = the entry of largest magnitude of column j (< dim) over the block's rows and its row, the lowest
+// row on ties; -1: the block has no row
+__global__ __launch_bounds__(256) void dm_colmax_kernel(const double* __restrict__ v, int64_t n, int b, int dim,
+                                                        double* __restrict__ part_v, int* __restrict__ part_i) {
+  constexpr int W = SP_WIDEB, RL = 256 / W;
+  __shared__ double rv[256];
+  __shared__ int ri[256];
+  const int j = threadIdx.x % W, rl = threadIdx.x / W;
+  const int64_t rows_per = (n + gridDim.x - 1) / gridDim.x;
+  const int64_t r0 = (int64_t)blockIdx.x * rows_per, r1 = r0 + rows_per < n ? r0 + rows_per : n;
+  double best = 0.0;
+  int bi = -1;
+  if (j < dim) {
+    for (int64_t r = r0 + rl; r < r1; r += RL) {  // (rows ascend: `>` keeps the lowest)
+      const double x = v[r * b + j];
+      if (bi < 0 || fabs(x) > fabs(best)) {
+        best = x;
+        bi = (int)r;
+      }
+    }
+  }
+  rv[threadIdx.x] = best;
+  ri[threadIdx.x] = bi;
+  __syncthreads();
+  if (rl == 0 && j < dim) {
+    for (int k = 1; k < RL; ++k) {
+      const double x = rv[k * W + j];
+      const int i = ri[k * W + j];
+      if (i >= 0 && (bi < 0 || fabs(x) > fabs(best) || (fabs(x) == fabs(best) && i < bi))) {
+        best = x;
+        bi = i;
+      }
+    }
+    part_v[(int64_t)blockIdx.x * dim + j] = best;
+    part_i[(int64_t)blockIdx.x * dim + j] = bi;
+  }
+}
+// sign[j] = -1 if the entry of largest magnitude of column j is negative, else 1 (blocks in index order = rows ascending);
+// evals[j] = 2 theta[j] - 1: the eigenvalue of T_sym behind the Ritz value of M
+__global__ void dm_sign_kernel(const double* __restrict__ part_v, const int* __restrict__ part_i, int nblk, int dim,
+                               const double* __restrict__ theta, double* __restrict__ sign, double* __restrict__ evals) {
+  const int j = blockIdx.x * blockDim.x + threadIdx.x;
+  if (j >= dim) return;
+  double best = 0.0;
+  bool have = false;
+  for (int blk = 0; blk < nblk; ++blk) {
+    if (part_i[(int64_t)blk * dim + j] < 0) continue;
+    const double x = part_v[(int64_t)blk * dim + j];
+    if (!have || fabs(x) > fabs(best)) {
+      best = x;
+      have = true;
+    }
+  }
+  sign[j] = best < 0.0 ? -1.0 : 1.0;
+  evals[j] = 2.0 * theta[j] - 1.0;
+}
+// out[row][j] = sign[j] v[row][j], j < dim (row stride b -> dim)
+__global__ void dm_take_kernel(const double* __restrict__ v, const double* __restrict__ sign, int64_t n, int b, int dim,
+                               double* __restrict__ out) {
+  const int64_t e = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
+  if (e >= n * dim) return;
+  const int64_t row = e / dim;
+  const int j = (int)(e - row * dim);
+  out[e] = sign[j] * v[row * b + j];
+}
+
+struct DiffmapBuffers {
+  SpectralBuffers sb;
+  int* part_i;
+  double* sign;
+};
+static void diffmap_carve(Workspace& ws, int64_t n, int b, DiffmapBuffers* db) {
+  spectral_carve(ws, n, 0, std::max(b, DM_GUARD_B), &db->sb);  // (T_sym is the caller's: sb.s stays unused)
+  db->part_i = ws.take<int>((size_t)SP_GRID * SP_WIDEB);
+  db->sign = ws.take<double>(SP_WIDEB);
+}
+
+// d[v] = sqrt(sum_j wgt_j (basis[iroot][j] - basis[v][j])^2), wgt_j = (lambda_j / (1 - lambda_j))^2 for lambda_j < 0.9994, else
+// 1 (float64, j ascending); +inf outside the root's component (labels != nullptr); part[blk] = largest finite d of the block
+__global__ __launch_bounds__(256) void dpt_row_kernel(const float* __restrict__ evals, const float* __restrict__ basis, int64_t n,
+                                                      int n_dcs, int64_t ld, int64_t iroot, const int32_t* __restrict__ labels,
+                                                      double* __restrict__ d, double* __restrict__ part) {
+  __shared__ double wgt[DPT_MAXC], root[DPT_MAXC], red[256];
+  for (int j = threadIdx.x; j < n_dcs; j += 256) {
+    const double lam = (double)evals[j];
+    const double q = lam / (1.0 - lam);
+    wgt[j] = lam < 0.9994 ? q * q : 1.0;
+    root[j] = (double)basis[iroot * ld + j];
+  }
+  __syncthreads();
+  const int root_label = labels ? labels[iroot] : 0;
+  const int64_t rows_per = (n + gridDim.x - 1) / gridDim.x;
+  const int64_t r0 = (int64_t)blockIdx.x * rows_per, r1 = r0 + rows_per < n ? r0 + rows_per : n;
+  double mx = 0.0;
+  for (int64_t r = r0 + threadIdx.x; r < r1; r += 256) {
+    double acc = 0.0;
+    for (int j = 0; j < n_dcs; ++j) {
+      const double df = root[j] - (double)basis[r * ld + j];
+      acc = fma(wgt[j] * df, df, acc);
+    }
+    double val = sqrt(acc);
+    if (labels && labels[r] != root_label) val = INFINITY;
+    d[r] = val;
+    if (val < INFINITY && val > mx) mx = val;
+  }
+  red[threadIdx.x] = mx;
+  __syncthreads();
+  for (int o = 128; o > 0; o >>= 1) {
+    if ((int)threadIdx.x < o) red[threadIdx.x] = fmax(red[threadIdx.x], red[threadIdx.x + o]);
+    __syncthreads();
+  }
+  if (threadIdx.x == 0) part[blockIdx.x] = red[0];
+}
+// part[nblk] = max over part[0 .. nblk)
+__global__ __launch_bounds__(256) void dpt_max_kernel(double* __restrict__ part, int nblk) {
+  __shared__ double red[256];
+  double mx = 0.0;
+  for (int i = threadIdx.x; i < nblk; i += 256) mx = fmax(mx, part[i]);
+  red[threadIdx.x] = mx;
+  __syncthreads();
+  for (int o = 128; o > 0; o >>= 1) {
+    if ((int)threadIdx.x < o) red[threadIdx.x] = fmax(red[threadIdx.x], red[threadIdx.x + o]);
+    __syncthreads();
+  }
+  if (threadIdx.x == 0) part[nblk] = red[0];
+}
+// out[v] = float(d[v] / max), or float(d[v]) with mx == nullptr: rounded to float32 once
+__global__ void dpt_scale_kernel(const double* __restrict__ d, const double* __restrict__ mx, int64_t n, float* __restrict__ out) {
+  const int64_t v = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
+  if (v < n) out[v] = mx ? (float)(d[v] / mx[0]) : (float)d[v];
+}
+struct DptBuffers {
+  double* d; double* part;
+};
+static void dpt_carve(Workspace& ws, int64_t n, DptBuffers* b) {
+  b->d = ws.take<double>((size_t)n);
+  b->part = ws.take<double>(DPT_GRID + 1);
+}
+}  // namespace scamd
+
+extern "C" size_t scamd_transitions_sym_workspace_bytes(int64_t n, int64_t nnz) {
+  if (n < 1 || nnz < 0) return 0;
+  Workspace ws(nullptr, 0);
+  ws.take<double>((size_t)n);
+  ws.take<double>((size_t)n);
+  ws.take<int>(8);
+  return ws.used();
+}
+
+extern "C" int scamd_transitions_sym_f32(const int64_t* indptr, const int32_t* indices, const float* weights, int64_t n,
+                                         int64_t nnz, int density_normalize, float* t_sym, double* z, void* workspace,
+                                         size_t workspace_bytes, scamd_stream_t stream) {
+  SCAMD_REQUIRE(indptr && indices && weights && t_sym && z, SCAMD_EINVAL, "transitions: null pointer");
+  SCAMD_REQUIRE(n >= 1 && n < ((int64_t)1 << 31) && nnz >= 1, SCAMD_EINVAL, "transitions: bad shape n=%lld nnz=%lld", (long long)n,
+                (long long)nnz);
+  Workspace ws(workspace, workspace_bytes);
+  double* dens = ws.take<double>((size_t)n);
+  double* ksum = ws.take<double>((size_t)n);
+  int* flag = ws.take<int>(8);
+  SCAMD_REQUIRE(workspace && ws.ok, SCAMD_EWORKSPACE, "transitions: workspace %zu < required %zu", workspace_bytes, ws.used());
+  hipStream_t s = stream;
+  HostReadbackScope readback_scope;
+  const unsigned grid = (unsigned)((n + 3) / 4);
+  SCAMD_HIP_CHECK(hipMemsetAsync(flag, 0, sizeof(int), s));
+  // dens = the column sums of the symmetric graph = its row sums
+  hipLaunchKernelGGL(sp_degree_kernel, dim3(grid), dim3(256), 0, s, indptr, weights, n, dens);
+  SCAMD_LAUNCH_CHECK();
+  if (density_normalize) {
+    hipLaunchKernelGGL(dm_kernel_sum_kernel, dim3(grid), dim3(256), 0, s, indptr, indices, weights, n, (const double*)dens, ksum);
+    SCAMD_LAUNCH_CHECK();
+  }
+  hipLaunchKernelGGL(dm_transitions_kernel, dim3(grid), dim3(256), 0, s, indptr, indices, weights, n,
+                     density_normalize ? (const double*)dens : (const double*)nullptr,
+                     density_normalize ? (const double*)ksum : (const double*)dens, t_sym, z, flag);
+  SCAMD_LAUNCH_CHECK();
+  int bad = 0;
+  SCAMD_READBACK_NOW(&bad, flag, sizeof(int), s);
+  SCAMD_REQUIRE(!bad, SCAMD_EUNSUPPORTED, "transitions: a row of the graph has no positive weight (empty row?)");
+  return SCAMD_OK;
+}
+
+extern "C" size_t scamd_diffmap_workspace_bytes(int64_t n, int64_t nnz, int n_comps) {
+  if (n < 1 || nnz < 0 || n_comps < 1 || n_comps + 6 > SP_WIDEB) return 0;
+  Workspace ws(nullptr, 0);
+  DiffmapBuffers db;
+  diffmap_carve(ws, n, n_comps + 6, &db);
+  return ws.used();
+}
+
+extern "C" int scamd_diffmap_f32(const int64_t* indptr, const int32_t* indices, const float* t_sym, int64_t n, int64_t nnz,
+                                 int n_comps, uint64_t seed, double tol, int max_outer, int max_degree, double* evals,
+                                 double* evecs, double* info_host, void* workspace, size_t workspace_bytes,
+                                 scamd_stream_t stream) {
+  SCAMD_REQUIRE(indptr && indices && t_sym && evals && evecs, SCAMD_EINVAL, "diffmap: null pointer");
+  SCAMD_REQUIRE(n_comps >= 1 && n_comps + 6 <= SP_WIDEB, SCAMD_EUNSUPPORTED, "diffmap: %d components (1 to %d)", n_comps,
+                SP_WIDEB - 6);
+  SCAMD_REQUIRE(n >= 1 && n < ((int64_t)1 << 31) && nnz >= 1, SCAMD_EINVAL, "diffmap: bad shape n=%lld nnz=%lld", (long long)n,
+                (long long)nnz);
+  const int b = n_comps + 6;
+  SCAMD_REQUIRE(n > std::max(b, DM_GUARD_B), SCAMD_EUNSUPPORTED, "diffmap: %lld cells, a block of %d columns needs more",
+                (long long)n, std::max(b, DM_GUARD_B));
+  DiffmapOp cx;
+  cx.s = stream;
+  cx.indptr = indptr;
+  cx.indices = indices;
+  cx.sval = t_sym;
+  cx.n = n;
+  cx.dim = n_comps;
+  cx.b = b;
+  cx.who = "diffmap";
+  Workspace ws(workspace, workspace_bytes);
+  DiffmapBuffers db;
+  diffmap_carve(ws, n, b, &db);
+  cx.sb = db.sb;
+  cx.w = db.sb.w;
+  SCAMD_REQUIRE(workspace && ws.ok, SCAMD_EWORKSPACE, "diffmap: workspace %zu < required %zu", workspace_bytes, ws.used());
+  int rc = prepare_lds_kernels();
+  if (rc != SCAMD_OK) return rc;
+  HostReadbackScope readback_scope;
+  hipStream_t s = stream;
+  int* empty_flag = cx.w.flags + 4;
+  SCAMD_HIP_CHECK(hipMemsetAsync(empty_flag, 0, sizeof(int), s));
+  hipLaunchKernelGGL(dm_empty_rows_kernel, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, s, indptr, n, empty_flag);
+  SCAMD_LAUNCH_CHECK();
+  int has_empty = 0;
+  SCAMD_READBACK_NOW(&has_empty, empty_flag, sizeof(int), s);
+  SCAMD_REQUIRE(!has_empty, SCAMD_EUNSUPPORTED, "diffmap: the transition matrix has an empty row");
+  // the n_comps largest eigenvalues of T_sym
+  double h_theta[SP_WIDEB];
+  SubspaceRun run;
+  rc = graph_subspace_iteration(cx, eigensolver_seed(seed, 0x2545f491u), tol, max_outer, max_degree, h_theta, &run);
+  if (rc != SCAMD_OK) return rc;
+  const int g = cx.grid_rows();
+  const double* v = db.sb.pan[3];
+  hipLaunchKernelGGL(dm_colmax_kernel, dim3(g), dim3(256), 0, s, v, n, b, n_comps, db.sb.part, db.part_i);
+  SCAMD_LAUNCH_CHECK();
+  hipLaunchKernelGGL(dm_sign_kernel, dim3(1), dim3(SP_WIDEB), 0, s, (const double*)db.sb.part, (const int*)db.part_i, g, n_comps,
+                     (const double*)cx.w.theta, db.sign, evals);
+  SCAMD_LAUNCH_CHECK();
+  hipLaunchKernelGGL(dm_take_kernel, dim3((unsigned)((n * n_comps + 255) / 256)), dim3(256), 0, s, v, (const double*)db.sign, n, b,
+                     n_comps, evecs);
+  SCAMD_LAUNCH_CHECK();
+  SCAMD_READBACK_SYNC(s);  // (the last theta of a run that ended by max_outer)
+  // the guard: the largest Ritz value of (I - T_sym) / 2 on a small block bounds lambda_min from above
+  DiffmapOp gx = cx;
+  gx.sgn = -1.0;
+  gx.b = DM_GUARD_B;
+  gx.dim = 1;
+  gx.who = "diffmap guard";
+  gx.n_apply = 0;
+  gx.n_chol_retry = 0;
+  double g_theta[SP_WIDEB];
+  SubspaceRun grun;
+  rc = graph_subspace_iteration(gx, eigensolver_seed(seed, 0x9e3779b9u), DM_GUARD_TOL, max_outer, max_degree, g_theta, &grun);
+  if (rc != SCAMD_OK) return rc;
+  SCAMD_READBACK_SYNC(s);
+  const double lam_last = 2.0 * h_theta[n_comps - 1] - 1.0, lam_min = 1.0 - 2.0 * g_theta[0];
+  const bool conflict = -lam_min >= lam_last;
+  if (info_host) {
+    info_host[0] = (double)run.outer;
+    info_host[1] = (double)cx.n_apply;
+    info_host[2] = run.resid;  // of the Ritz pairs of M = (T_sym + I) / 2: half the residual of the pairs of T_sym
+    info_host[3] = run.resid < tol ? 1.0 : 0.0;
+    info_host[4] = lam_min;
+    info_host[5] = (double)gx.n_apply;
+    info_host[6] = conflict ? 1.0 : 0.0;
+    info_host[7] = (double)(cx.n_chol_retry + gx.n_chol_retry);
+  }
+  SCAMD_REQUIRE(!conflict, SCAMD_EUNSUPPORTED,
+                "diffmap: T_sym has an eigenvalue <= %.6f, of larger magnitude than the last requested one (%.6f): the largest-"
+                "magnitude and the largest-algebraic eigenpairs differ",
+                lam_min, lam_last);
+  return SCAMD_OK;
+}
+
+extern "C" size_t scamd_dpt_pseudotime_workspace_bytes(int64_t n) {
+  if (n < 1) return 0;
+  Workspace ws(nullptr, 0);
+  DptBuffers b;
+  dpt_carve(ws, n, &b);
+  return ws.used();
+}
+
+extern "C" int scamd_dpt_pseudotime_f32(const float* evals, const float* basis, int64_t n, int n_dcs, int64_t ld, int64_t iroot,
+                                        const int32_t* labels, int scale, float* out, void* workspace, size_t workspace_bytes,
+                                        scamd_stream_t stream) {
+  SCAMD_REQUIRE(evals && basis && out, SCAMD_EINVAL, "dpt: null pointer");
+  SCAMD_REQUIRE(n >= 1 && n < ((int64_t)1 << 31) && n_dcs >= 1 && n_dcs <= DPT_MAXC && ld >= n_dcs && iroot >= 0 && iroot < n,
+                SCAMD_EINVAL, "dpt: bad shape n=%lld n_dcs=%d ld=%lld iroot=%lld (at most %d components)", (long long)n, n_dcs,
+                (long long)ld, (long long)iroot, DPT_MAXC);
+  Workspace ws(workspace, workspace_bytes);
+  DptBuffers b;
+  dpt_carve(ws, n, &b);
+  SCAMD_REQUIRE(workspace && ws.ok, SCAMD_EWORKSPACE, "dpt: workspace %zu < required %zu", workspace_bytes, ws.used());
+  hipStream_t s = stream;
+  const int g = (int)std::min<int64_t>(DPT_GRID, (n + 255) / 256);
+  hipLaunchKernelGGL(dpt_row_kernel, dim3(g), dim3(256), 0, s, evals, basis, n, n_dcs, ld, iroot, labels, b.d, b.part);
+  SCAMD_LAUNCH_CHECK();
+  if (scale) {
+    hipLaunchKernelGGL(dpt_max_kernel, dim3(1), dim3(256), 0, s, b.part, g);
+    SCAMD_LAUNCH_CHECK();
+  }
+  hipLaunchKernelGGL(dpt_scale_kernel, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, s, (const double*)b.d,
+                     scale ? (const double*)(b.part + g) : (const double*)nullptr, n, out);
+  SCAMD_LAUNCH_CHECK();
   return SCAMD_OK;
 }

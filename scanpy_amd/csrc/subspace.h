@@ -1,9 +1,10 @@
 // Chebyshev-filtered subspace iteration (Zhou & Saad), its steps written ONCE over an operator: CholeskyQR2 with shifted rounds,
 // Rayleigh-Ritz by the one-workgroup Jacobi, the degree rule and the filter.  Two operators use them (dense.hip): the dense
 // float64 matrix of the PCA (`DenseOp`: Gram matrices and products on the f64 MFMA GEMM) and the normalised graph of the
-// spectral initialisation (`SpectralOp`: float32 SpMM, two-stage tall Gram sums, the trivial eigenvector projected out).
-// The outer iterations stay with the two drivers (dense_topk, scamd_spectral_embedding_f32): their prologues, residuals, stop
-// rules and degenerate-block steps differ, and a shared loop would need a hook for each.
+// spectral initialisation (`SpectralOp`: float32 SpMM, two-stage tall Gram sums, the trivial eigenvector projected out);
+// `DiffmapOp` is the latter on a stored transition matrix with nothing projected out.
+// The outer iterations stay with the two drivers (dense_topk; graph_subspace_iteration for both graph operators): their
+// prologues, residuals, stop rules and degenerate-block steps differ, and a shared loop would need a hook for each.
 //
 // Included by dense.hip AFTER the kernels these steps launch (chol_factor_kernel, panel_small_kernel, jacobi_eigh_kernel,
 // axpby_kernel); it is not a stand-alone header.

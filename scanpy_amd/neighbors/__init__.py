@@ -41,7 +41,7 @@ def _to_device(a, dtype):
 
     if isinstance(a, torch.Tensor):
         return a.to(dtype).contiguous()
-    np_dtype = {torch.int32: np.int32, torch.float32: np.float32}[dtype]
+    np_dtype = {torch.int32: np.int32, torch.int64: np.int64, torch.float32: np.float32}[dtype]
     return torch.from_numpy(np.ascontiguousarray(a, dtype=np_dtype)).to(require_gpu())
 
 
@@ -74,8 +74,12 @@ def _connectivities_kernel(method: str, knn_indices, knn_dists, n_obs: int) -> s
 class Neighbors:
     """Data represented as graph of nearest neighbors (the slice of the reference class the path needs)."""
 
-    def __init__(self, adata, *, n_dcs=None, neighbors_key=None):
+    def __init__(self, adata, *, n_dcs=None, neighbors_key=None, diffmap_key=None):
         self._adata = adata
+        self._iroot = _UNSET  # the root cell is looked for when `.iroot` is first read (`tl.dpt`), never by `pp.neighbors`
+        self._transitions_sym = None
+        self.Z = None
+        self._eigen_info = None
         self._distances = None
         self._connectivities = None
         self.n_neighbors = None
@@ -103,6 +107,23 @@ class Neighbors:
                 else:
                     self.n_neighbors = int(count_nonzero(self._connectivities) / self._connectivities.shape[0] / 2)
             self._cc = None  # `:466-472`, lazily (see `_connected_components`)
+        # a stored diffusion map (neighbors/__init__.py:476-497)
+        keys = (diffmap_key, diffmap_key) if diffmap_key else existing_diffmap_keys(adata)
+        if keys:
+            evals = adata.uns[keys[0]]
+            self._eigen_values = np.asarray(evals["evals"] if isinstance(evals, dict) else evals)  # (`uns[key_added]['evals']`)
+            self._eigen_basis = adata.obsm[keys[1]]
+            if n_dcs is not None:
+                if n_dcs > len(self._eigen_values):
+                    msg = f"Cannot instantiate using `n_dcs`={n_dcs}. Compute diffmap/spectrum with more components first."
+                    raise ValueError(msg)
+                self._eigen_values = self._eigen_values[:n_dcs]
+                self._eigen_basis = self._eigen_basis[:, :n_dcs]
+            self.n_dcs = len(self._eigen_values)
+        else:
+            self._eigen_values = None
+            self._eigen_basis = None
+            self.n_dcs = None
 
     @property
     def _connected_components(self):
@@ -129,6 +150,152 @@ class Neighbors:
     @property
     def connectivities(self):
         return self._connectivities
+
+    # ---- diffusion maps and pseudotime (neighbors/__init__.py:516-575, 791-985) --------------------------------------------
+    @property
+    def transitions_sym(self):
+        """Symmetrised transition matrix (scipy CSR, float32)."""
+        return self._transitions_sym
+
+    @property
+    def transitions(self):
+        """Transition matrix `Z T_sym Z^-1` (neighbors/__init__.py:516-537)."""
+        return self.Z @ self.transitions_sym @ self.Z.power(-1)
+
+    @property
+    def eigen_values(self):
+        return self._eigen_values
+
+    @property
+    def eigen_basis(self):
+        return self._eigen_basis
+
+    @property
+    def distances_dpt(self):
+        return _DptRows(self)
+
+    def compute_transitions(self, *, density_normalize: bool = True) -> None:
+        """neighbors/__init__.py:791-828 -> scamd_transitions_sym_f32.  Makes `.transitions_sym`, `.transitions` and `.Z`
+        available (scipy matrices on the host, as the reference returns them)."""
+        import torch
+
+        from .. import _kernels
+
+        conn = self._connectivities
+        if not sparse.issparse(conn):
+            msg = "compute_transitions: a dense connectivity matrix is outside the MI355X path (pp.neighbors stores a sparse one)."
+            raise NotImplementedError(msg)
+        conn = sparse.csr_matrix(conn)
+        conn.sort_indices()
+        n = conn.shape[0]
+        if np.any(np.diff(conn.indptr) == 0):
+            msg = "compute_transitions: the graph has a cell without neighbours (an empty row)."
+            raise ValueError(msg)
+        t, z = _kernels.transitions_sym(_to_device(conn.indptr, torch.int64), _to_device(conn.indices, torch.int32),
+                                        _to_device(conn.data, torch.float32), n, density_normalize=density_normalize)
+        self._transitions_sym = sparse.csr_matrix((t.cpu().numpy(), conn.indices.copy(), conn.indptr.copy()), shape=conn.shape)
+        self.Z = sparse.diags(1.0 / z.cpu().numpy()).tocsr()
+
+    def compute_eigen(self, *, n_comps: int = 15, sort: str = "decrease", rng=None, random_state=_UNSET, sym=None) -> None:
+        """neighbors/__init__.py:830-895 -> scamd_diffmap_f32: the `n_comps` leading eigenpairs of `.transitions_sym`
+        (`eigsh(which='LM')` there), float32 as the reference casts them.  `rng` / `random_state` seed the start block."""
+        import torch
+
+        from .. import _kernels
+
+        if self._transitions_sym is None:
+            msg = "Run `.compute_transitions` first."
+            raise ValueError(msg)
+        check_eigen_arguments(n_comps, sort)
+        seed, _ = resolve_seed(rng, random_state)
+        t = self._transitions_sym
+        n = t.shape[0]
+        n_comps = min(n - 1, n_comps)
+        if np.any(np.diff(t.indptr) == 0):
+            msg = "compute_eigen: the transition matrix has an empty row."
+            raise ValueError(msg)
+        evals, evecs, info = _kernels.diffmap(_to_device(t.indptr, torch.int64), _to_device(t.indices, torch.int32),
+                                              _to_device(t.data, torch.float32), n, n_comps, seed=seed)
+        if not info["converged"]:
+            from .._lib import ScamdError
+
+            raise ScamdError(f"compute_eigen: the subspace iteration did not converge ({info})")
+        self._eigen_info = info
+        self._eigen_values = evals.to(torch.float32).cpu().numpy()
+        self._eigen_basis = evecs.to(torch.float32).cpu().numpy()
+        # (the reference counts the connected components of the graph, :892; every component owns one eigenvalue 1, so the
+        # eigenvalues just computed say the same without a pass over the graph on the host)
+        if int(np.sum(self._eigen_values > 1.0 - 1e-5)) > len(self._eigen_values) / 2:
+            warnings.warn("Transition matrix has many disconnected components!", UserWarning, stacklevel=2)
+
+    @property
+    def iroot(self):
+        """index of the root cell, from `uns['iroot']` or `uns['xroot']` / `var['xroot']` (neighbors/__init__.py:897-918); the
+        reference looks for it when the object is built, here the first read does"""
+        if self._iroot is _UNSET:
+            self._init_iroot()
+        return self._iroot
+
+    @iroot.setter
+    def iroot(self, value):
+        self._iroot = value
+
+    def _init_iroot(self):
+        """neighbors/__init__.py:897-918."""
+        self._iroot = None
+        adata = self._adata
+        uns, var = getattr(adata, "uns", {}), getattr(adata, "var", None)
+        if "iroot" in uns:
+            if uns["iroot"] >= adata.n_obs:
+                warnings.warn(f"Root cell index {uns['iroot']} does not exist for {adata.n_obs} samples. It’s ignored.",
+                              UserWarning, stacklevel=3)
+            else:
+                self.iroot = uns["iroot"]
+            return
+        xroot = None
+        if "xroot" in uns:
+            xroot = uns["xroot"]
+        elif var is not None and "xroot" in var:
+            xroot = var["xroot"]
+        if xroot is not None and np.size(xroot) == adata.shape[1]:
+            self._set_iroot_via_xroot(np.asarray(xroot))
+
+    def _set_iroot_via_xroot(self, xroot):
+        """neighbors/__init__.py:955-985: the cell nearest to `xroot` in X -- the first within 1e-10, else the first of the
+        nearest; a host loop over the rows there, row blocks here."""
+        if self._adata.shape[1] != xroot.size:
+            msg = "The root vector you provided does not have the correct dimension."
+            raise ValueError(msg)
+        x = self._adata.X
+        xroot = np.asarray(xroot).ravel()
+        dsq = np.empty(x.shape[0])
+        for i0 in range(0, x.shape[0], 4096):
+            blk = x[i0:i0 + 4096]
+            diff = (blk.toarray() if sparse.issparse(blk) else np.asarray(blk)) - xroot
+            dsq[i0:i0 + 4096] = np.einsum("ij,ij->i", diff, diff)
+        exact = np.flatnonzero(np.sqrt(dsq) < 1e-10)
+        iroot = int(exact[0]) if exact.size else (int(np.argmin(dsq)) if dsq.min() < 1e10 else 0)
+        if self.iroot is not None and iroot != self.iroot:
+            warnings.warn(f"Changing index of iroot from {self.iroot} to {iroot}.", UserWarning, stacklevel=3)
+        self.iroot = iroot
+
+    def _get_dpt_row(self, i: int, *, scale: bool = False) -> np.ndarray:
+        """One row of the DPT distance matrix (neighbors/__init__.py:920-948); scale: divided by its largest finite entry, as
+        `_set_pseudotime` does (:950-953), in the same call of scamd_dpt_pseudotime_f32."""
+        import torch
+
+        from .. import _kernels
+
+        labels = None
+        if self._number_connected_components is not None and self._number_connected_components > 1:
+            labels = _to_device(self._connected_components[1], torch.int32)
+        evals = _to_device(np.asarray(self.eigen_values, dtype=np.float32), torch.float32)
+        basis = _to_device(np.asarray(self.eigen_basis, dtype=np.float32), torch.float32)
+        return _kernels.dpt_pseudotime(evals, basis, int(i), labels, scale=scale).cpu().numpy()
+
+    def _set_pseudotime(self):
+        """Pseudotime with respect to the root cell (neighbors/__init__.py:950-953)."""
+        self.pseudotime = self._get_dpt_row(self.iroot, scale=True)
 
     def compute_neighbors(self, n_neighbors: int = 30, n_pcs: int | None = None, *, use_rep: str | None = None,
                           knn: bool = True, method: str | None = "umap", transformer=None,
@@ -186,6 +353,51 @@ class Neighbors:
             if pending_distances is not None:
                 self._distances = pending_distances()
         self._cc = None  # connected components (neighbors/__init__.py:666-671) are computed on first use
+
+
+class _DptRows:
+    """`Neighbors.distances_dpt`: row i of the DPT distances on demand (the reference's OnFlySymMatrix,
+    neighbors/__init__.py:547-575)"""
+
+    def __init__(self, neighbors):
+        self._neighbors = neighbors
+
+    def __getitem__(self, i):
+        return self._neighbors._get_dpt_row(int(i))
+
+
+MAX_DIFFMAP_COMPS = 26  # the block of scamd_diffmap_f32 holds n_comps + 6 <= 32 columns
+
+
+def check_eigen_arguments(n_comps: int, sort: str = "decrease") -> None:
+    """what `compute_eigen` refuses, before anything touches the library"""
+    if sort != "decrease":
+        msg = f"compute_eigen: sort={sort!r} (the smallest eigenvalues, eigsh(which='SM')) is not offered on the MI355X path."
+        raise NotImplementedError(msg)
+    if n_comps == 0:
+        msg = "compute_eigen: n_comps=0 (the full dense eigendecomposition of an n x n matrix) is not offered on the MI355X path."
+        raise NotImplementedError(msg)
+    if n_comps > MAX_DIFFMAP_COMPS:
+        msg = (f"compute_eigen: n_comps={n_comps}: the device eigensolver holds a block of n_comps + 6 <= 32 columns, "
+               f"at most {MAX_DIFFMAP_COMPS} components.")
+        raise NotImplementedError(msg)
+
+
+def diffmap_keys(key_added) -> tuple:
+    """(uns key, obsm key) of a diffusion map (src/scanpy/_keys.py:76-79)"""
+    return ("diffmap_evals", "X_diffmap") if key_added is None else (key_added, key_added)
+
+
+def existing_diffmap_keys(adata):
+    """the keys of a stored diffusion map under either preset, V1 first (src/scanpy/_keys.py:113-126), or None"""
+    obsm = getattr(adata, "obsm", None)
+    if obsm is None:
+        return None
+    for key_added in (None, "diffmap"):
+        keys = diffmap_keys(key_added)
+        if keys[1] in obsm and keys[0] in adata.uns:
+            return keys
+    return None
 
 
 def _get_metadata(key_added, **params):
