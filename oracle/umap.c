@@ -9,7 +9,7 @@
  *     int((n - epoch_of_next_negative_sample[i]) / epochs_per_negative_sample[i]) negative samples k' drawn with the
  *     per-vertex tau88 generator, repulsive coefficient 2 gamma b / ((0.001 + d^2)(a d^(2b) + 1));
  *   alpha = initial_alpha * (1 - n / n_epochs) after each epoch.
- * Two entry points:
+ * Three entry points (oracle_umap_synchronous_f64, at the end: the synchronous scheme with its forces in double):
  *   oracle_umap_sequential   -- the reference's sequential (Gauss-Seidel) sweep, `parallel=False`
  *   oracle_umap_synchronous  -- the SAME forces evaluated on a snapshot of the embedding per epoch (Jacobi), negatives
  *                               drawn from a counter-based hash: the scheme of scanpy_amd/csrc/umap.hip, restated on
@@ -176,6 +176,93 @@ int oracle_umap_synchronous(int64_t n_vertices, int dim, const int64_t* indptr, 
     yout = tmp;
   }
   if (yin != y) memcpy(y, yin, sizeof(float) * n_vertices * dim);
+  free(next);
+  free(next_neg);
+  free(y2);
+  return 0;
+}
+
+/* The same scheme with the FORCES in double: the schedule arithmetic (next, next_neg, eps_neg, n_neg) stays in float32,
+ * operation for operation as above and as in csrc/umap.hip -- it does not depend on y, so which sample fires when, and how
+ * many negatives it draws, is decided identically; the hash is the same.  Differences, pow, coefficients, clipping and sums
+ * are double, and the embedding is held in double between the epochs (y is read once, rounded to float32 never; y64_out
+ * takes the result).  sabs_out[v * dim + t] = the sum of |term| that went into coordinate t of vertex v in the LAST epoch
+ * (attractive terms counted with their factor 2): alpha * 2^-23 * sabs is the unit in which the tests bound a float32
+ * evaluation of that epoch. */
+int oracle_umap_synchronous_f64(int64_t n_vertices, int dim, const int64_t* indptr, const int32_t* indices,
+                                const float* epochs_per_sample, int n_epochs, double a, double b, double gamma,
+                                double initial_alpha, double negative_sample_rate, uint64_t seed, const float* y,
+                                double* y64_out, double* sabs_out) {
+  const int64_t n_samples = indptr[n_vertices];
+  float* next = malloc(sizeof(float) * (n_samples + 1));
+  float* next_neg = malloc(sizeof(float) * (n_samples + 1));
+  double* y2 = malloc(sizeof(double) * n_vertices * dim);
+  if (!next || !next_neg || !y2) return -1;
+  for (int64_t i = 0; i < n_samples; ++i) {
+    next[i] = epochs_per_sample[i];
+    next_neg[i] = epochs_per_sample[i] / (float)negative_sample_rate;
+  }
+  for (int64_t i = 0; i < n_vertices * dim; ++i) {
+    y64_out[i] = (double)y[i];
+    sabs_out[i] = 0.0;
+  }
+  double* yin = y64_out;
+  double* yout = y2;
+  /* the kernel receives a, b, gamma and alpha as float32: the same values, widened */
+  const double fa = (double)(float)a, fb = (double)(float)b, fg = (double)(float)gamma;
+  for (int n = 0; n < n_epochs; ++n) {
+    const double alpha_n = (double)(float)(initial_alpha * (1.0 - (double)(n > 0 ? n - 1 : 0) / (double)n_epochs));
+    for (int64_t v = 0; v < n_vertices; ++v) {
+      double delta[8] = {0}, sabs[8] = {0};
+      const double* cur = yin + v * dim;
+      for (int64_t i = indptr[v]; i < indptr[v + 1]; ++i) {
+        const float eps = epochs_per_sample[i];
+        if (!(eps > 0.f) || next[i] > (float)n) continue;
+        const double* oth = yin + (int64_t)indices[i] * dim;
+        double d2 = 0.0;
+        for (int t = 0; t < dim; ++t) d2 += (cur[t] - oth[t]) * (cur[t] - oth[t]);
+        double coeff = 0.0;
+        if (d2 > 0.0) {
+          const double pw = pow(d2, fb);
+          coeff = (-2.0 * fa * fb * (pw / d2)) / (fa * pw + 1.0);
+        }
+        for (int t = 0; t < dim; ++t) {
+          double g = coeff * (cur[t] - oth[t]);
+          g = 2.0 * (g > 4.0 ? 4.0 : (g < -4.0 ? -4.0 : g));
+          delta[t] += g;
+          sabs[t] += fabs(g);
+        }
+        next[i] += eps;
+        const float eps_neg = eps / (float)negative_sample_rate;
+        const int n_neg = (int)(((float)n - next_neg[i]) / eps_neg);
+        for (int p = 0; p < n_neg; ++p) {
+          const int64_t kk = neg_vertex(seed, n, i, p, n_vertices);
+          if (kk == v) continue;
+          const double* o2 = yin + kk * dim;
+          double e2 = 0.0;
+          for (int t = 0; t < dim; ++t) e2 += (cur[t] - o2[t]) * (cur[t] - o2[t]);
+          if (e2 > 0.0) {
+            const double c2 = (2.0 * fg * fb) / (((double)0.001f + e2) * (fa * pow(e2, fb) + 1.0));
+            for (int t = 0; t < dim; ++t) {
+              double g = c2 * (cur[t] - o2[t]);
+              g = g > 4.0 ? 4.0 : (g < -4.0 ? -4.0 : g);
+              delta[t] += g;
+              sabs[t] += fabs(g);
+            }
+          }
+        }
+        next_neg[i] += (float)n_neg * eps_neg;
+      }
+      for (int t = 0; t < dim; ++t) {
+        yout[v * dim + t] = cur[t] + alpha_n * delta[t];
+        if (n == n_epochs - 1) sabs_out[v * dim + t] = sabs[t];
+      }
+    }
+    double* tmp = yin;
+    yin = yout;
+    yout = tmp;
+  }
+  if (yin != y64_out) memcpy(y64_out, yin, sizeof(double) * n_vertices * dim);
   free(next);
   free(next_neg);
   free(y2);

@@ -38,6 +38,10 @@ def _load():
         lib.oracle_umap_synchronous.restype = C.c_int
         lib.oracle_umap_synchronous.argtypes = [C.c_int64, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int, C.c_double,
                                                 C.c_double, C.c_double, C.c_double, C.c_double, C.c_uint64, C.c_void_p]
+        lib.oracle_umap_synchronous_f64.restype = C.c_int
+        lib.oracle_umap_synchronous_f64.argtypes = [C.c_int64, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int, C.c_double,
+                                                    C.c_double, C.c_double, C.c_double, C.c_double, C.c_uint64, C.c_void_p,
+                                                    C.c_void_p, C.c_void_p]
         _lib = lib
     return _lib
 
@@ -156,6 +160,40 @@ def optimize_layout(g, y0, *, n_epochs, a, b, gamma=1.0, initial_alpha=1.0, nega
     if rc != 0:
         raise RuntimeError(f"oracle umap failed: {rc}")
     return y
+
+
+def synchronous_csr(indptr, indices, eps, y0, *, n_epochs, a, b, gamma=1.0, initial_alpha=1.0, negative_sample_rate=5.0,
+                    seed=0) -> np.ndarray:
+    """`oracle_umap_synchronous` on the arrays scamd_umap_optimize_f32 takes (eps = epochs per sample, <= 0: never fires)
+    -> float32 [n, dim], every operation in float32"""
+    lib = _load()
+    y = np.ascontiguousarray(y0, dtype=np.float32).copy()
+    n, dim = y.shape
+    indptr, indices = np.ascontiguousarray(indptr, dtype=np.int64), np.ascontiguousarray(indices, dtype=np.int32)
+    eps = np.ascontiguousarray(eps, dtype=np.float32)
+    rc = lib.oracle_umap_synchronous(n, dim, indptr.ctypes.data, indices.ctypes.data, eps.ctypes.data, int(n_epochs), a, b, gamma,
+                                     initial_alpha, float(negative_sample_rate), int(seed) & (2**64 - 1), y.ctypes.data)
+    if rc != 0:
+        raise RuntimeError(f"oracle umap failed: {rc}")
+    return y
+
+
+def synchronous_csr_f64(indptr, indices, eps, y0, *, n_epochs, a, b, gamma=1.0, initial_alpha=1.0, negative_sample_rate=5.0,
+                        seed=0):
+    """`oracle_umap_synchronous_f64`: the same firing schedule (float32 arithmetic, as the kernel's) and the same hash, forces
+    and embedding in double -> (y float64 [n, dim], sum of |term| per coordinate in the last epoch, float64 [n, dim])"""
+    lib = _load()
+    y = np.ascontiguousarray(y0, dtype=np.float32)
+    n, dim = y.shape
+    indptr, indices = np.ascontiguousarray(indptr, dtype=np.int64), np.ascontiguousarray(indices, dtype=np.int32)
+    eps = np.ascontiguousarray(eps, dtype=np.float32)
+    out, sabs = np.empty((n, dim), dtype=np.float64), np.empty((n, dim), dtype=np.float64)
+    rc = lib.oracle_umap_synchronous_f64(n, dim, indptr.ctypes.data, indices.ctypes.data, eps.ctypes.data, int(n_epochs), a, b,
+                                         gamma, initial_alpha, float(negative_sample_rate), int(seed) & (2**64 - 1),
+                                         y.ctypes.data, out.ctypes.data, sabs.ctypes.data)
+    if rc != 0:
+        raise RuntimeError(f"oracle umap (float64) failed: {rc}")
+    return out, sabs
 
 
 # ---- layout quality (what the tests compare between the GPU result and the reference scheme) ---------------------

@@ -47,6 +47,7 @@ constexpr unsigned long long POISON = 0xBAD0BAD0BAD0BAD0ull;
 long long g_seq = 0;
 struct Stats {
   long long launches = 0, partial_collectives = 0, mixed_collectives = 0, reads_of_inactive = 0;
+  long long max_dyn_lds = 0;  // the largest dynamic-LDS request of a launch since the last reset
 } g_stats;
 
 Lane g_lanes[MAX_THREADS];
@@ -273,6 +274,7 @@ void launch_body(dim3 grid, dim3 block, size_t shmem, void (*tramp)(void*), void
     if (g_stacks == MAP_FAILED) abort();
   }
   ++g_stats.launches;
+  if ((long long)shmem > g_stats.max_dyn_lds) g_stats.max_dyn_lds = (long long)shmem;
   g_tramp = tramp;
   g_closure = closure;
   // 16-byte aligned dynamic LDS, poisoned per workgroup (LDS is not zero on the hardware either)
@@ -509,6 +511,7 @@ long long emu_launches() { return emu::g_stats.launches; }
 long long emu_partial_collectives() { return emu::g_stats.partial_collectives; }
 long long emu_mixed_collectives() { return emu::g_stats.mixed_collectives; }
 long long emu_reads_of_inactive_lanes() { return emu::g_stats.reads_of_inactive; }
+long long emu_max_dyn_lds() { return emu::g_stats.max_dyn_lds; }
 // event counters a kernel may bump under `#ifdef SCAMD_EMU` (tests/emu/hip/hip_runtime.h declares the array): what the
 // hardware counters cannot say, e.g. how many list insertions a query of the kNN sweep costs (tools/emu_knn_insertions.py)
 void emu_set_dma_late(int late) { emu::g_dma_late = late; }

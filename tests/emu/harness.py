@@ -27,7 +27,7 @@ def load(asan: bool = False, path: str | None = None) -> C.CDLL:
     for name, (res, args) in SIGNATURES.items():
         fn = getattr(lib, name)
         fn.restype, fn.argtypes = res, args
-    for name in ("emu_launches", "emu_partial_collectives", "emu_mixed_collectives", "emu_reads_of_inactive_lanes"):
+    for name in ("emu_launches", "emu_partial_collectives", "emu_mixed_collectives", "emu_reads_of_inactive_lanes", "emu_max_dyn_lds"):
         getattr(lib, name).restype = C.c_longlong
     lib.emu_user_counter.restype, lib.emu_user_counter.argtypes = C.c_longlong, (C.c_int,)
     lib.emu_set_dma_late.restype, lib.emu_set_dma_late.argtypes = None, (C.c_int,)
@@ -391,6 +391,151 @@ class Abi:
         rc = self.lib.scamd_csr_row_stats_f32(m.ptr(ip), m.ptr(dv), n, m.ptr(s), m.ptr(q), m.stream)
         m.sync()
         return rc, m.get(s), m.get(q)
+
+    # ---- csrc/preprocess.hip and csrc/umap.hip (tables: tests/pp_umap_kernel_cases.py) --------------------------------
+    # x: scipy CSR float32.  n / g / nnz: the sizes PASSED, where they are to differ from x's (the argument checks);
+    # null: names of pointer arguments passed as NULL.  Outputs are sized by x and prefilled, whatever sizes are passed.
+    def _pp_in(self, x, n, nnz, null):
+        self._alive = []  # the optional inputs of this call (`_opt`): referenced until the next call
+        ip, ix, dv = self._csr(x)
+        z, p = C.c_void_p(0), self.mem.ptr
+        ptrs = [z if name in null else p(b) for name, b in (("indptr", ip), ("indices", ix), ("data", dv))]
+        return (ip, ix, dv), ptrs, x.shape[0] if n is None else n, x.nnz if nnz is None else nnz
+
+    def _opt(self, a, dtype, name="", null=()):
+        """-> (buffer kept alive, pointer): NULL for None"""
+        if a is None or name in null:
+            return None, C.c_void_p(0)
+        b = self.mem.put(a, dtype)
+        self._alive.append(b)
+        return b, self.mem.ptr(b)
+
+    def pp_row_sums(self, x, col_skip=None, *, n=None, nnz=None, null=()):
+        """-> (rc, out float32 [rows of x], prefilled with NaN)"""
+        m = self.mem
+        keep, (ip, ix, dv), n, nnz = self._pp_in(x, n, nnz, null)
+        _, skip = self._opt(col_skip, np.int32)
+        out = m.full(max(x.shape[0], 1), np.float32, np.nan)
+        rc = self.lib.scamd_pp_row_sums_f32(ip, ix, dv, n, nnz, skip, m.ptr(out), m.stream)
+        m.sync()
+        return rc, m.get(out)[: x.shape[0]]
+
+    def pp_row_count_positive(self, x, *, n=None, nnz=None, null=()):
+        """-> (rc, out int32 [rows of x], prefilled with -1)"""
+        m = self.mem
+        keep, (ip, ix, dv), n, nnz = self._pp_in(x, n, nnz, null)
+        out = m.full(max(x.shape[0], 1), np.int32, -1)
+        rc = self.lib.scamd_pp_row_count_positive_f32(ip, dv, n, nnz, m.ptr(out), m.stream)
+        m.sync()
+        return rc, m.get(out)[: x.shape[0]]
+
+    def pp_count_high(self, x, row_total, max_fraction, *, n=None, g=None, nnz=None, null=()):
+        """-> (rc, col_counts int32 [columns of x], prefilled with -1)"""
+        m = self.mem
+        keep, (ip, ix, dv), n, nnz = self._pp_in(x, n, nnz, null)
+        _, tot = self._opt(row_total, np.float32)
+        out = m.full(max(x.shape[1], 1), np.int32, -1)
+        rc = self.lib.scamd_pp_count_high_f32(ip, ix, dv, n, x.shape[1] if g is None else g, nnz, tot, float(max_fraction), m.ptr(out), m.stream)
+        m.sync()
+        return rc, m.get(out)[: x.shape[1]]
+
+    def pp_row_divide(self, x, factor, *, n=None, nnz=None, null=()):
+        """-> (rc, the stored values after the call)"""
+        m = self.mem
+        keep, (ip, ix, dv), n, nnz = self._pp_in(x, n, nnz, null)
+        data = keep[2]
+        _, fac = self._opt(factor, np.float32)
+        rc = self.lib.scamd_pp_row_divide_f32(ip, dv, n, nnz, fac, m.stream)
+        m.sync()
+        return rc, m.get(data)
+
+    def pp_log1p(self, values, offset=0, base=0.0, *, count=None, null=(), pad=7, fill=-7.0):
+        """the values sit `offset` float32 elements into a 16-byte aligned buffer of `fill`, `pad` more elements of it after
+        them: offset 1..3 hands the kernel a pointer that is NOT 16-byte aligned.  -> (rc, the whole buffer)"""
+        m = self.mem
+        values = np.asarray(values, dtype=np.float32)
+        host = np.full(offset + len(values) + pad, fill, dtype=np.float32)
+        host[offset: offset + len(values)] = values
+        buf = m.put(host, np.float32)
+        addr = m.ptr(buf).value
+        assert addr % 16 == 0, "the allocator was expected to hand out 16-byte aligned buffers"
+        ptr = C.c_void_p(0) if "data" in null else C.c_void_p(addr + 4 * offset)
+        rc = self.lib.scamd_pp_log1p_f32(ptr, len(values) if count is None else count, float(base), m.stream)
+        m.sync()
+        return rc, m.get(buf)
+
+    def pp_col_stats(self, x, row_mask=None, transform=0, tscale=1.0, *, n=None, g=None, nnz=None, null=(), want_npos=True):
+        """-> (rc, sum float64 [g], sumsq float64 [g], npos [g] read as int64, or None), prefilled with NaN / -1"""
+        m = self.mem
+        keep, (ip, ix, dv), n, nnz = self._pp_in(x, n, nnz, null)
+        g = x.shape[1] if g is None else g
+        ga = max(min(g, 1 << 16), 1)
+        _, mask = self._opt(row_mask, np.uint8)
+        s, q = m.full(ga, np.float64, np.nan), m.full(ga, np.float64, np.nan)
+        cnt = m.full(ga, np.int64, -1) if want_npos else None
+        z = C.c_void_p(0)
+        rc = self.lib.scamd_pp_col_stats_f32(ip, ix, dv, n, g, nnz, mask, int(transform), float(tscale), z if "sum" in null else m.ptr(s),
+                                             m.ptr(q), m.ptr(cnt) if want_npos else z, m.stream)
+        m.sync()
+        return rc, m.get(s), m.get(q), m.get(cnt) if want_npos else None
+
+    def pp_col_stats_clip(self, x, clip, row_mask=None, *, n=None, g=None, nnz=None, null=()):
+        """-> (rc, sum float64 [g], sumsq float64 [g]), prefilled with NaN"""
+        m = self.mem
+        keep, (ip, ix, dv), n, nnz = self._pp_in(x, n, nnz, null)
+        g = x.shape[1] if g is None else g
+        ga = max(min(g, 1 << 16), 1)
+        _, mask = self._opt(row_mask, np.uint8)
+        _, cl = self._opt(clip, np.float64, "clip", null)
+        s, q = m.full(ga, np.float64, np.nan), m.full(ga, np.float64, np.nan)
+        rc = self.lib.scamd_pp_col_stats_clip_f32(ip, ix, dv, n, g, nnz, mask, cl, m.ptr(s), m.ptr(q), m.stream)
+        m.sync()
+        return rc, m.get(s), m.get(q)
+
+    def pp_scale_csr(self, x, std, max_value=None, row_mask=None, *, n=None, nnz=None, null=()):
+        """-> (rc, the stored values after the call)"""
+        m = self.mem
+        keep, (ip, ix, dv), n, nnz = self._pp_in(x, n, nnz, null)
+        data = keep[2]
+        _, sd = self._opt(std, np.float64)
+        _, mask = self._opt(row_mask, np.uint8)
+        rc = self.lib.scamd_pp_scale_csr_f32(ip, ix, dv, n, nnz, sd, float(max_value or 0.0), int(max_value is not None), mask, m.stream)
+        m.sync()
+        return rc, m.get(data)
+
+    def pp_scale_dense(self, x, mean, std, max_value=None, row_mask=None, out_f64=True, *, n=None, g=None, nnz=None, null=()):
+        """-> (rc, out [rows of x, columns of x] float64 | float32, prefilled with NaN)"""
+        m = self.mem
+        keep, (ip, ix, dv), n, nnz = self._pp_in(x, n, nnz, null)
+        _, mu = self._opt(mean, np.float64)
+        _, sd = self._opt(std, np.float64)
+        _, mask = self._opt(row_mask, np.uint8)
+        out = m.full((max(x.shape[0], 1), max(x.shape[1], 1)), np.float64 if out_f64 else np.float32, np.nan)
+        rc = self.lib.scamd_pp_scale_dense_f32(ip, ix, dv, n, x.shape[1] if g is None else g, nnz, mu, sd, float(max_value or 0.0),
+                                               int(max_value is not None), mask, m.ptr(out), int(out_f64), m.stream)
+        m.sync()
+        return rc, m.get(out)
+
+    def umap_workspace_bytes(self, n, nnz, dim):
+        return int(self.lib.scamd_umap_workspace_bytes(int(n), int(nnz), int(dim)))
+
+    def umap_optimize(self, indptr, indices, eps, y0, *, n_epochs, a, b, gamma=1.0, initial_alpha=1.0, negative_sample_rate=5.0,
+                      seed=0, dim=None, ws_short=0, null=()):
+        """y0 float32 [n, dim] (`dim`: the value PASSED, where it is to differ) -> (rc, y after the call)"""
+        m, lib = self.mem, self.lib
+        n, d = y0.shape
+        nnz = int(len(indices))
+        dim = d if dim is None else dim
+        ip = m.put(indptr, np.int64)
+        ix, ep = m.put(indices, np.int32), m.put(eps, np.float32)
+        y = m.put(y0, np.float32)
+        ws, wsz = self._ws(lib.scamd_umap_workspace_bytes(n, nnz, dim), ws_short)
+        z, p = C.c_void_p(0), m.ptr
+        rc = lib.scamd_umap_optimize_f32(z if "indptr" in null else p(ip), p(ix), p(ep), n, nnz, dim, int(n_epochs), float(a), float(b),
+                                         float(gamma), float(initial_alpha), float(negative_sample_rate), int(seed) & (2**64 - 1),
+                                         z if "y" in null else p(y), p(ws), wsz, m.stream)
+        m.sync()
+        return rc, m.get(y)
 
 
 def abi(lib) -> Abi:
