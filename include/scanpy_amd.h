@@ -414,6 +414,24 @@ int scamd_leiden_tier_bounds(int lanes, int* main_max, int* wave_max, int* block
 int scamd_leiden_debug_split_f32(const int64_t* indptr, const int32_t* indices, const float* weights,
                                  int64_t n, int64_t nnz, int32_t* membership, int32_t* n_split_host,
                                  void* workspace, size_t workspace_bytes, scamd_stream_t stream);
+/* Test entry: ONE level of a Leiden iteration on a given partition, by the functions the run itself calls -- the refinement
+ * of `membership` (ids in [0, n), device) at `resolution`, `beta` and `seed` as scamd_leiden_csr_f32 takes them, then the
+ * coarse graph under the refined partition.  refined_in != NULL (device, [n]: the id of a refined group is one of its members,
+ * every group lies inside one community): the refinement is skipped and the coarse graph is built under refined_in.
+ * Device outputs, the caller's: refined, Kref, Eref, refsize [n] (the sums and the size of a group at its representative: total
+ * vertex weight, weight to the rest of its community -- zero when refined_in is given -- and members; zero elsewhere);
+ * cid [n] (vertex -> coarse vertex), coarse_indptr [n + 1], coarse_indices / coarse_wq [nnz] (weights in units of 2^-32),
+ * coarse_k [n] (strengths), coarse_comm [n] (the community of a coarse vertex, named by its smallest coarse vertex): the first
+ * n_coarse + 1 / coarse nnz / n_coarse elements are written.  info_host [8]: merges, n_coarse, coarse nnz, rows built by
+ * the 512-thread builder, by the 1024-thread builder, by the split path, 1 if nothing merged (n_coarse == n: no graph is
+ * built and nothing from cid on is written), 0.  The SCAMD_LEIDEN_QUAD, SCAMD_LEIDEN_AGG_* and SCAMD_LEIDEN_HUB_TRY_PROBES
+ * switches apply as in a run.  Workspace: scamd_leiden_workspace_bytes. */
+int scamd_leiden_debug_level_f32(const int64_t* indptr, const int32_t* indices, const float* weights, int64_t n,
+                                 int64_t nnz, const int32_t* membership, const int32_t* refined_in, double resolution,
+                                 double beta, uint64_t seed, int32_t* refined, uint64_t* Kref, uint64_t* Eref,
+                                 int32_t* refsize, int32_t* cid, int64_t* coarse_indptr, int32_t* coarse_indices,
+                                 int64_t* coarse_wq, int64_t* coarse_k, int32_t* coarse_comm, int64_t* info_host,
+                                 void* workspace, size_t workspace_bytes, scamd_stream_t stream);
 /* Modularity of a given membership (replaces igraph Graph.modularity as used by
  * src/scanpy/metrics/_metrics.py:202-214). */
 int scamd_modularity_csr_f32(const int64_t* indptr, const int32_t* indices, const float* weights,

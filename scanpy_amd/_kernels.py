@@ -588,6 +588,43 @@ def leiden_tier_bounds(lanes: int):
     return a.value, b.value, c.value
 
 
+LEVEL_INFO_KEYS = ("merges", "n_coarse", "coarse_nnz", "n_mid", "n_big", "n_split", "skipped")
+
+
+def leiden_debug_level(indptr: torch.Tensor, indices: torch.Tensor, weights: torch.Tensor, n: int, membership: torch.Tensor, *,
+                       refined_in: torch.Tensor | None = None, resolution: float = 1.0, beta: float = 0.01, seed: int = 0) -> dict:
+    """Test entry scamd_leiden_debug_level_f32: the refinement of `membership` (skipped when `refined_in` is given) and the
+    coarse graph under the refined partition -> dict of device tensors (refined, Kref, Eref, refsize, and, unless `skipped`, cid,
+    indptr, indices, wq, k, comm cut to their lengths) plus the integers of LEVEL_INFO_KEYS."""
+    dev = require_gpu()
+    lib = _lib.load()
+    indptr = indptr.to(torch.int64).contiguous()
+    indices = indices.to(torch.int32).contiguous()
+    weights = weights.to(torch.float32).contiguous()
+    membership = membership.to(device=dev, dtype=torch.int32).contiguous()
+    given = None if refined_in is None else refined_in.to(device=dev, dtype=torch.int32).contiguous()
+    if membership.numel() != n or (given is not None and given.numel() != n):
+        raise ValueError(f"membership / refined_in must have {n} entries")
+    nnz = weights.numel()
+    i32 = lambda m: _empty(max(m, 1), dtype=torch.int32, device=dev)  # noqa: E731
+    i64 = lambda m: _empty(max(m, 1), dtype=torch.int64, device=dev)  # noqa: E731
+    out = dict(refined=i32(n), Kref=i64(n), Eref=i64(n), refsize=i32(n), cid=i32(n), indptr=i64(n + 1), indices=i32(nnz), wq=i64(nnz),
+               k=i64(n), comm=i32(n))
+    ws, wsz = _ws(lib.scamd_leiden_workspace_bytes(n, nnz), dev)
+    info = (C.c_int64 * 8)()
+    rc = lib.scamd_leiden_debug_level_f32(ptr(indptr), ptr(indices), ptr(weights), n, nnz, ptr(membership), ptr(given), float(resolution),
+                                          float(beta), int(seed) & (2**64 - 1), *(ptr(out[key]) for key in out), info, ptr(ws), wsz,
+                                          stream_ptr())
+    _check(rc, "scamd_leiden_debug_level_f32")
+    res = dict(zip(LEVEL_INFO_KEYS, (int(v) for v in info)))
+    nn, ne = res["n_coarse"], res["coarse_nnz"]
+    cut = dict(refined=n, Kref=n, Eref=n, refsize=n, cid=n, indptr=nn + 1, indices=ne, wq=ne, k=nn, comm=nn)
+    for key, m in cut.items():
+        if not res["skipped"] or key in ("refined", "Kref", "Eref", "refsize"):
+            res[key] = out[key][:m]
+    return res
+
+
 def modularity(indptr: torch.Tensor, indices: torch.Tensor, weights: torch.Tensor, n: int, membership: torch.Tensor,
                *, resolution: float = 1.0) -> float:
     dev = require_gpu()

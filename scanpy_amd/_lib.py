@@ -72,6 +72,8 @@ SIGNATURES = {
     "scamd_leiden_stat_name": (C.c_char_p, [_i32]),
     "scamd_leiden_tier_bounds": (_i32, [_i32, C.POINTER(_i32), C.POINTER(_i32), C.POINTER(_i32)]),
     "scamd_leiden_debug_split_f32": (_i32, [_vp, _vp, _vp, _i64, _i64, _vp, C.POINTER(_i32), _vp, _sz, _vp]),
+    "scamd_leiden_debug_level_f32": (_i32, [_vp, _vp, _vp, _i64, _i64, _vp, _vp, _f64, _f64, _u64, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp,
+                                            C.POINTER(_i64), _vp, _sz, _vp]),
     "scamd_modularity_csr_f32": (_i32, [_vp, _vp, _vp, _i64, _i64, _vp, _f64, C.POINTER(_f64), _vp, _sz, _vp]),
     "scamd_pp_row_sums_f32": (_i32, [_vp, _vp, _vp, _i64, _i64, _vp, _vp, _vp]),
     "scamd_pp_row_count_positive_f32": (_i32, [_vp, _vp, _i64, _i64, _vp, _vp]),

@@ -1583,6 +1583,22 @@ __global__ void ld_refine_init_kernel(int n, const long long* __restrict__ k, co
   }
 }
 
+// Test entry scamd_leiden_debug_level_f32 with a caller-supplied refined partition: ref[v] = given[v]; *err |= 1 when an id
+// lies outside [0, n), |= 2 when a group is not named by one of its members or does not lie inside one community of `comm`
+__global__ void ld_given_ref_kernel(int n, const int* __restrict__ given, const int* __restrict__ comm, int* __restrict__ ref,
+                                    int* __restrict__ err) {
+  const int v = blockIdx.x * blockDim.x + threadIdx.x;
+  if (v >= n) return;
+  const int r = given[v];
+  if (r < 0 || r >= n) {
+    atomicOr(err, 1);
+    ref[v] = v;
+    return;
+  }
+  if (given[r] != r || comm[r] != comm[v]) atomicOr(err, 2);
+  ref[v] = r;
+}
+
 // ---- phase 3: aggregation --------------------------------------------------------------------------
 __global__ void ld_flag_kernel(int n, const int* __restrict__ size, int* __restrict__ flag, int* __restrict__ fill_max) {
   int v = blockIdx.x * blockDim.x + threadIdx.x;
@@ -2830,6 +2846,9 @@ struct LeidenCtx {
   int agg_mid_work = 65536;
   int hub_try_probes = HUB_TRY_PROBES;  // 0: no optimistic single pass over multi-pass rows (SCAMD_LEIDEN_HUB_TRY_PROBES; tests)
   int64_t agg_split_chunk = 0, agg_split_work = 0;  // (agg_split_chunk() / agg_split_work(): as the workspace query saw them)
+  // rows the last aggregate() handed to the 512-thread builder, the 1024-thread builder, the split path (the debug trace and
+  // the test entry scamd_leiden_debug_level_f32 report them)
+  int agg_rows_mid = 0, agg_rows_big = 0, agg_rows_split = 0;
   // ---- the stored hierarchy (StoredLevel) ----
   size_t cap_e = 0, cap_p = 0, cap_c = 0;  // pool capacities: entries, row pointers / vertex weights, map elements
   StoredLevel lv[MAX_LEVELS + 1];          // [l], l >= 1: level l as the running iteration sees it
@@ -3437,6 +3456,9 @@ static int aggregate(LeidenCtx& cx, const LevelGraph& g, int n_orig, int level, 
   LD_FETCH(htier, b.counters + PH_AGG_MID, sizeof(htier), cx.s);
   LD_SYNC(cx.s);
   const int n_mid = htier[0], n_big = htier[1], n_split = htier[2];
+  cx.agg_rows_mid = n_mid;
+  cx.agg_rows_big = n_big;
+  cx.agg_rows_split = n_split;
   if (cx.debug && (n_mid || n_big))
     fprintf(stderr, "[leiden] aggregate n=%d -> %d: %d rows through the workgroup tier, %d through the 8192-slot tier\n", g.n, inn,
             n_mid, n_big);
@@ -3790,23 +3812,8 @@ static int accept_iteration(LeidenCtx& cx, const LevelGraph& g0, int it, double*
   return SCAMD_OK;
 }
 
-static int leiden_run(const LeidenCall& c) {
-  SCAMD_REQUIRE(c.membership, SCAMD_EINVAL, "leiden: null pointer");
-  SCAMD_REQUIRE(c.resolution >= 0.0, SCAMD_EINVAL, "leiden: negative resolution");
-  for (int i = 0; i < LD_NSTATS; ++i) g_ld_stats[i] = 0;
-  g_ld_sweep_bytes = 0.0;
-  const int64_t n = c.n;
-  const int n_iterations = c.n_iterations;
-  LeidenCtx cx;
-  cx.gamma = c.resolution;
-  cx.inv_beta = c.beta > 0.0 ? 1.0 / (c.beta * WSCALE) : 0.0;  // beta <= 0: the greedy limit (largest gain, no "stay")
-  cx.seed = (unsigned int)(c.seed ^ (c.seed >> 32)) * 0x9E3779B1u + 0x632BE5ABu;
-  cx.cpm = c.objective == 1;
-  cx.node_weights = c.node_weights;
-  LevelGraph g0;
-  int rc = leiden_open(cx, "leiden", c.indptr, c.indices, c.weights, n, c.nnz, c.workspace, c.workspace_bytes, c.stream, &g0);
-  if (rc != SCAMD_OK) return rc;
-  if (cx.cpm) cx.small_levels = false;  // (ld_small_levels_kernel derives its coarse vertex weights from row sums: strengths)
+// the kernels whose dynamic LDS exceeds the default limit of a launch (every entry that may launch one asks first)
+static int allow_dynamic_lds() {
   const struct {
     const void* kernel;
     size_t lds;
@@ -3816,6 +3823,33 @@ static int leiden_run(const LeidenCall& c) {
                  {reinterpret_cast<const void*>(ld_agg_block_kernel<BHUB_SLOTS, 1024>), HUB_LDS},
                  {reinterpret_cast<const void*>(ld_small_levels_kernel), sizeof(SmallLds)}};
   for (const auto& k : dyn_lds) SCAMD_HIP_CHECK(hipFuncSetAttribute(k.kernel, hipFuncAttributeMaxDynamicSharedMemorySize, (int)k.lds));
+  return SCAMD_OK;
+}
+
+// the merge rule's parameters as a run derives them from its arguments
+static void set_rule(LeidenCtx& cx, double resolution, double beta, uint64_t seed) {
+  cx.gamma = resolution;
+  cx.inv_beta = beta > 0.0 ? 1.0 / (beta * WSCALE) : 0.0;  // beta <= 0: the greedy limit (largest gain, no "stay")
+  cx.seed = (unsigned int)(seed ^ (seed >> 32)) * 0x9E3779B1u + 0x632BE5ABu;
+}
+
+static int leiden_run(const LeidenCall& c) {
+  SCAMD_REQUIRE(c.membership, SCAMD_EINVAL, "leiden: null pointer");
+  SCAMD_REQUIRE(c.resolution >= 0.0, SCAMD_EINVAL, "leiden: negative resolution");
+  for (int i = 0; i < LD_NSTATS; ++i) g_ld_stats[i] = 0;
+  g_ld_sweep_bytes = 0.0;
+  const int64_t n = c.n;
+  const int n_iterations = c.n_iterations;
+  LeidenCtx cx;
+  set_rule(cx, c.resolution, c.beta, c.seed);
+  cx.cpm = c.objective == 1;
+  cx.node_weights = c.node_weights;
+  LevelGraph g0;
+  int rc = leiden_open(cx, "leiden", c.indptr, c.indices, c.weights, n, c.nnz, c.workspace, c.workspace_bytes, c.stream, &g0);
+  if (rc != SCAMD_OK) return rc;
+  if (cx.cpm) cx.small_levels = false;  // (ld_small_levels_kernel derives its coarse vertex weights from row sums: strengths)
+  rc = allow_dynamic_lds();
+  if (rc != SCAMD_OK) return rc;
   LeidenBuffers& b = cx.b;
   if (c.initial_membership) {
     // (b.counters[PHASE_ERR] is zero: setup_level0 cleared the counters and checked whatever it raised)
@@ -4016,6 +4050,90 @@ extern "C" int scamd_leiden_debug_split_f32(const int64_t* indptr, const int32_t
   }
   SCAMD_HIP_CHECK(hipStreamSynchronize(cx.s));
   *n_split_host = n_split;
+  return SCAMD_OK;
+}
+
+// Test entry: ONE level of an iteration on a GIVEN partition -- the refinement and the coarse graph, by the functions the run
+// itself calls (leiden_open, ld_iter_init_kernel, compute_totals, refinement, aggregate), with their results copied out.
+// refined_in != NULL: the refinement is skipped and the coarse graph is built under the caller's refined partition (group
+// shapes chosen, not drawn); Kref and refsize are then its totals (ld_totals_kernel), Eref is zero.
+extern "C" int scamd_leiden_debug_level_f32(const int64_t* indptr, const int32_t* indices, const float* weights, int64_t n,
+                                            int64_t nnz, const int32_t* membership, const int32_t* refined_in, double resolution,
+                                            double beta, uint64_t seed, int32_t* refined, uint64_t* Kref, uint64_t* Eref,
+                                            int32_t* refsize, int32_t* cid, int64_t* coarse_indptr, int32_t* coarse_indices,
+                                            int64_t* coarse_wq, int64_t* coarse_k, int32_t* coarse_comm, int64_t* info_host,
+                                            void* workspace, size_t workspace_bytes, scamd_stream_t stream) {
+  SCAMD_REQUIRE(membership && refined && Kref && Eref && refsize && cid && coarse_indptr && coarse_k && coarse_comm && info_host &&
+                    (nnz == 0 || (coarse_indices && coarse_wq)),
+                SCAMD_EINVAL, "leiden level: null pointer");
+  SCAMD_REQUIRE(resolution >= 0.0, SCAMD_EINVAL, "leiden level: negative resolution");
+  for (int i = 0; i < LD_NSTATS; ++i) g_ld_stats[i] = 0;  // (scamd_leiden_last_stats: the tiers of the propose steps of this call)
+  g_ld_sweep_bytes = 0.0;
+  LeidenCtx cx;
+  set_rule(cx, resolution, beta, seed);
+  LevelGraph g0;
+  int rc = leiden_open(cx, "leiden level", indptr, indices, weights, n, nnz, workspace, workspace_bytes, stream, &g0);
+  if (rc == SCAMD_OK) rc = allow_dynamic_lds();
+  if (rc != SCAMD_OK) return rc;
+  LeidenBuffers& b = cx.b;
+  const int in = (int)n;
+  // (b.counters[PHASE_ERR] is zero: setup_level0 cleared the counters and checked whatever it raised)
+  hipLaunchKernelGGL(ld_copy_membership_kernel, GRID1(n), 0, cx.s, in, membership, b.memb, b.counters + PHASE_ERR);
+  SCAMD_LAUNCH_CHECK();
+  hipLaunchKernelGGL(ld_iter_init_kernel, GRID1(n), 0, cx.s, in, (const int*)b.memb, b.comm, b.node_of);
+  SCAMD_LAUNCH_CHECK();
+  if (refined_in) {
+    hipLaunchKernelGGL(ld_given_ref_kernel, GRID1(n), 0, cx.s, in, refined_in, (const int*)b.comm, b.ref, b.counters + PHASE_ERR);
+    SCAMD_LAUNCH_CHECK();
+  }
+  int bad = 0;
+  LD_FETCH(&bad, b.counters + PHASE_ERR, sizeof(int), cx.s);
+  LD_SYNC(cx.s);
+  SCAMD_REQUIRE(bad == 0, SCAMD_EINVAL,
+                "leiden level: ids must lie in [0, n), a refined group is named by one of its members and lies inside one community");
+  int merged = 0;
+  if (refined_in) {
+    rc = run_fill(cx, Filler().add(b.Kref, sizeof(unsigned long long) * n).add(b.Eref, sizeof(unsigned long long) * n).add(b.refsize, sizeof(int) * n));
+    if (rc != SCAMD_OK) return rc;
+    hipLaunchKernelGGL(ld_totals_kernel, dim3((unsigned)std::min(REDUCE_GRID, ceil_div(in, 1024))), dim3(1024), 0, cx.s, (const int*)b.ref,
+                       g0.k, in, b.Kref, b.refsize, (unsigned long long*)nullptr);
+    SCAMD_LAUNCH_CHECK();
+  } else {
+    SCAMD_REQUIRE(cx.m2 > 0.0, SCAMD_EINVAL, "leiden level: the refinement needs a graph with weight");
+    rc = compute_totals(cx, g0, b.comm);
+    if (rc == SCAMD_OK) rc = refinement(cx, g0, &merged);
+    if (rc != SCAMD_OK) return rc;
+  }
+  // (before aggregate(): it borrows refinement scratch and swaps b.comm)
+  SCAMD_HIP_CHECK(hipMemcpyAsync(refined, b.ref, sizeof(int) * n, hipMemcpyDeviceToDevice, cx.s));
+  SCAMD_HIP_CHECK(hipMemcpyAsync(Kref, b.Kref, sizeof(unsigned long long) * n, hipMemcpyDeviceToDevice, cx.s));
+  SCAMD_HIP_CHECK(hipMemcpyAsync(Eref, b.Eref, sizeof(unsigned long long) * n, hipMemcpyDeviceToDevice, cx.s));
+  SCAMD_HIP_CHECK(hipMemcpyAsync(refsize, b.refsize, sizeof(int) * n, hipMemcpyDeviceToDevice, cx.s));
+  LevelGraph gc;
+  int n_new = 0;
+  rc = aggregate(cx, g0, in, 0, &gc, &n_new);
+  if (rc != SCAMD_OK) return rc;
+  const bool skipped = n_new == in;  // nothing merged: aggregate() builds no graph
+  if (!skipped) {
+    const size_t nn = (size_t)gc.n, ne = (size_t)gc.nnz;
+    SCAMD_HIP_CHECK(hipMemcpyAsync(cid, cx.lv[1].cid, sizeof(int) * n, hipMemcpyDeviceToDevice, cx.s));
+    SCAMD_HIP_CHECK(hipMemcpyAsync(coarse_indptr, gc.indptr, sizeof(int64_t) * (nn + 1), hipMemcpyDeviceToDevice, cx.s));
+    if (ne > 0) {
+      SCAMD_HIP_CHECK(hipMemcpyAsync(coarse_indices, gc.indices, sizeof(int) * ne, hipMemcpyDeviceToDevice, cx.s));
+      SCAMD_HIP_CHECK(hipMemcpyAsync(coarse_wq, gc.wq, sizeof(long long) * ne, hipMemcpyDeviceToDevice, cx.s));
+    }
+    SCAMD_HIP_CHECK(hipMemcpyAsync(coarse_k, gc.k, sizeof(long long) * nn, hipMemcpyDeviceToDevice, cx.s));
+    SCAMD_HIP_CHECK(hipMemcpyAsync(coarse_comm, b.comm, sizeof(int) * nn, hipMemcpyDeviceToDevice, cx.s));
+  }
+  SCAMD_HIP_CHECK(hipStreamSynchronize(cx.s));
+  info_host[0] = refined_in ? (int64_t)(in - n_new) : (int64_t)merged;
+  info_host[1] = n_new;
+  info_host[2] = skipped ? 0 : gc.nnz;
+  info_host[3] = skipped ? 0 : cx.agg_rows_mid;
+  info_host[4] = skipped ? 0 : cx.agg_rows_big;
+  info_host[5] = skipped ? 0 : cx.agg_rows_split;
+  info_host[6] = skipped ? 1 : 0;
+  info_host[7] = 0;
   return SCAMD_OK;
 }
 

@@ -130,6 +130,39 @@ def leiden_split(lib, adj, membership):
     return memb, int(ns.value)
 
 
+LEVEL_INFO_KEYS = ("merges", "n_coarse", "coarse_nnz", "n_mid", "n_big", "n_split", "skipped")
+
+
+def leiden_level(lib, adj, membership, *, refined_in=None, resolution=1.0, beta=0.01, seed=0) -> dict:
+    """scamd_leiden_debug_level_f32 -> dict: refined, Kref, Eref, refsize [n], the integers of LEVEL_INFO_KEYS and, unless
+    `skipped`, cid [n] and the coarse indptr, indices, wq, k, comm cut to their lengths.  `adj` goes in as it is stored (no
+    sorting, no merging of its entries)."""
+    n = adj.shape[0]
+    indptr = np.ascontiguousarray(adj.indptr, dtype=np.int64)
+    indices = np.ascontiguousarray(adj.indices, dtype=np.int32)
+    w = np.ascontiguousarray(adj.data, dtype=np.float32)
+    nnz = int(indptr[-1])
+    memb = np.ascontiguousarray(membership, dtype=np.int32)
+    given = None if refined_in is None else np.ascontiguousarray(refined_in, dtype=np.int32)
+    assert memb.size == n and (given is None or given.size == n)
+    i32 = lambda m: np.full(max(m, 1), -7, dtype=np.int32)  # noqa: E731
+    i64 = lambda m: np.full(max(m, 1), -7, dtype=np.int64)  # noqa: E731
+    out = dict(refined=i32(n), Kref=i64(n), Eref=i64(n), refsize=i32(n), cid=i32(n), indptr=i64(n + 1), indices=i32(nnz), wq=i64(nnz),
+               k=i64(n), comm=i32(n))
+    info = (C.c_int64 * 8)()
+    ws = _ws(lib.scamd_leiden_workspace_bytes(n, nnz))
+    rc = lib.scamd_leiden_debug_level_f32(_p(indptr), _p(indices), _p(w), n, nnz, _p(memb), _p(given), float(resolution), float(beta),
+                                          int(seed), *(_p(out[key]) for key in out), info, _p(ws), ws.size, None)
+    _check(lib, rc, "leiden level")
+    res = dict(zip(LEVEL_INFO_KEYS, (int(v) for v in info)))
+    nn, ne = res["n_coarse"], res["coarse_nnz"]
+    cut = dict(refined=n, Kref=n, Eref=n, refsize=n, cid=n, indptr=nn + 1, indices=ne, wq=ne, k=nn, comm=nn)
+    for key, m in cut.items():
+        if not res["skipped"] or key in ("refined", "Kref", "Eref", "refsize"):
+            res[key] = out[key][:m]
+    return res
+
+
 def leiden_stats(lib) -> dict:
     keys = leiden_stat_names(lib)
     out = (C.c_int32 * len(keys))()
