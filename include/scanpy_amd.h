@@ -536,6 +536,64 @@ int scamd_rank_genes_wilcoxon_f32(const int64_t* t_indptr, const int32_t* t_indi
                                   void* workspace, size_t workspace_bytes, scamd_stream_t stream);
 
 /* ------------------------------------------------------------------------------------------
+ * Harmony batch correction (`sc.pp.harmony_integrate`; src/scanpy/preprocessing/_harmony/core.py), csrc/harmony.hip.
+ * All arithmetic is float64.  z_norm / x [n x d], R [n x K], O / E / lambda_kb [n_levels x K], centroids / y_norm [K x d],
+ * codes int32[n] with 0 <= code < n_levels, pr_b / theta / n_b float64[n_levels] (cells of a level / n, the penalty
+ * weight after the tau discount, cells of a level).  Limits (SCAMD_EUNSUPPORTED beyond, nothing written): d <= 128,
+ * K <= 256, n_levels <= 1024, n < 2^31, n_covariates == 1 (several batch variables need the general-design ridge solve).
+ * Every sum over cells is rounded once per term (or per fixed chunk of cells) to 64-bit fixed point and added in
+ * integers: all outputs are bitwise reproducible.
+ *
+ * scamd_harmony_permutation_i32: perm = a keyed bijection on [0, n) (6-round Feistel network with cycle walking) of
+ *   (seed, round); element i is computed on its own.
+ * scamd_harmony_normalize_f64: rows of x divided by max(their Euclidean norm, 1e-12).
+ * scamd_harmony_kmeans_f64: k-means++ seeding by D^2 sampling driven by K uniforms in [0, 1) (host array): centre 0 is cell
+ *   floor(u_0 n), centre c the first cell whose running sum of D^2 exceeds u_c * total; then at most max_iter Lloyd sweeps
+ *   (ties to the lowest centre, an empty centre stays), stopping after the sweep that changes no label.
+ *   *n_iter_host = sweeps run.  Synchronises the stream.
+ * scamd_harmony_init_f64: R = exp(-2/sigma (1 - z_norm . y_norm)) with rows divided by max(sum, 1e-12) (y_norm = the
+ *   normalised centroids), O[b, k] = sum of R[i, k] over the cells of level b, E = pr_b (x) column sums of R,
+ *   objective[4] = total, k-means error, entropy term, diversity term.  stabilized != 0: the harmony2 penalty
+ *   (denominator O + E + 1), else harmony1 (O + 1).
+ * scamd_harmony_cluster_round_f64: one clustering iteration: y_norm = rows of R^T z_norm normalised; the cells
+ *   perm[0..n) cut into n_blocks blocks (the first n % n_blocks hold one cell more) processed one after another -- take
+ *   the block's rows out of O and E, penalty theta_b (log(E + 1) - log(O [+ E] + 1)) of each cell's level, row-max-shifted
+ *   softmax with the sum clamped at 1e-12, put the new rows back; then the objective as above.  R, E, O in/out.
+ * scamd_harmony_correct_f64: lambda_kb (harmony2, dynamic_lambda != 0: alpha E, 1e30 where O / n_b <
+ *   batch_prune_threshold or n_b = 0, a negative threshold prunes nothing; harmony1: ridge_lambda; 1e30 where O + lambda
+ *   = 0), the closed-form single-variable ridge correction z_hat = x - sum_k R[:, k] W_k[code], z_norm = its normalised
+ *   rows.  lambda_kb_out may be NULL.
+ * init and cluster_round share scamd_harmony_state_workspace_bytes.
+ * ---------------------------------------------------------------------------------------- */
+#define SCAMD_HARMONY_MAX_D 128
+#define SCAMD_HARMONY_MAX_K 256
+#define SCAMD_HARMONY_MAX_LEVELS 1024
+size_t scamd_harmony_permutation_workspace_bytes(int64_t n);
+int scamd_harmony_permutation_i32(int64_t n, uint64_t seed, uint64_t round, int32_t* perm, void* workspace,
+                                  size_t workspace_bytes, scamd_stream_t stream);
+int scamd_harmony_normalize_f64(const double* x, int64_t n, int d, double* z_norm, scamd_stream_t stream);
+size_t scamd_harmony_kmeans_workspace_bytes(int64_t n, int d, int K);
+int scamd_harmony_kmeans_f64(const double* z_norm, int64_t n, int d, int K, const double* uniforms_host, int max_iter,
+                             double* centroids, int32_t* labels, int* n_iter_host, void* workspace,
+                             size_t workspace_bytes, scamd_stream_t stream);
+size_t scamd_harmony_state_workspace_bytes(int64_t n, int d, int K, int n_levels);
+int scamd_harmony_init_f64(const double* z_norm, const int32_t* codes, int64_t n, int d, int K, int n_levels,
+                           int n_covariates, const double* centroids, const double* pr_b, const double* theta,
+                           double sigma, int stabilized, double* R, double* E, double* O, double* objective,
+                           void* workspace, size_t workspace_bytes, scamd_stream_t stream);
+int scamd_harmony_cluster_round_f64(const double* z_norm, const int32_t* codes, int64_t n, int d, int K, int n_levels,
+                                    int n_covariates, const int32_t* perm, int64_t n_blocks, const double* pr_b,
+                                    const double* theta, double sigma, int stabilized, double* R, double* E, double* O,
+                                    double* y_norm, double* objective, void* workspace, size_t workspace_bytes,
+                                    scamd_stream_t stream);
+size_t scamd_harmony_correct_workspace_bytes(int64_t n, int d, int K, int n_levels);
+int scamd_harmony_correct_f64(const double* x, const int32_t* codes, int64_t n, int d, int K, int n_levels,
+                              int n_covariates, const double* R, const double* O, const double* E, const double* n_b,
+                              int dynamic_lambda, double alpha, double batch_prune_threshold, double ridge_lambda,
+                              double* z_hat, double* z_norm, double* lambda_kb_out /* may be NULL */, void* workspace,
+                              size_t workspace_bytes, scamd_stream_t stream);
+
+/* ------------------------------------------------------------------------------------------
  * UMAP layout: the SGD of umap-learn's optimize_layout_euclidean, which
  * simplicial_set_embedding runs for sc.tl.umap (src/scanpy/tools/_umap.py:196-216), in a synchronous, race-free
  * gather formulation (csrc/umap.hip).  Input: CSR of the pruned symmetric fuzzy graph (indptr [n+1], indices [nnz]),

@@ -789,3 +789,100 @@ def umap_optimize_(indptr, indices, epochs_per_sample, n: int, y: torch.Tensor, 
                                      float(a), float(b), float(gamma), float(initial_alpha), float(negative_sample_rate),
                                      int(seed) & (2**64 - 1), ptr(y), ptr(ws), wsz, stream_ptr())
     _check(rc, "scamd_umap_optimize_f32")
+
+
+# ---- Harmony batch correction (csrc/harmony.hip) -------------------------------------------------------------------
+def _f64c(t: torch.Tensor) -> torch.Tensor:
+    if t.dtype != torch.float64 or not t.is_contiguous() or not t.is_cuda:
+        raise ValueError(f"harmony: expected a contiguous float64 device tensor, got {t.dtype} on {t.device}, contiguous={t.is_contiguous()}")
+    return t
+
+
+def harmony_permutation(n: int, seed: int, rnd: int) -> torch.Tensor:
+    """-> perm int32 [n]: the keyed bijection on [0, n) of (seed, round)."""
+    dev = require_gpu()
+    perm = _empty(n, dtype=torch.int32, device=dev)
+    rc = _lib.load().scamd_harmony_permutation_i32(n, int(seed) & (2**64 - 1), int(rnd) & (2**64 - 1), ptr(perm), None, 0, stream_ptr())
+    _check(rc, "scamd_harmony_permutation_i32")
+    return perm
+
+
+def harmony_normalize(x: torch.Tensor) -> torch.Tensor:
+    dev = require_gpu()
+    n, d = _f64c(x).shape
+    out = _empty((n, d), dtype=torch.float64, device=dev)
+    rc = _lib.load().scamd_harmony_normalize_f64(ptr(x), n, d, ptr(out), stream_ptr())
+    _check(rc, "scamd_harmony_normalize_f64")
+    return out
+
+
+def harmony_kmeans(z_norm: torch.Tensor, n_clusters: int, uniforms, *, max_iter: int = 25):
+    """-> (centroids float64 [K, d], labels int32 [n], sweeps): k-means++ by D^2 sampling with the given K uniforms, then Lloyd."""
+    dev = require_gpu()
+    lib = _lib.load()
+    n, d = _f64c(z_norm).shape
+    u = (C.c_double * n_clusters)(*[float(v) for v in uniforms])
+    cen = _empty((n_clusters, d), dtype=torch.float64, device=dev)
+    lab = _empty(n, dtype=torch.int32, device=dev)
+    it = C.c_int(0)
+    ws, wsz = _ws(lib.scamd_harmony_kmeans_workspace_bytes(n, d, n_clusters), dev)
+    rc = lib.scamd_harmony_kmeans_f64(ptr(z_norm), n, d, n_clusters, u, int(max_iter), ptr(cen), ptr(lab), C.byref(it), ptr(ws), wsz, stream_ptr())
+    _check(rc, "scamd_harmony_kmeans_f64")
+    return cen, lab, int(it.value)
+
+
+def harmony_init(z_norm: torch.Tensor, codes: torch.Tensor, n_levels: int, centroids: torch.Tensor, pr_b: torch.Tensor, theta: torch.Tensor,
+                 sigma: float, stabilized: bool, *, n_covariates: int = 1):
+    """-> (R [n, K], E [levels, K], O [levels, K], objective [4] = total, k-means error, entropy, diversity), all float64."""
+    dev = require_gpu()
+    lib = _lib.load()
+    n, d = _f64c(z_norm).shape
+    k = _f64c(centroids).shape[0]
+    assert codes.dtype == torch.int32 and codes.numel() == n and _f64c(pr_b).numel() == n_levels and _f64c(theta).numel() == n_levels
+    r = _empty((n, k), dtype=torch.float64, device=dev)
+    e = _empty((n_levels, k), dtype=torch.float64, device=dev)
+    o = _empty((n_levels, k), dtype=torch.float64, device=dev)
+    obj = _empty(4, dtype=torch.float64, device=dev)
+    ws, wsz = _ws(lib.scamd_harmony_state_workspace_bytes(n, d, k, n_levels), dev)
+    rc = lib.scamd_harmony_init_f64(ptr(z_norm), ptr(codes), n, d, k, n_levels, n_covariates, ptr(centroids), ptr(pr_b), ptr(theta), float(sigma),
+                                    int(bool(stabilized)), ptr(r), ptr(e), ptr(o), ptr(obj), ptr(ws), wsz, stream_ptr())
+    _check(rc, "scamd_harmony_init_f64")
+    return r, e, o, obj
+
+
+def harmony_cluster_round_(z_norm: torch.Tensor, codes: torch.Tensor, n_levels: int, perm: torch.Tensor, n_blocks: int, pr_b: torch.Tensor,
+                           theta: torch.Tensor, sigma: float, stabilized: bool, r: torch.Tensor, e: torch.Tensor, o: torch.Tensor,
+                           y_norm: torch.Tensor, objective: torch.Tensor, *, n_covariates: int = 1) -> None:
+    """one clustering iteration, in place on r, e, o; y_norm [K, d] and objective [4] are written."""
+    dev = require_gpu()
+    lib = _lib.load()
+    n, d = _f64c(z_norm).shape
+    k = _f64c(r).shape[1]
+    assert codes.dtype == torch.int32 and perm.dtype == torch.int32 and perm.numel() == n and codes.numel() == n
+    assert tuple(_f64c(e).shape) == (n_levels, k) == tuple(_f64c(o).shape) and tuple(_f64c(y_norm).shape) == (k, d) and _f64c(objective).numel() == 4
+    ws, wsz = _ws(lib.scamd_harmony_state_workspace_bytes(n, d, k, n_levels), dev)
+    rc = lib.scamd_harmony_cluster_round_f64(ptr(z_norm), ptr(codes), n, d, k, n_levels, n_covariates, ptr(perm), int(n_blocks), ptr(pr_b), ptr(theta),
+                                             float(sigma), int(bool(stabilized)), ptr(r), ptr(e), ptr(o), ptr(y_norm), ptr(objective), ptr(ws), wsz,
+                                             stream_ptr())
+    _check(rc, "scamd_harmony_cluster_round_f64")
+
+
+def harmony_correct(x: torch.Tensor, codes: torch.Tensor, n_levels: int, r: torch.Tensor, o: torch.Tensor, e: torch.Tensor, n_b: torch.Tensor, *,
+                    dynamic_lambda: bool, alpha: float, batch_prune_threshold: float | None, ridge_lambda: float, want_lambda: bool = False,
+                    n_covariates: int = 1):
+    """-> (z_hat [n, d], z_norm [n, d], lambda_kb [levels, K] or None)."""
+    dev = require_gpu()
+    lib = _lib.load()
+    n, d = _f64c(x).shape
+    k = _f64c(r).shape[1]
+    assert codes.dtype == torch.int32 and codes.numel() == n and _f64c(n_b).numel() == n_levels
+    _f64c(o), _f64c(e)
+    z_hat = _empty((n, d), dtype=torch.float64, device=dev)
+    z_norm = _empty((n, d), dtype=torch.float64, device=dev)
+    lam = _empty((n_levels, k), dtype=torch.float64, device=dev) if want_lambda else None
+    ws, wsz = _ws(lib.scamd_harmony_correct_workspace_bytes(n, d, k, n_levels), dev)
+    rc = lib.scamd_harmony_correct_f64(ptr(x), ptr(codes), n, d, k, n_levels, n_covariates, ptr(r), ptr(o), ptr(e), ptr(n_b), int(bool(dynamic_lambda)),
+                                       float(alpha), -1.0 if batch_prune_threshold is None else float(batch_prune_threshold), float(ridge_lambda),
+                                       ptr(z_hat), ptr(z_norm), ptr(lam), ptr(ws), wsz, stream_ptr())
+    _check(rc, "scamd_harmony_correct_f64")
+    return z_hat, z_norm, lam

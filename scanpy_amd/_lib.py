@@ -88,6 +88,18 @@ SIGNATURES = {
     "scamd_rank_genes_chunk_entries": (_i32, [_i32]),
     "scamd_rank_genes_group_stats_f32": (_i32, [_vp, _vp, _vp, _i64, _i64, _vp, _i32, _i32, _f64, _vp, _vp, _vp, _vp, _sz, _vp]),
     "scamd_rank_genes_wilcoxon_f32": (_i32, [_vp, _vp, _vp, _i64, _i64, _vp, _i32, _vp, _i32, _vp, _vp, _vp, _sz, _vp]),
+    "scamd_harmony_permutation_workspace_bytes": (_sz, [_i64]),
+    "scamd_harmony_permutation_i32": (_i32, [_i64, _u64, _u64, _vp, _vp, _sz, _vp]),
+    "scamd_harmony_normalize_f64": (_i32, [_vp, _i64, _i32, _vp, _vp]),
+    "scamd_harmony_kmeans_workspace_bytes": (_sz, [_i64, _i32, _i32]),
+    "scamd_harmony_kmeans_f64": (_i32, [_vp, _i64, _i32, _i32, C.POINTER(_f64), _i32, _vp, _vp, C.POINTER(_i32), _vp, _sz, _vp]),
+    "scamd_harmony_state_workspace_bytes": (_sz, [_i64, _i32, _i32, _i32]),
+    "scamd_harmony_init_f64": (_i32, [_vp, _vp, _i64, _i32, _i32, _i32, _i32, _vp, _vp, _vp, _f64, _i32, _vp, _vp, _vp, _vp, _vp, _sz, _vp]),
+    "scamd_harmony_cluster_round_f64": (_i32, [_vp, _vp, _i64, _i32, _i32, _i32, _i32, _vp, _i64, _vp, _vp, _f64, _i32, _vp, _vp, _vp, _vp, _vp,
+                                               _vp, _sz, _vp]),
+    "scamd_harmony_correct_workspace_bytes": (_sz, [_i64, _i32, _i32, _i32]),
+    "scamd_harmony_correct_f64": (_i32, [_vp, _vp, _i64, _i32, _i32, _i32, _i32, _vp, _vp, _vp, _vp, _i32, _f64, _f64, _f64, _vp, _vp, _vp, _vp,
+                                         _sz, _vp]),
     "scamd_umap_workspace_bytes": (_sz, [_i64, _i64, _i32]),
     "scamd_umap_optimize_f32": (_i32, [_vp, _vp, _vp, _i64, _i64, _i32, _i32, _f64, _f64, _f64, _f64, _f64, _u64, _vp, _vp, _sz, _vp]),
     "scamd_lzf_decompress": (_i64, [_vp, _sz, _vp, _sz]),
