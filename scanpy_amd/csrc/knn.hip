@@ -26,13 +26,15 @@
 #include <type_traits>
 #include <vector>
 
-static thread_local float g_last_select_ms = -1.f;
-static thread_local double g_last_select_pairs = -1.0;
-static thread_local double g_last_select_prepass_pairs = -1.0;
-static thread_local int g_last_select_engine = -1;
-static thread_local int g_last_second_tier = 0;
-static thread_local int g_last_coarse = 0;  // 1: the last pruned sweep ran with the coarse first stage
-static thread_local int g_last_nprobe = 0;  // cells probed by the last search on this thread (0: it was answered exactly)
+// what the scamd_knn_last_* getters report: the last search on this thread; every field is written by the stage that knows it
+struct KnnLast {
+  float select_ms = -1.f;
+  double select_pairs = -1.0, select_prepass_pairs = -1.0;
+  int select_engine = -1, second_tier = 0;  // 1: bf16 x 3; queries the second tier re-ranked
+  int coarse = 0;                           // 1: the last pruned sweep ran with the coarse first stage
+  int nprobe = 0;                           // cells probed (0: the search was answered exactly)
+};
+static thread_local KnnLast g_last;
 
 namespace scamd {
 
@@ -87,12 +89,19 @@ typedef __attribute__((__vector_size__(8 * sizeof(__bf16)))) __bf16 bf16x8;
 constexpr int FALLBACK_CAP = 2048;    // collected rows per uncertified query
 constexpr int FALLBACK_CHUNK = 1024;  // uncertified queries processed per launch
 
+// slots of a search's counter block (KnnBuffers::counters; the second tier's `ctr2` has the first KC_HOST_SLOTS): queries the
+// certificate rejected; queries whose float64 scan overflowed its table (per round); swept and pre-pass pairs of the pruned sweep
+// (u64 each, IvfArgs::pairs); a query block without a launch slot; scans that did not lower their bound; 8 XCD queue positions
+constexpr int KC_UNCERTIFIED = 0, KC_RETRY = 1, KC_PAIRS = 2, KC_PREPASS_PAIRS = 4, KC_LAUNCH_ORDER_ERR = 6, KC_SCAN_STUCK = 7,
+              KC_XCD_QUEUE = 8;
+constexpr int KC_HOST_SLOTS = 8;  // what a search clears at its start and the host reads back
+
 // ------------------------------------------------------------------------------------------------
 // centring: the float32 pass works on x - mu (mu = column means, float32).  Euclidean distances do not change, the
 // scores ||c||^2 - 2 q.c do: far from the origin (||x||^2 >> d^2) they lose every digit that matters -- at an offset
 // of 300 per coordinate a float32 ulp of a score is 0.5 against squared neighbour distances of ~100, every query
 // failed its certificate and went through the float64 scan.  fl(x - mu) is exact to 2^-24 relative per coordinate;
-// that perturbation is part of the certificate's error bound (knn_rerank_kernel).  The exact passes (re-rank, fallback)
+// that perturbation is part of the certificate's error bound (certify).  The exact passes (re-rank, fallback)
 // read the caller's x.  Two stages, fixed summation order: the same mu for the same input, run to run.
 // ------------------------------------------------------------------------------------------------
 constexpr int MEAN_BLOCKS = 256;
@@ -437,7 +446,7 @@ struct RegCfg {
   static_assert(!B3 || H == 25, "the bf16 engine is built for d <= 50");
 };
 constexpr int B3_DPL = 68;
-// certificate factors (units of u = 2^-24), see knn_rerank_kernel.  bf16 engine: 198 accumulated terms instead of 52
+// certificate factors (units of u = 2^-24), see certify().  bf16 engine: 198 accumulated terms instead of 52
 // (+146 on both terms), and on the 2 q.c term the split's own error: bf16 carries 8 significant bits (unit roundoff 2^-8), so
 // |x - hi - lo| <= 2^-16 |x| and the three dropped pieces (ql.cl, q's residual, c's residual) sum to <= 3 * 2^-16 = 768 u.
 constexpr double CERT_K_F32 = 138.0, CERT_K_B3 = 284.0, CERT_K2_B3 = 768.0;
@@ -490,8 +499,29 @@ __device__ __forceinline__ unsigned int b3_row_dword(int c, int d, float nf, F v
   return w[0] | (w[1] << 16);
 }
 
-// packed image of x for the register-list kernel: [n_pad][DPL] float32 (layout above); rows >= n get
-// ||c||^2 = +inf so that they can never be selected.
+// element c (0..DPL-1) of the float32 image row [x0..xH-1, 1 | xH.., ||c||^2 | pad] of a point with centred coordinates vc(dim)
+// and squared norm nf (RegCfg: two halves of HP floats; the column after a half's H coordinates feeds the extra k-pair)
+template <typename F>
+__device__ __forceinline__ float f32_row_dword(int c, int H, int HP, int d, float nf, F vc) {
+  const int hh = c / HP, cc = c - hh * HP;
+  if (hh >= 2) return 0.f;  // trailing pad
+  if (cc < H) {
+    const int dim = hh * H + cc;
+    return dim < d ? vc(dim) : 0.f;
+  }
+  return cc == H ? (hh == 0 ? 1.0f : nf) : 0.f;
+}
+// image row r, written by the lanes first, first + step, ...: bf16 hi / lo pairs (b3; RegCfg: B3) or float32
+template <typename F>
+__device__ __forceinline__ void pack_image_row(float* __restrict__ xp, int64_t r, int first, int step, int b3, int H, int HP,
+                                               int DPL, int d, bool pad, float nf, F vc) {
+  unsigned int* xu = reinterpret_cast<unsigned int*>(xp);
+  if (b3) for (int c = first; c < B3_DPL; c += step) xu[r * B3_DPL + c] = b3_row_dword(c, d, pad ? B3_PAD_NORM : nf, vc);
+  else for (int c = first; c < DPL; c += step) xp[r * DPL + c] = f32_row_dword(c, H, HP, d, nf, vc);
+}
+
+// packed image of x for the register-list kernel: [n_pad][DPL] float32 or [n_pad][B3_DPL] bf16 pairs (the two functions
+// above); rows >= n get ||c||^2 = +inf so that they can never be selected.
 __global__ void knn_pack_image_kernel(const float* __restrict__ x, const float* __restrict__ mu, int64_t n, int d,
                                       int64_t ld, int H, int HP, int DPL, int64_t n_pad, float* __restrict__ xp,
                                       unsigned int* __restrict__ cmax_bits, int b3) {
@@ -508,24 +538,7 @@ __global__ void knn_pack_image_kernel(const float* __restrict__ x, const float* 
 #pragma unroll
     for (int o = 32; o > 0; o >>= 1) s += __shfl_xor(s, o);
     const float nf = (r < n) ? (float)s : INFINITY;
-    if (b3) {  // bf16 hi / lo image (RegCfg: B3)
-      const float nb = (r < n) ? nf : B3_PAD_NORM;
-      unsigned int* xu = reinterpret_cast<unsigned int*>(xp);
-      for (int c = lane; c < B3_DPL; c += 64)
-        xu[r * B3_DPL + c] = b3_row_dword(c, d, nb, [&](int dim) { return r < n ? __fsub_rn(x[r * ld + dim], mu[dim]) : 0.f; });
-      if (r < n) wmax = fmaxf(wmax, nf);
-      continue;
-    }
-    for (int c = lane; c < DPL; c += 64) {
-      const int hh = c / HP, cc = c - hh * HP;  // hh == 2: trailing pad
-      float v = 0.f;
-      if (hh < 2) {
-        const int dim = hh * H + cc;
-        if (cc < H) v = (r < n && dim < d) ? __fsub_rn(x[r * ld + dim], mu[dim]) : 0.f;
-        else if (cc == H) v = (hh == 0) ? 1.0f : nf;  // B operand of the extra k-pair: [1 | ||c||^2]
-      }
-      xp[r * DPL + c] = v;
-    }
+    pack_image_row(xp, r, lane, 64, b3, H, HP, DPL, d, r >= n, nf, [&](int dim) { return r < n ? __fsub_rn(x[r * ld + dim], mu[dim]) : 0.f; });
     if (r < n) wmax = fmaxf(wmax, nf);
   }
   if (lane == 0 && wmax > 0.f) atomicMax(cmax_bits, __float_as_uint(wmax));
@@ -1480,24 +1493,73 @@ __device__ inline bool key_less(double da, int ia, double db, int ib) {
   return da < db || (da == db && ia < ib);
 }
 
+// The rank-and-write step of both re-rank kernels.  sd / si: the `count` (exact d^2, row) entries of one query; (myd, myi): the
+// caller's own entry, `slot` its place in the table.  Counts the keys below mine -- missing entries (idx -1, +inf) order after
+// everything, ties among them by slot --, writes columns 1 .. kk of the query's output rows and keeps the kk-th distance.
+__device__ __forceinline__ void rank_and_write(const double* sd, const int* si, int count, double myd, int myi, int slot, int kk,
+                                               int32_t* __restrict__ idx_row, double* __restrict__ dist_row, double* skth) {
+  int rank = 0;
+  for (int v = 0; v < count; ++v) {
+    const double dv = sd[v];
+    const int iv = si[v];
+    const bool less = (iv >= 0) ? (myi < 0 || key_less(dv, iv, myd, myi)) : (myi < 0 && v < slot);
+    rank += less ? 1 : 0;
+  }
+  if (rank < kk) {
+    idx_row[1 + rank] = myi;
+    dist_row[1 + rank] = (myi >= 0) ? sqrt(myd) : INFINITY;
+    if (rank == kk - 1) *skth = myd;
+  }
+}
+
+// The certificate of both re-rank kernels: no row the sweep left out is nearer than the k-th exact distance dk.  qn =
+// ||fl(q - mu)||^2, tau = the query's final threshold, cert_k / cert_k2 = the factors of the engine that swept (CERT_K_*).
+// |s_float32 - s_exact| <= (2H+2) u (||c||^2 + 2 ||q|| ||c||), u = 2^-24; 2H+2 <= 130.
+// Centring: the image holds fl(x - mu), each coordinate off by <= u |x - mu|, so a squared distance between image
+// rows differs from the true one by <= 4 u (qn + cmax) <= 8 u (cmax + 2 ||q|| ||c||) -> 138.
+// Slot keys (register-list kernel): the threshold and the keys it was compared with carry a slot number in their
+// 5 low mantissa bits, i.e. each is off by < 32 ulp OF ITS OWN MAGNITUDE -- the threshold's, not cmax's (keys far
+// above the threshold cannot be confused with it): 128 u |tau| with a factor 2 for a binade boundary.  (Charging it
+// against cmax as well, factor 202, sent 4317 instead of 379 queries of the 10M x 50 run to the float64 scan: +3 s.)
+// 3 x bf16 engine: cert_k = 138 + 146 (198 accumulated terms instead of 2H + 2 = 52) and cert_k2 = 768 on the 2 q.c
+// term alone (the hi + lo split's dropped pieces, 3 * 2^-16: the norm and the threshold are split EXACTLY).
+// Which candidates does the bound have to hold for?  Only for rows that could be a missed neighbour, i.e. rows within
+// sqrt(dk) of the query: their norm is at most ||q|| + sqrt(dk) (triangle inequality; 1e-3 relative slack for the
+// centring perturbation of the image rows).  The global maximum norm is only the cap: one far outlier row no longer
+// inflates the bound of every query (round 4; before, a single row with a huge coordinate sent ALL queries to the
+// float64 scan).
+__device__ __forceinline__ bool certify(double qn, double dk, double tau, const unsigned int* __restrict__ cmax_bits,
+                                        double cert_scale, double cert_k, double cert_k2) {
+  double cmax = (double)__uint_as_float(*cmax_bits);
+  const double rq = sqrt(qn) + sqrt(dk);
+  const double cq = rq * rq * (1.0 + 1e-3);
+  if (cq < cmax) cmax = cq;
+  const double eps = cert_scale * 5.9604644775390625e-08 *
+                     (cert_k * (cmax + 2.0 * sqrt(qn * cmax)) + cert_k2 * 2.0 * sqrt(qn * cmax) + 128.0 * fabs(tau));
+  return (tau >= 1e38f) || ((dk - qn) + eps < tau);
+}
+// what follows the verdict: the k-th distance is the float64 scan's first bound, a rejected query joins the flag list
+__device__ __forceinline__ void record_verdict(bool certified, int64_t qi, double dk, double* __restrict__ kth_d2,
+                                               int* __restrict__ flag_list, int* __restrict__ n_flag) {
+  kth_d2[qi] = dk;
+  if (!certified) flag_list[atomicAdd(n_flag, 1)] = (int)qi;
+}
+
 template <int KP>
 __global__ __launch_bounds__(256) void knn_rerank_kernel(
     const float* __restrict__ x, const float* __restrict__ mu, int64_t n, int d, int64_t ld, int64_t q_begin,
     int64_t n_query, int k, const int* __restrict__ cand_idx, const float* __restrict__ cand_tau,
     const unsigned int* __restrict__ cmax_bits, double cert_scale, double cert_k, double cert_k2,
     int32_t* __restrict__ out_idx,
-    double* __restrict__ out_dist, double* __restrict__ kth_d2, int* __restrict__ flag_list,
-    int* __restrict__ n_flag, const int* __restrict__ qlist, int n_list) {
+    double* __restrict__ out_dist, double* __restrict__ kth_d2, int* __restrict__ flag_list, int* __restrict__ n_flag) {
   constexpr int PER = (KP + 63) / 64;
   __shared__ float qs[4][KNN_MAX_D];
   __shared__ double sd[4][KP];
   __shared__ int si[4][KP];
   __shared__ double skth[4];
   const int lane = threadIdx.x & 63, w = threadIdx.x >> 6;
-  // (qlist: only these queries -- the second tier of the bf16 engine re-ranks what its first certificate rejected)
-  const int64_t qj = (int64_t)blockIdx.x * 4 + w;
-  if (qj >= (qlist ? (int64_t)n_list : n_query)) return;  // whole wave exits together (no block-level sync below)
-  const int64_t qi = qlist ? (int64_t)qlist[qj] : qj;
+  const int64_t qi = (int64_t)blockIdx.x * 4 + w;
+  if (qi >= n_query) return;  // whole wave exits together (no block-level sync below)
   const int64_t q = q_begin + qi;
   for (int c = lane; c < d; c += 64) qs[w][c] = x[q * ld + c];
   if (lane == 0) skth[w] = INFINITY;
@@ -1572,56 +1634,14 @@ __global__ __launch_bounds__(256) void knn_rerank_kernel(
 #pragma unroll
   for (int p = 0; p < PER; ++p) {
     int u = lane + p * 64;
-    if (u < KP) {
-      int rank = 0;
-      for (int v = 0; v < KP; ++v) {
-        double dv = sd[w][v];
-        int iv = si[w][v];
-        // missing entries (idx -1, +inf) order after everything, ties among them by slot
-        bool less = (iv >= 0) ? (myi[p] < 0 || key_less(dv, iv, myd[p], myi[p]))
-                              : (myi[p] < 0 && v < u);
-        rank += less ? 1 : 0;
-      }
-      if (rank < kk) {
-        out_idx[qi * k + 1 + rank] = myi[p];
-        out_dist[qi * k + 1 + rank] = (myi[p] >= 0) ? sqrt(myd[p]) : INFINITY;
-        if (rank == kk - 1) skth[w] = myd[p];
-      }
-    }
+    if (u < KP) rank_and_write(sd[w], si[w], KP, myd[p], myi[p], u, kk, out_idx + qi * k, out_dist + qi * k, &skth[w]);
   }
   __builtin_amdgcn_wave_barrier();
   __builtin_amdgcn_s_waitcnt(0);
   if (lane == 0) {
-    double dk = (kk > 0) ? skth[w] : 0.0;
-    double tau = (double)cand_tau[qi];
-    double cmax = (double)__uint_as_float(*cmax_bits);
-    // |s_float32 - s_exact| <= (2H+2) u (||c||^2 + 2 ||q|| ||c||), u = 2^-24; 2H+2 <= 130.
-    // Centring: the image holds fl(x - mu), each coordinate off by <= u |x - mu|, so a squared distance between image
-    // rows differs from the true one by <= 4 u (qn + cmax) <= 8 u (cmax + 2 ||q|| ||c||) -> 138.
-    // Slot keys (register-list kernel): the threshold and the keys it was compared with carry a slot number in their
-    // 5 low mantissa bits, i.e. each is off by < 32 ulp OF ITS OWN MAGNITUDE -- the threshold's, not cmax's (keys far
-    // above the threshold cannot be confused with it): 128 u |tau| with a factor 2 for a binade boundary.  (Charging it
-    // against cmax as well, factor 202, sent 4317 instead of 379 queries of the 10M x 50 run to the float64 scan: +3 s.)
-    // 3 x bf16 engine: cert_k = 138 + 146 (198 accumulated terms instead of 2H + 2 = 52) and cert_k2 = 768 on the 2 q.c
-    // term alone (the hi + lo split's dropped pieces, 3 * 2^-16: the norm and the threshold are split EXACTLY).
-    // Which candidates does the bound have to hold for?  Only for rows that could be a missed neighbour, i.e. rows within
-    // sqrt(dk) of the query: their norm is at most ||q|| + sqrt(dk) (triangle inequality; 1e-3 relative slack for the
-    // centring perturbation of the image rows).  The global maximum norm is only the cap: one far outlier row no longer
-    // inflates the bound of every query (round 4; before, a single row with a huge coordinate sent ALL queries to the
-    // float64 scan).
-    {
-      const double rq = sqrt(qn) + sqrt(dk);
-      const double cq = rq * rq * (1.0 + 1e-3);
-      if (cq < cmax) cmax = cq;
-    }
-    double eps = cert_scale * 5.9604644775390625e-08 *
-                 (cert_k * (cmax + 2.0 * sqrt(qn * cmax)) + cert_k2 * 2.0 * sqrt(qn * cmax) + 128.0 * fabs(tau));
-    bool certified = (tau >= 1e38f) || ((dk - qn) + eps < tau);
-    kth_d2[qi] = dk;
-    if (!certified) {
-      int slot = atomicAdd(n_flag, 1);
-      flag_list[slot] = (int)qi;
-    }
+    const double dk = (kk > 0) ? skth[w] : 0.0;
+    const bool certified = certify(qn, dk, (double)cand_tau[qi], cmax_bits, cert_scale, cert_k, cert_k2);
+    record_verdict(certified, qi, dk, kth_d2, flag_list, n_flag);
   }
 }
 
@@ -1637,7 +1657,11 @@ __global__ __launch_bounds__(256) void knn_rerank_kernel(
 // a certified query has its k - 1 neighbours there; an uncertified one is redone by the float64 scan whatever this
 // kernel reports), and the queries come in the select kernel's slot order (qlist = IvfArgs::qorder: queries of one
 // cell after another, whose candidate rows are the same few thousand rows of x).
-// LDS per wave: [2 n_rank + 2][RS] floats (RS = d | 1), then n_rank-entry (double, int) tables per half.
+// LDS per wave: [2 n_rank + 2][RS] floats (RS = d | 1: rows, query rows), (pad,) then n_rank-entry (double, int) tables and a
+// double (skth) per half; a multiple of 4 floats.
+__host__ __device__ constexpr int rerank_rows_wave_floats(int d, int n_rank) {
+  return ((2 * n_rank + 2) * (d | 1) + 2 + 2 * n_rank * 3 + 4 + 3) & ~3;
+}
 __global__ __launch_bounds__(256) void knn_rerank_rows_kernel(
     const float* __restrict__ x, const float* __restrict__ mu, int64_t n, int d, int64_t ld, int64_t q_begin,
     int64_t n_query, int k, int n_rank, const int* __restrict__ cand_idx, const float* __restrict__ cand_tau,
@@ -1648,8 +1672,7 @@ __global__ __launch_bounds__(256) void knn_rerank_rows_kernel(
   const int lane = threadIdx.x & 63, half = lane >> 5, l31 = lane & 31;
   const int w = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
   const int RS = d | 1;
-  const int wave_floats = (2 * n_rank + 2) * RS + 2 + 2 * n_rank * 3 + 4;  // rows, query rows, (pad,) sd (double) + si, skth (double)
-  float* rows = rsm + (size_t)w * ((wave_floats + 3) & ~3);
+  float* rows = rsm + (size_t)w * rerank_rows_wave_floats(d, n_rank);
   float* qrows = rows + 2 * n_rank * RS;
   double* sd = reinterpret_cast<double*>(rows + (((2 * n_rank + 2) * RS + 1) & ~1));  // [2][n_rank]
   double* skth = sd + 2 * n_rank;                                                    // [2]
@@ -1724,48 +1747,18 @@ __global__ __launch_bounds__(256) void knn_rerank_rows_kernel(
     out_idx[(int64_t)qi * k] = (int32_t)q;
     out_dist[(int64_t)qi * k] = 0.0;
   }
-  if (qv && l31 < n_rank) {
-    int rank = 0;
-    for (int v = 0; v < n_rank; ++v) {
-      const double dv = sd[half * n_rank + v];
-      const int iv = si[half * n_rank + v];
-      // missing entries (idx -1, +inf) order after everything, ties among them by position
-      const bool less = (iv >= 0) ? (myi < 0 || key_less(dv, iv, myd, myi)) : (myi < 0 && v < l31);
-      rank += less ? 1 : 0;
-    }
-    if (rank < kk) {
-      out_idx[(int64_t)qi * k + 1 + rank] = myi;
-      out_dist[(int64_t)qi * k + 1 + rank] = (myi >= 0) ? sqrt(myd) : INFINITY;
-      if (rank == kk - 1) skth[half] = myd;
-    }
-  }
+  if (qv && l31 < n_rank)
+    rank_and_write(sd + half * n_rank, si + half * n_rank, n_rank, myd, myi, l31, kk, out_idx + (int64_t)qi * k,
+                   out_dist + (int64_t)qi * k, &skth[half]);
   __builtin_amdgcn_s_waitcnt(0);
   __builtin_amdgcn_wave_barrier();
   if (qv && l31 == 0) {
-    // the certificate: see knn_rerank_kernel (same expressions)
     const double dk = (kk > 0) ? skth[half] : 0.0;
-    const double tau = (double)cand_tau[qi];
-    double cmax = (double)__uint_as_float(*cmax_bits);
-    {
-      const double rq = sqrt(qn) + sqrt(dk);
-      const double cq = rq * rq * (1.0 + 1e-3);
-      if (cq < cmax) cmax = cq;
-    }
-    const double eps = cert_scale * 5.9604644775390625e-08 *
-                       (cert_k * (cmax + 2.0 * sqrt(qn * cmax)) + cert_k2 * 2.0 * sqrt(qn * cmax) + 128.0 * fabs(tau));
-    const bool certified = (tau >= 1e38f) || ((dk - qn) + eps < tau);
-    kth_d2[qi] = dk;
-    if (!certified) {
-      const int slot = atomicAdd(n_flag, 1);
-      flag_list[slot] = qi;
-    }
+    const bool certified = certify(qn, dk, (double)cand_tau[qi], cmax_bits, cert_scale, cert_k, cert_k2);
+    record_verdict(certified, qi, dk, kth_d2, flag_list, n_flag);
   }
 }
-static size_t rerank_rows_lds_bytes(int d, int n_rank) {
-  const int RS = d | 1;
-  const int wave_floats = (2 * n_rank + 2) * RS + 2 + 2 * n_rank * 3 + 4;
-  return (size_t)4 * ((wave_floats + 3) & ~3) * sizeof(float);
-}
+static size_t rerank_rows_lds_bytes(int d, int n_rank) { return (size_t)4 * rerank_rows_wave_floats(d, n_rank) * sizeof(float); }
 
 // ------------------------------------------------------------------------------------------------
 // pass 3: float64 scan for uncertified queries, two kernels.
@@ -1778,37 +1771,68 @@ static size_t rerank_rows_lds_bytes(int d, int n_rank) {
 // ------------------------------------------------------------------------------------------------
 constexpr int FALLBACK_ROW_CHUNKS = 128;
 
-__global__ __launch_bounds__(256) void knn_fallback_scan_kernel(
-    const float* __restrict__ x, int64_t n, int d, int64_t ld, int64_t q_begin,
-    const int* __restrict__ flag_list, int flag_begin, const double* __restrict__ kth_d2, const int* __restrict__ kth_idx,
-    double* __restrict__ scratch_d, int* __restrict__ scratch_i, int* __restrict__ counts) {
-  __shared__ float qs[KNN_MAX_D];
+// what both scan kernels take: the rows, the queries flag_list[flag_begin + blockIdx.y] with their bound keys (kth_d2, kth_idx), and
+// per query of the launch a table of FALLBACK_CAP (d^2, row) entries and a counter; ScanQuery: all that for the block's own query
+struct ScanArgs {
+  const float* x; int d; int64_t ld, q_begin; const int* flag_list; int flag_begin; const double* kth_d2; const int* kth_idx;
+  double* scratch_d; int* scratch_i; int* counts;
+};
+struct ScanQuery {
+  int64_t q;
+  double bound;
+  unsigned int ibound;  // (-1 = no index bound)
+  double* bd; int* bi; int* count;
+  // accept a key (s, row) at or below the bound key and append it; beyond the table rows are counted only (-> knn_fallback_rank_kernel)
+  __device__ __forceinline__ void collect(double s, int row) const {
+    if (s < bound || (s == bound && (unsigned int)row <= ibound)) {
+      const int slot = atomicAdd(count, 1);
+      if (slot < FALLBACK_CAP) {
+        bd[slot] = s;
+        bi[slot] = row;
+      }
+    }
+  }
+};
+// prologue of both scan kernels: the query's row into LDS (qs, visible to the block on return), bound key and table pointers
+__device__ __forceinline__ ScanQuery scan_query(float* qs, const ScanArgs& a) {
   const int fb = blockIdx.y;
-  const int64_t qi = flag_list[flag_begin + fb];
-  const int64_t q = q_begin + qi;
-  double* bd = scratch_d + (int64_t)fb * FALLBACK_CAP;
-  int* bi = scratch_i + (int64_t)fb * FALLBACK_CAP;
-  for (int c = threadIdx.x; c < d; c += blockDim.x) qs[c] = x[q * ld + c];
+  const int64_t qi = a.flag_list[a.flag_begin + fb];
+  const int64_t q = a.q_begin + qi;
+  for (int c = threadIdx.x; c < a.d; c += blockDim.x) qs[c] = a.x[q * a.ld + c];
   __syncthreads();
-  const double bound = kth_d2[qi];
-  const unsigned int ibound = (unsigned int)kth_idx[qi];  // (-1 = no index bound)
+  return {q, a.kth_d2[qi], (unsigned int)a.kth_idx[qi], a.scratch_d + (int64_t)fb * FALLBACK_CAP,
+          a.scratch_i + (int64_t)fb * FALLBACK_CAP, &a.counts[fb]};
+}
+// exact (q - c)^2 of one row: ten coordinates requested at a time, summed in the same order as one by one (one load in flight
+// per thread made a cell of 2048 rows 400 serial round trips per thread: 0.9 ms for the 58 queries of the 1M bench)
+__device__ __forceinline__ double row_dist2_f64(const float* qs, const float* __restrict__ cp, int d) {
+  double s = 0.0;
+  int t = 0;
+  for (; t + 10 <= d; t += 10) {
+    float v[10];
+#pragma unroll
+    for (int u = 0; u < 10; ++u) v[u] = cp[t + u];
+#pragma unroll
+    for (int u = 0; u < 10; ++u) {
+      const double df = (double)qs[t + u] - (double)v[u];
+      s = fma(df, df, s);
+    }
+  }
+  for (; t < d; ++t) {
+    const double df = (double)qs[t] - (double)cp[t];
+    s = fma(df, df, s);
+  }
+  return s;
+}
+
+__global__ __launch_bounds__(256) void knn_fallback_scan_kernel(const ScanArgs a, int64_t n) {
+  __shared__ float qs[KNN_MAX_D];
+  const ScanQuery sq = scan_query(qs, a);
   const int64_t rows_per_chunk = (n + gridDim.x - 1) / gridDim.x;
   const int64_t r0 = (int64_t)blockIdx.x * rows_per_chunk, r1 = std::min<int64_t>(n, r0 + rows_per_chunk);
   for (int64_t r = r0 + threadIdx.x; r < r1; r += blockDim.x) {
-    if (r == q) continue;
-    const float* cp = x + r * ld;
-    double s = 0.0;
-    for (int c = 0; c < d; ++c) {
-      double df = (double)qs[c] - (double)cp[c];
-      s = fma(df, df, s);
-    }
-    if (s < bound || (s == bound && (unsigned int)r <= ibound)) {
-      int slot = atomicAdd(&counts[fb], 1);
-      if (slot < FALLBACK_CAP) {
-        bd[slot] = s;
-        bi[slot] = (int)r;
-      }
-    }
+    if (r == sq.q) continue;
+    sq.collect(row_dist2_f64(qs, a.x + r * a.ld, a.d), (int)r);
   }
 }
 
@@ -1817,21 +1841,11 @@ __global__ __launch_bounds__(256) void knn_fallback_scan_kernel(
 // scan over ALL rows cost 0.7 ms per query at 10M rows (1.1 s for the 1499 uncertified queries of the 10M x 50 run);
 // with ~2.5 % of the rows in reach it is noise again.  grid (cell chunks, queries).
 __global__ __launch_bounds__(256) void knn_fallback_scan_cells_kernel(
-    const float* __restrict__ x, int d, int64_t ld, int64_t q_begin, const int* __restrict__ flag_list, int flag_begin,
-    const double* __restrict__ kth_d2, const int* __restrict__ kth_idx, double* __restrict__ scratch_d,
-    int* __restrict__ scratch_i, int* __restrict__ counts, const float* __restrict__ cent,
-    const float* __restrict__ radius, const int* __restrict__ cell_tile0,
+    const ScanArgs a, const float* __restrict__ cent, const float* __restrict__ radius, const int* __restrict__ cell_tile0,
     const int* __restrict__ cell_ntiles, const int* __restrict__ perm, int n_cells) {
   __shared__ float qs[KNN_MAX_D];
-  const int fb = blockIdx.y;
-  const int64_t qi = flag_list[flag_begin + fb];
-  const int64_t q = q_begin + qi;
-  double* bd = scratch_d + (int64_t)fb * FALLBACK_CAP;
-  int* bi = scratch_i + (int64_t)fb * FALLBACK_CAP;
-  for (int c = threadIdx.x; c < d; c += blockDim.x) qs[c] = x[q * ld + c];
-  __syncthreads();
-  const double bound = kth_d2[qi];
-  const unsigned int ibound = (unsigned int)kth_idx[qi];  // (-1 = no index bound)
+  const ScanQuery sq = scan_query(qs, a);
+  const int d = a.d;
   const int per = (n_cells + gridDim.x - 1) / gridDim.x;
   const int c0 = blockIdx.x * per, c1 = min(n_cells, c0 + per);
   for (int c = c0; c < c1; ++c) {
@@ -1843,37 +1857,12 @@ __global__ __launch_bounds__(256) void knn_fallback_scan_cells_kernel(
       dc2 = fma(df, df, dc2);
     }
     const double lb = sqrt(dc2) * (1.0 - 1e-6) - (double)radius[c];  // (the radius is stored inflated by 1e-4)
-    if (lb > 0.0 && lb * lb > bound * (1.0 + 1e-9)) continue;
+    if (lb > 0.0 && lb * lb > sq.bound * (1.0 + 1e-9)) continue;
     const int64_t r0 = (int64_t)cell_tile0[c] * 64, r1 = r0 + (int64_t)nt * 64;
     for (int64_t row = r0 + threadIdx.x; row < r1; row += blockDim.x) {
       const int orig = perm[row];
-      if (orig < 0 || orig == q) continue;
-      const float* cp = x + (int64_t)orig * ld;
-      double s = 0.0;
-      // ten coordinates requested at a time, summed in the same order as one by one (one load in flight per thread made a
-      // cell of 2048 rows 400 serial round trips per thread: 0.9 ms for the 58 queries of the 1M bench)
-      int t = 0;
-      for (; t + 10 <= d; t += 10) {
-        float v[10];
-#pragma unroll
-        for (int u = 0; u < 10; ++u) v[u] = cp[t + u];
-#pragma unroll
-        for (int u = 0; u < 10; ++u) {
-          const double df = (double)qs[t + u] - (double)v[u];
-          s = fma(df, df, s);
-        }
-      }
-      for (; t < d; ++t) {
-        const double df = (double)qs[t] - (double)cp[t];
-        s = fma(df, df, s);
-      }
-      if (s < bound || (s == bound && (unsigned int)orig <= ibound)) {
-        const int slot = atomicAdd(&counts[fb], 1);
-        if (slot < FALLBACK_CAP) {
-          bd[slot] = s;
-          bi[slot] = orig;
-        }
-      }
+      if (orig < 0 || orig == sq.q) continue;
+      sq.collect(row_dist2_f64(qs, a.x + (int64_t)orig * a.ld, d), orig);
     }
   }
 }
@@ -2233,7 +2222,7 @@ __global__ void knn_iota_kernel(int* __restrict__ a, int n) {
   if (i < n) a[i] = i;
 }
 
-// image of the cell-sorted rows (layout of knn_pack_image_kernel); padding rows get ||c||^2 = +inf.  Also the
+// image of the cell-sorted rows (b3_row_dword / f32_row_dword, as knn_pack_image_kernel); padding rows get ||c||^2 = +inf.  Also the
 // cell radii: max distance of a member to its cell's centre (float32, as uint bits for atomicMax).
 // 16 lanes per row, four rows per wave: the chain perm -> labels -> cell_map -> x row is four dependent gathers, and a
 // wave that walks its rows one at a time has one of them in flight (1.43 ms at 1M x 50 for 0.4 GB of traffic).
@@ -2281,23 +2270,8 @@ __global__ void ivf_pack_image_kernel(const float* __restrict__ x, const float* 
       dc2 += __shfl_xor(dc2, o);
     }
     const float nf = (src >= 0) ? (float)s : INFINITY;
-    if (b3) {  // bf16 hi / lo image (RegCfg: B3)
-      const float nb = (src >= 0) ? nf : B3_PAD_NORM;
-      unsigned int* xu = reinterpret_cast<unsigned int*>(xp);
-      for (int c = sub; c < B3_DPL; c += 16)
-        xu[r * B3_DPL + c] =
-            b3_row_dword(c, d, nb, [&](int dim) { return src >= 0 ? __fsub_rn(x[(int64_t)src * ld + dim], mu[dim]) : 0.f; });
-    } else
-    for (int c = sub; c < DPL; c += 16) {
-      const int hh = c / HP, cc = c - hh * HP;
-      float v = 0.f;
-      if (hh < 2) {
-        const int dim = hh * H + cc;
-        if (cc < H) v = (src >= 0 && dim < d) ? __fsub_rn(x[(int64_t)src * ld + dim], mu[dim]) : 0.f;
-        else if (cc == H) v = (hh == 0) ? 1.0f : nf;
-      }
-      xp[r * DPL + c] = v;
-    }
+    pack_image_row(xp, r, sub, 16, b3, H, HP, DPL, d, src < 0, nf,
+                   [&](int dim) { return src >= 0 ? __fsub_rn(x[(int64_t)src * ld + dim], mu[dim]) : 0.f; });
     if (src >= 0) {
       wmax = fmaxf(wmax, nf);
       const unsigned int rb = __float_as_uint(sqrtf(dc2) * 1.0001f + 1e-6f);
@@ -2436,7 +2410,7 @@ static void knn_carve(Workspace& ws, const KnnPlan& p, int64_t n_query, KnnBuffe
   b->cand_tau = ws.take<float>((size_t)p.nq_pad);
   b->kth_d2 = ws.take<double>((size_t)n_query);
   b->flag_list = ws.take<int>((size_t)n_query);
-  b->counters = ws.take<int>(16);  // [0] uncertified, [1] overflow, [2..3] swept pairs, [4..5] pre-pass pairs (u64), [6] launch-order error, [7] float64 scans without progress, [8..15] XCD queue positions
+  b->counters = ws.take<int>(16);  // slots: KC_*
   b->scratch_d = ws.take<double>((size_t)FALLBACK_CHUNK * FALLBACK_CAP);
   b->scratch_i = ws.take<int>((size_t)FALLBACK_CHUNK * FALLBACK_CAP);
   b->fb_counts = ws.take<int>((size_t)FALLBACK_CHUNK);
@@ -2563,8 +2537,9 @@ static int dispatch_select(const KnnPlan& p, const KnnBuffers& b, int64_t q_begi
 }
 
 // ---- cell-pruned search: quantiser, cell-sorted image, launch -------------------------------------------
-// the rows, the query range and the stream of one call
-struct KnnCall { const float* x; int64_t n; int d; int64_t ld, q_begin, n_query; hipStream_t s; };
+// the rows, the query range and the stream of one call; what it asks for and where the lists go
+struct KnnCall { const float* x; int64_t n; int d; int64_t ld, q_begin, n_query; hipStream_t s;
+                 int k; double cert_scale; int32_t* out_idx; double* out_dist; };
 // owners: the events around the select launch and the trace buffer of the pruned sweep are released on every way out
 struct HipRelease {
   void operator()(hipEvent_t e) const { (void)hipEventDestroy(e); }
@@ -2769,7 +2744,7 @@ struct IvfSelect {
     SCAMD_HIP_CHECK(hipMemsetAsync(b.perm, 0xff, sizeof(int) * L.rows, s));
     SCAMD_HIP_CHECK(hipMemsetAsync(b.qpos, 0xff, sizeof(int) * L.slots, s));
     SCAMD_HIP_CHECK(hipMemsetAsync(b.radius_bits, 0, sizeof(unsigned int) * nc, s));
-    SCAMD_HIP_CHECK(hipMemsetAsync(b.counters + 2, 0, 16, s));
+    SCAMD_HIP_CHECK(hipMemsetAsync(b.counters + KC_PAIRS, 0, sizeof(int) * (KC_LAUNCH_ORDER_ERR - KC_PAIRS), s));
     SCAMD_HIP_CHECK(hipStreamSynchronize(s));  // the host vectors of L must outlive their copies
     return SCAMD_OK;
   }
@@ -2794,7 +2769,7 @@ struct IvfSelect {
     SCAMD_LAUNCH_CHECK();
     // launch order: longest expected sweeps first
     hipLaunchKernelGGL(ivf_block_order_kernel, dim3(1), dim3(1024), 0, s, t.work, t.first_block, t.n_blocks, nc, b.block_perm, L.n_launch,
-                       L.xcd_mode, b.counters + 6);
+                       L.xcd_mode, b.counters + KC_LAUNCH_ORDER_ERR);
     SCAMD_LAUNCH_CHECK();
     return SCAMD_OK;
   }
@@ -2826,7 +2801,7 @@ struct IvfSelect {
     const size_t lds = sweep_lds + 64 + IVF_META_BYTES;
     SCAMD_HIP_CHECK(hipFuncSetAttribute(reinterpret_cast<const void*>(kern), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
     IvfArgs iv = ivf_args(b, t, nc, c.d);
-    iv.pairs = reinterpret_cast<unsigned long long*>(b.counters + 2);
+    iv.pairs = reinterpret_cast<unsigned long long*>(b.counters + KC_PAIRS);
     iv.qorder = b.qorder;
     // float32 engine, measured at 1M: 48 -> 29.3 ms, 24 / 12 -> 29.0, 6 -> 29.6, 2 -> 30.2; bf16 engine (the pre-pass
     // costs a quarter): 8 -> 17.1, 16 -> 16.8, 32 -> 16.15, 64 -> 16.1
@@ -2846,8 +2821,8 @@ struct IvfSelect {
     const int want = env_int("SCAMD_KNN_PERSISTENT", 768);
     if (want > 0 && L.n_launch > want) {
       n_groups = (want + 7) / 8 * 8;
-      iv.queue_ctr = b.counters + 8;
-      SCAMD_HIP_CHECK(hipMemsetAsync(b.counters + 8, 0, sizeof(int) * 8, s));
+      iv.queue_ctr = b.counters + KC_XCD_QUEUE;
+      SCAMD_HIP_CHECK(hipMemsetAsync(b.counters + KC_XCD_QUEUE, 0, sizeof(int) * 8, s));
     }
     SCAMD_HIP_CHECK(hipEventRecord(ev0, s));
     hipLaunchKernelGGL(kern, dim3(n_groups), dim3(RegCfg<8>::NT), lds, s, b.xp, (int)(L.rows / 64), L.rows, c.q_begin, p.thr_rank,
@@ -2881,7 +2856,7 @@ struct IvfSelect {
     if (int rc = build_image_and_orders(L)) return rc;
     bool coarse = false;
     if (int rc = choose_coarse(L, &coarse)) return rc;
-    g_last_coarse = coarse ? 1 : 0;
+    g_last.coarse = coarse ? 1 : 0;
     return launch_sweep(L, coarse, ev0, ev1);
   }
 };
@@ -2911,6 +2886,34 @@ static int dispatch_ivf(const KnnPlan& p, const KnnBuffers& b, const KnnCall& c,
   }
 }
 
+// ---- pass 2 launchers: one per re-rank kernel, for the first search and the second tier alike -------------------
+// register-list kernels (lists of 32, d <= 64): the entries below the threshold entry thr_rank, row-wise.  qlist / n_list: these
+// queries in this order (null: all n_query).  Rejected queries go to flag_list, their number to *n_flag.
+static int launch_rerank_rows(const KnnBuffers& b, const KnnCall& c, int thr_rank, double cert_k, double cert_k2, int* flag_list,
+                              int* n_flag, const int* qlist, int64_t n_list) {
+  const int n_rank = std::max(1, thr_rank - 1);
+  const size_t lds = rerank_rows_lds_bytes(c.d, n_rank);
+  SCAMD_HIP_CHECK(hipFuncSetAttribute(reinterpret_cast<const void*>(knn_rerank_rows_kernel),
+                                      hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
+  hipLaunchKernelGGL(knn_rerank_rows_kernel, dim3((unsigned)ceil_div(n_list, 8)), dim3(256), lds, c.s, c.x, b.mu, c.n, c.d, c.ld,
+                     c.q_begin, c.n_query, c.k, n_rank, b.cand_idx, b.cand_tau, b.cmax, c.cert_scale, cert_k, cert_k2, c.out_idx,
+                     c.out_dist, b.kth_d2, flag_list, n_flag, qlist, n_list);
+  SCAMD_LAUNCH_CHECK();
+  return SCAMD_OK;
+}
+// LDS-list kernels: all KP entries of every query, a lane per entry
+static int launch_rerank_lds(const KnnPlan& p, const KnnBuffers& b, const KnnCall& c, double cert_k, double cert_k2) {
+  auto rerank = knn_rerank_kernel<32>;
+  if (p.KP == 64) rerank = knn_rerank_kernel<64>;
+  else if (p.KP == 128) rerank = knn_rerank_kernel<128>;
+  else if (p.KP != 32) rerank = knn_rerank_kernel<288>;
+  hipLaunchKernelGGL(rerank, dim3((unsigned)((c.n_query + 3) / 4)), dim3(256), 0, c.s, c.x, b.mu, c.n, c.d, c.ld, c.q_begin,
+                     c.n_query, c.k, b.cand_idx, b.cand_tau, b.cmax, c.cert_scale, cert_k, cert_k2, c.out_idx, c.out_dist, b.kth_d2,
+                     b.flag_list, b.counters + KC_UNCERTIFIED);
+  SCAMD_LAUNCH_CHECK();
+  return SCAMD_OK;
+}
+
 // Second tier of the bf16 engine (pruned mode).  Its certificate is ~4x looser than the float32 engine's relative to
 // ||q|| ||c||; how many queries it rejects depends on the data (508 of 1M planted cells at a margin of 6 ranks, 76543 of
 // 10M x 4k at a margin of 10: 7 s of float64 cell scans).  The rejected queries alone -- grouped by cell into query
@@ -2922,18 +2925,17 @@ static void t2_dbg(hipStream_t s, int line) {
   fprintf(stderr, "[knn tier2] line %d done (%s)\n", line, hipGetErrorString(hipStreamSynchronize(s)));
   fflush(stderr);
 }
-static int run_ivf_tier2(const KnnPlan& p, const KnnBuffers& b, const KnnCall& c, int k, double cert_scale, int n_flag,
-                         int64_t rows, int32_t* out_idx, double* out_dist, int* n_flag2_host) {
+static int run_ivf_tier2(const KnnPlan& p, const KnnBuffers& b, const KnnCall& c, int n_flag, int64_t rows, int* n_flag2_host) {
   using C = RegCfg<25, 64, false>;
   const int nc = p.n_cells;
   const CellTables t = cell_tables(b, nc);
   hipStream_t s = c.s;
   int* cnt2 = b.t2_ints;
   int* slot_off2 = b.t2_ints + nc;
-  int* ctr2 = b.t2_ints + 2 * nc;  // [0] still uncertified, [2..3] / [4..5] pair counters of the second sweep (not reported)
+  int* ctr2 = b.t2_ints + 2 * nc;  // KC_UNCERTIFIED: still uncertified; KC_PAIRS, KC_PREPASS_PAIRS of the second sweep (not reported)
   *n_flag2_host = 0;
   SCAMD_HIP_CHECK(hipMemsetAsync(cnt2, 0, sizeof(int) * nc, s));
-  SCAMD_HIP_CHECK(hipMemsetAsync(ctr2, 0, sizeof(int) * 8, s));
+  SCAMD_HIP_CHECK(hipMemsetAsync(ctr2, 0, sizeof(int) * KC_HOST_SLOTS, s));
   hipLaunchKernelGGL(ivf_t2_count_kernel, dim3((unsigned)ceil_div(n_flag, 256)), dim3(256), 0, s, b.flag_list, n_flag, c.q_begin,
                      b.labels, t.cell_map, cnt2, b.t2_cell, b.t2_pos);
   SCAMD_LAUNCH_CHECK();
@@ -2965,24 +2967,127 @@ static int run_ivf_tier2(const KnnPlan& p, const KnnBuffers& b, const KnnCall& c
   SCAMD_HIP_CHECK(hipFuncSetAttribute(reinterpret_cast<const void*>(kern), hipFuncAttributeMaxDynamicSharedMemorySize,
                                       (int)lds));
   IvfArgs iv = ivf_args(b, t, nc, c.d);
-  iv.pairs = reinterpret_cast<unsigned long long*>(ctr2 + 2);
+  iv.pairs = reinterpret_cast<unsigned long long*>(ctr2 + KC_PAIRS);
   iv.prepass_tiles = 16;
   iv.prepass_min2 = 1;
   iv.n_slots = n_blocks;  // (a few hundred queries: one workgroup per block, no queues)
-  const int thr_rank = std::min(32, std::max(1, k + 6));
+  const int thr_rank = std::min(32, std::max(1, c.k + 6));
   hipLaunchKernelGGL(kern, dim3(n_blocks), dim3(C::NT), lds, s, b.xp2, (int)(rows / 64), rows, c.q_begin, thr_rank, b.cand_idx,
                      b.cand_tau, iv);
   SCAMD_LAUNCH_CHECK();
   t2_dbg(s, __LINE__);
-  const size_t rlds = rerank_rows_lds_bytes(c.d, thr_rank - 1);
-  SCAMD_HIP_CHECK(hipFuncSetAttribute(reinterpret_cast<const void*>(knn_rerank_rows_kernel),
-                                      hipFuncAttributeMaxDynamicSharedMemorySize, (int)rlds));
-  hipLaunchKernelGGL(knn_rerank_rows_kernel, dim3((unsigned)ceil_div(n_flag, 8)), dim3(256), rlds, s, c.x, b.mu, c.n, c.d, c.ld,
-                     c.q_begin, c.n_query, k, std::max(1, thr_rank - 1), b.cand_idx, b.cand_tau, b.cmax, cert_scale, CERT_K_F32,
-                     0.0, out_idx, out_dist, b.kth_d2, b.flag_list2, ctr2, (const int*)b.flag_list, (int64_t)n_flag);
-  SCAMD_LAUNCH_CHECK();
+  if (int rc = launch_rerank_rows(b, c, thr_rank, CERT_K_F32, 0.0, b.flag_list2, ctr2 + KC_UNCERTIFIED, b.flag_list, n_flag)) return rc;
   t2_dbg(s, __LINE__);
-  SCAMD_READBACK_NOW(n_flag2_host, ctr2, sizeof(int), s);
+  SCAMD_READBACK_NOW(n_flag2_host, ctr2 + KC_UNCERTIFIED, sizeof(int), s);
+  return SCAMD_OK;
+}
+
+// ---- the stages of one search, in the order knn_l2_impl runs them ---------------------------------------------
+// column means and, for the brute-force sweep, the image (the pruned sweep packs its own, cell-sorted)
+static int stage_mean_and_image(const KnnPlan& p, const KnnBuffers& b, const KnnCall& c) {
+  hipStream_t s = c.s;
+  SCAMD_HIP_CHECK(hipMemsetAsync(b.cmax, 0, 16, s));
+  SCAMD_HIP_CHECK(hipMemsetAsync(b.counters, 0, sizeof(int) * KC_HOST_SLOTS, s));
+  hipLaunchKernelGGL(knn_colsum_kernel, dim3(MEAN_BLOCKS), dim3(1024), 0, s, c.x, c.n, c.d, c.ld, b.mean_partial);
+  SCAMD_LAUNCH_CHECK();
+  hipLaunchKernelGGL(knn_colmean_kernel, dim3(1), dim3(KNN_MAX_D), 0, s, b.mean_partial, c.n, c.d, b.mu);
+  SCAMD_LAUNCH_CHECK();
+  if (p.ivf) return SCAMD_OK;
+  const int blocks = (int)std::min<int64_t>((p.n_pad + 3) / 4, 256 * 16);
+  if (p.reg) {
+    const int HP = (p.H + 1 + 3) / 4 * 4;
+    hipLaunchKernelGGL(knn_pack_image_kernel, dim3(blocks), dim3(256), 0, s, c.x, b.mu, c.n, c.d, c.ld, p.H, HP, p.row_dwords,
+                       p.n_pad, b.xp, b.cmax, p.b3 ? 1 : 0);
+  } else {
+    hipLaunchKernelGGL(knn_pack_kernel, dim3(blocks), dim3(256), 0, s, c.x, b.mu, c.n, c.d, c.ld, 2 * p.H, p.n_pad, b.xp, b.cn,
+                       b.cmax);
+  }
+  SCAMD_LAUNCH_CHECK();
+  return SCAMD_OK;
+}
+// pass 1 between the two events; ivf_layout: image rows and query slots of the pruned sweep
+static int stage_sweep(const KnnPlan& p, const KnnBuffers& b, const KnnCall& c, hipEvent_t ev0, hipEvent_t ev1, int64_t* ivf_layout) {
+  if (p.ivf) return dispatch_ivf(p, b, c, ev0, ev1, ivf_layout);
+  SCAMD_HIP_CHECK(hipEventRecord(ev0, c.s));
+  if (int rc = dispatch_select(p, b, c.q_begin, c.s)) return rc;
+  SCAMD_HIP_CHECK(hipEventRecord(ev1, c.s));
+  return SCAMD_OK;
+}
+// pass 2 with the certificate factors of the engine that swept (d > 128: 2 * (H - 64) more accumulated terms, float32 engine only);
+// the register-list kernels' sorted lists go row-wise, in slot order when pruned
+static int stage_rerank(const KnnPlan& p, const KnnBuffers& b, const KnnCall& c, int64_t n_slots) {
+  const double cert_k = p.b3 ? CERT_K_B3 : CERT_K_F32 + (p.H > 64 ? 2.0 * (p.H - 64) : 0.0);
+  const double cert_k2 = p.b3 ? CERT_K2_B3 : 0.0;
+  if (!(p.reg && p.KP == 32 && c.d <= 64)) return launch_rerank_lds(p, b, c, cert_k, cert_k2);
+  return launch_rerank_rows(b, c, p.thr_rank, cert_k, cert_k2, b.flag_list, b.counters + KC_UNCERTIFIED,
+                            p.ivf ? (const int*)b.qorder : (const int*)nullptr, p.ivf ? n_slots : c.n_query);
+}
+// the counters of passes 1 and 2 -> what the getters report; *n_flag: queries the certificate rejected
+static int stage_statistics(const KnnPlan& p, const KnnBuffers& b, const KnnCall& c, hipEvent_t ev0, hipEvent_t ev1, int* n_flag) {
+  int h_counters[KC_HOST_SLOTS] = {};
+  SCAMD_READBACK_NOW(h_counters, b.counters, sizeof(h_counters), c.s);
+  float ms = -1.f;
+  if (hipEventElapsedTime(&ms, ev0, ev1) != hipSuccess) ms = -1.f;
+  g_last.select_ms = ms;
+  unsigned long long pairs = 0, pre = 0;
+  memcpy(&pairs, &h_counters[KC_PAIRS], 8);
+  memcpy(&pre, &h_counters[KC_PREPASS_PAIRS], 8);
+  g_last.select_pairs = p.ivf ? (double)pairs : (double)c.n_query * (double)c.n;
+  g_last.select_prepass_pairs = p.ivf ? (double)pre : 0.0;
+  g_last.select_engine = p.b3 ? 1 : 0;
+  SCAMD_REQUIRE(h_counters[KC_LAUNCH_ORDER_ERR] == 0, SCAMD_EINTERNAL,
+                "knn: a query block of the pruned sweep got no launch slot (XCD-aware order)");
+  *n_flag = h_counters[KC_UNCERTIFIED];
+  return SCAMD_OK;
+}
+// second tier: the float32 engine on what the bf16 engine's certificate rejected (SCAMD_KNN_TIER2_MIN, default 256
+// queries: below that the float64 scan of a few queries is cheaper than a second image); *n_flag / *flag_list: what is left
+static int stage_second_tier(const KnnPlan& p, const KnnBuffers& b, const KnnCall& c, int64_t rows, int* n_flag, const int** flag_list) {
+  g_last.second_tier = 0;
+  if (!(p.ivf && p.b3 && *n_flag > env_int("SCAMD_KNN_TIER2_MIN", 256))) return SCAMD_OK;
+  int n_flag2 = 0;
+  if (int rc = run_ivf_tier2(p, b, c, *n_flag, rows, &n_flag2)) return rc;
+  g_last.second_tier = *n_flag;
+  *n_flag = n_flag2;
+  *flag_list = b.flag_list2;
+  return SCAMD_OK;
+}
+// pass 3: float64 scan of the queries `todo`; one whose table overflowed comes back with a tighter bound (knn_fallback_rank_kernel)
+static int stage_scan_rounds(const KnnPlan& p, const KnnBuffers& b, const KnnCall& c, int n_todo, const int* todo) {
+  hipStream_t s = c.s;
+  if (n_todo > 0) SCAMD_HIP_CHECK(hipMemsetAsync(b.kth_idx, 0xff, sizeof(int) * (size_t)c.n_query, s));
+  for (int round = 0; n_todo > 0; ++round) {
+    int* retry = b.fb_retry[round & 1];
+    SCAMD_HIP_CHECK(hipMemsetAsync(b.counters + KC_RETRY, 0, sizeof(int), s));
+    for (int begin = 0; begin < n_todo; begin += FALLBACK_CHUNK) {
+      const int count = std::min(FALLBACK_CHUNK, n_todo - begin);
+      SCAMD_HIP_CHECK(hipMemsetAsync(b.fb_counts, 0, sizeof(int) * count, s));
+      const ScanArgs a{c.x, c.d, c.ld, c.q_begin, todo, begin, b.kth_d2, b.kth_idx, b.scratch_d, b.scratch_i, b.fb_counts};
+      if (p.ivf) {
+        const int nc = p.n_cells;
+        const CellTables t = cell_tables(b, nc);
+        // (few queries: one workgroup per cell and query -- a launch lasts as long as its busiest workgroup)
+        hipLaunchKernelGGL(knn_fallback_scan_cells_kernel, dim3(count <= 128 ? nc : std::min(nc, 64), count), dim3(256), 0, s, a, b.cent,
+                           t.radius, t.tile0, t.ntiles, b.perm, nc);
+      } else {
+        const int chunks = (int)std::max<int64_t>(1, std::min<int64_t>(FALLBACK_ROW_CHUNKS, c.n / 2048));
+        hipLaunchKernelGGL(knn_fallback_scan_kernel, dim3(chunks, count), dim3(256), 0, s, a, c.n);
+      }
+      SCAMD_LAUNCH_CHECK();
+      hipLaunchKernelGGL(knn_fallback_rank_kernel, dim3(count), dim3(256), 0, s, c.k, todo, begin, b.scratch_d,
+                         b.scratch_i, b.fb_counts, c.out_idx, c.out_dist, b.kth_d2, b.kth_idx, retry, b.counters + KC_RETRY,
+                         b.counters + KC_SCAN_STUCK);
+      SCAMD_LAUNCH_CHECK();
+    }
+    int h_counters[KC_HOST_SLOTS] = {};
+    SCAMD_READBACK_NOW(h_counters, b.counters, sizeof(h_counters), s);
+    // every round lowers the bound key of every query it sends back (knn_fallback_rank_kernel), so the loop ends; a round
+    // that did not is a defect and is reported at once instead of being repeated
+    SCAMD_REQUIRE(h_counters[KC_SCAN_STUCK] == 0, SCAMD_EINTERNAL, "knn: float64 scan round %d made no progress on %d of %d queries",
+                  round, h_counters[KC_SCAN_STUCK], n_todo);
+    n_todo = h_counters[KC_RETRY];
+    todo = retry;
+  }
   return SCAMD_OK;
 }
 
@@ -2990,13 +3095,13 @@ static int run_ivf_tier2(const KnnPlan& p, const KnnBuffers& b, const KnnCall& c
 
 using namespace scamd;
 
-extern "C" float scamd_knn_last_select_ms(void) { return g_last_select_ms; }
-extern "C" double scamd_knn_last_select_pairs(void) { return g_last_select_pairs; }
-extern "C" double scamd_knn_last_select_prepass_pairs(void) { return g_last_select_prepass_pairs; }
-extern "C" int scamd_knn_last_select_engine(void) { return g_last_select_engine; }
-extern "C" int scamd_knn_last_second_tier_queries(void) { return g_last_second_tier; }
-extern "C" int scamd_knn_last_nprobe(void) { return g_last_nprobe; }
-extern "C" int scamd_knn_last_coarse(void) { return g_last_coarse; }
+extern "C" float scamd_knn_last_select_ms(void) { return g_last.select_ms; }
+extern "C" double scamd_knn_last_select_pairs(void) { return g_last.select_pairs; }
+extern "C" double scamd_knn_last_select_prepass_pairs(void) { return g_last.select_prepass_pairs; }
+extern "C" int scamd_knn_last_select_engine(void) { return g_last.select_engine; }
+extern "C" int scamd_knn_last_second_tier_queries(void) { return g_last.second_tier; }
+extern "C" int scamd_knn_last_nprobe(void) { return g_last.nprobe; }
+extern "C" int scamd_knn_last_coarse(void) { return g_last.coarse; }
 
 extern "C" size_t scamd_knn_workspace_bytes(int64_t n, int d, int64_t n_query, int k) {
   // one figure for the exact and the approximate entry point: the approximate plan goes through the cell tables at
@@ -3015,7 +3120,45 @@ extern "C" size_t scamd_knn_workspace_bytes(int64_t n, int d, int64_t n_query, i
 
 static int knn_l2_impl(const float* x, int64_t n, int d, int64_t ld_x, int64_t q_begin, int64_t n_query, int k,
                        int32_t* out_idx, double* out_dist, double cert_scale, int64_t* n_fallback_host, void* workspace,
-                       size_t workspace_bytes, scamd_stream_t stream, int nprobe);
+                       size_t workspace_bytes, scamd_stream_t stream, int nprobe) {
+  // (an empty query range has empty outputs: an allocator may hand out null for them)
+  SCAMD_REQUIRE(x && ((out_idx && out_dist) || n_query == 0), SCAMD_EINVAL, "knn: null pointer");
+  SCAMD_REQUIRE(n >= 1 && d >= 1 && ld_x >= d, SCAMD_EINVAL, "knn: bad shape n=%lld d=%d ld=%lld",
+                (long long)n, d, (long long)ld_x);
+  SCAMD_REQUIRE(n < (int64_t)1 << 31, SCAMD_EUNSUPPORTED, "knn: n=%lld exceeds int32 row ids", (long long)n);
+  SCAMD_REQUIRE(q_begin >= 0 && n_query >= 0 && q_begin + n_query <= n, SCAMD_EINVAL,
+                "knn: query range [%lld, %lld) outside [0, %lld)", (long long)q_begin,
+                (long long)(q_begin + n_query), (long long)n);
+  SCAMD_REQUIRE(k >= 1, SCAMD_EINVAL, "knn: k=%d", k);
+  KnnPlan p;
+  SCAMD_REQUIRE(knn_plan(n, d, n_query, k, &p, nprobe), SCAMD_EUNSUPPORTED,
+                "knn: unsupported d=%d (max 256) or k=%d (max 256)", d, k);
+  g_last.nprobe = p.nprobe;
+  if (n_fallback_host) *n_fallback_host = 0;
+  if (n_query == 0) return SCAMD_OK;
+  Workspace ws(workspace, workspace_bytes);
+  KnnBuffers b;
+  knn_carve(ws, p, n_query, &b);
+  SCAMD_REQUIRE(workspace && ws.ok, SCAMD_EWORKSPACE, "knn: workspace %zu < required %zu",
+                workspace_bytes, ws.used());
+  const KnnCall call{x, n, d, ld_x, q_begin, n_query, stream, k, cert_scale, out_idx, out_dist};
+  hipEvent_t ev0 = nullptr, ev1 = nullptr;
+  SCAMD_HIP_CHECK(hipEventCreate(&ev0));
+  const EventOwner own0(ev0);
+  SCAMD_HIP_CHECK(hipEventCreate(&ev1));
+  const EventOwner own1(ev1);
+
+  int64_t ivf_layout[2] = {0, 0};  // image rows, query slots of the pruned sweep
+  int n_flag = 0;
+  const int* flag_list = b.flag_list;
+  if (int rc = stage_mean_and_image(p, b, call)) return rc;
+  if (int rc = stage_sweep(p, b, call, ev0, ev1, ivf_layout)) return rc;
+  if (int rc = stage_rerank(p, b, call, ivf_layout[1])) return rc;
+  if (int rc = stage_statistics(p, b, call, ev0, ev1, &n_flag)) return rc;
+  if (int rc = stage_second_tier(p, b, call, ivf_layout[0], &n_flag, &flag_list)) return rc;
+  if (n_fallback_host) *n_fallback_host = n_flag;
+  return stage_scan_rounds(p, b, call, n_flag, flag_list);
+}
 
 extern "C" int scamd_knn_l2_f32(const float* x, int64_t n, int d, int64_t ld_x, int64_t q_begin,
                                 int64_t n_query, int k, int32_t* out_idx, double* out_dist,
@@ -3037,154 +3180,6 @@ extern "C" int scamd_knn_l2_ivf_f32(const float* x, int64_t n, int d, int64_t ld
                                     scamd_stream_t stream) {
   return knn_l2_impl(x, n, d, ld_x, q_begin, n_query, k, out_idx, out_dist, 1.0, n_fallback_host, workspace,
                      workspace_bytes, stream, nprobe > 0 ? nprobe : 0);
-}
-
-static int knn_l2_impl(const float* x, int64_t n, int d, int64_t ld_x, int64_t q_begin, int64_t n_query, int k,
-                       int32_t* out_idx, double* out_dist, double cert_scale, int64_t* n_fallback_host, void* workspace,
-                       size_t workspace_bytes, scamd_stream_t stream, int nprobe) {
-  // (an empty query range has empty outputs: an allocator may hand out null for them)
-  SCAMD_REQUIRE(x && ((out_idx && out_dist) || n_query == 0), SCAMD_EINVAL, "knn: null pointer");
-  SCAMD_REQUIRE(n >= 1 && d >= 1 && ld_x >= d, SCAMD_EINVAL, "knn: bad shape n=%lld d=%d ld=%lld",
-                (long long)n, d, (long long)ld_x);
-  SCAMD_REQUIRE(n < (int64_t)1 << 31, SCAMD_EUNSUPPORTED, "knn: n=%lld exceeds int32 row ids", (long long)n);
-  SCAMD_REQUIRE(q_begin >= 0 && n_query >= 0 && q_begin + n_query <= n, SCAMD_EINVAL,
-                "knn: query range [%lld, %lld) outside [0, %lld)", (long long)q_begin,
-                (long long)(q_begin + n_query), (long long)n);
-  SCAMD_REQUIRE(k >= 1, SCAMD_EINVAL, "knn: k=%d", k);
-  KnnPlan p;
-  SCAMD_REQUIRE(knn_plan(n, d, n_query, k, &p, nprobe), SCAMD_EUNSUPPORTED,
-                "knn: unsupported d=%d (max 256) or k=%d (max 256)", d, k);
-  g_last_nprobe = p.nprobe;
-  if (n_fallback_host) *n_fallback_host = 0;
-  if (n_query == 0) return SCAMD_OK;
-  Workspace ws(workspace, workspace_bytes);
-  KnnBuffers b;
-  knn_carve(ws, p, n_query, &b);
-  SCAMD_REQUIRE(workspace && ws.ok, SCAMD_EWORKSPACE, "knn: workspace %zu < required %zu",
-                workspace_bytes, ws.used());
-  hipStream_t s = stream;
-
-  SCAMD_HIP_CHECK(hipMemsetAsync(b.cmax, 0, 16, s));
-  SCAMD_HIP_CHECK(hipMemsetAsync(b.counters, 0, 32, s));
-  hipLaunchKernelGGL(knn_colsum_kernel, dim3(MEAN_BLOCKS), dim3(1024), 0, s, x, n, d, ld_x, b.mean_partial);
-  SCAMD_LAUNCH_CHECK();
-  hipLaunchKernelGGL(knn_colmean_kernel, dim3(1), dim3(KNN_MAX_D), 0, s, b.mean_partial, n, d, b.mu);
-  SCAMD_LAUNCH_CHECK();
-  if (!p.ivf) {
-    int blocks = (int)std::min<int64_t>((p.n_pad + 3) / 4, 256 * 16);
-    if (p.reg) {
-      const int HP = (p.H + 1 + 3) / 4 * 4;
-      hipLaunchKernelGGL(knn_pack_image_kernel, dim3(blocks), dim3(256), 0, s, x, b.mu, n, d, ld_x, p.H, HP,
-                         p.row_dwords, p.n_pad, b.xp, b.cmax, p.b3 ? 1 : 0);
-    } else {
-      hipLaunchKernelGGL(knn_pack_kernel, dim3(blocks), dim3(256), 0, s, x, b.mu, n, d, ld_x, 2 * p.H,
-                         p.n_pad, b.xp, b.cn, b.cmax);
-    }
-    SCAMD_LAUNCH_CHECK();
-  }
-  const KnnCall call{x, n, d, ld_x, q_begin, n_query, s};
-  int64_t ivf_layout[2] = {0, 0};  // image rows, query slots of the pruned sweep
-  hipEvent_t ev0 = nullptr, ev1 = nullptr;
-  SCAMD_HIP_CHECK(hipEventCreate(&ev0));
-  const EventOwner own0(ev0);
-  SCAMD_HIP_CHECK(hipEventCreate(&ev1));
-  const EventOwner own1(ev1);
-  if (p.ivf) {
-    if (int rc = dispatch_ivf(p, b, call, ev0, ev1, ivf_layout)) return rc;
-  } else {
-    SCAMD_HIP_CHECK(hipEventRecord(ev0, s));
-    if (int rc = dispatch_select(p, b, q_begin, s)) return rc;
-    SCAMD_HIP_CHECK(hipEventRecord(ev1, s));
-  }
-  // certificate factors of the engine that swept (d > 128: 2 * (H - 64) more accumulated terms, float32 engine only)
-  const double cert_k = p.b3 ? CERT_K_B3 : CERT_K_F32 + (p.H > 64 ? 2.0 * (p.H - 64) : 0.0);
-  const double cert_k2 = p.b3 ? CERT_K2_B3 : 0.0;
-  if (p.reg && p.KP == 32 && d <= 64) {
-    // register-list kernels: sorted lists, row-wise re-rank of the entries below the threshold, in slot order when pruned
-    const int n_rank = std::max(1, p.thr_rank - 1);
-    const int64_t n_list = p.ivf ? ivf_layout[1] : n_query;
-    const size_t lds = rerank_rows_lds_bytes(d, n_rank);
-    SCAMD_HIP_CHECK(hipFuncSetAttribute(reinterpret_cast<const void*>(knn_rerank_rows_kernel),
-                                        hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
-    hipLaunchKernelGGL(knn_rerank_rows_kernel, dim3((unsigned)ceil_div(n_list, 8)), dim3(256), lds, s, x, b.mu, n, d, ld_x,
-                       q_begin, n_query, k, n_rank, b.cand_idx, b.cand_tau, b.cmax, cert_scale, cert_k, cert_k2, out_idx,
-                       out_dist, b.kth_d2, b.flag_list, b.counters, p.ivf ? (const int*)b.qorder : (const int*)nullptr, n_list);
-    SCAMD_LAUNCH_CHECK();
-  } else {
-    auto rerank = knn_rerank_kernel<32>;
-    if (p.KP == 64) rerank = knn_rerank_kernel<64>;
-    else if (p.KP == 128) rerank = knn_rerank_kernel<128>;
-    else if (p.KP != 32) rerank = knn_rerank_kernel<288>;
-    hipLaunchKernelGGL(rerank, dim3((unsigned)((n_query + 3) / 4)), dim3(256), 0, s, x, b.mu, n, d, ld_x, q_begin, n_query, k,
-                       b.cand_idx, b.cand_tau, b.cmax, cert_scale, cert_k, cert_k2, out_idx, out_dist, b.kth_d2, b.flag_list,
-                       b.counters, (const int*)nullptr, 0);
-    SCAMD_LAUNCH_CHECK();
-  }
-  int h_counters[8] = {0, 0, 0, 0, 0, 0, 0, 0};
-  SCAMD_READBACK_NOW(h_counters, b.counters, 32, s);
-  {
-    float ms = -1.f;
-    if (hipEventElapsedTime(&ms, ev0, ev1) != hipSuccess) ms = -1.f;
-    g_last_select_ms = ms;
-    unsigned long long pairs = 0;
-    memcpy(&pairs, &h_counters[2], 8);
-    g_last_select_pairs = p.ivf ? (double)pairs : (double)n_query * (double)n;
-    unsigned long long pre = 0;
-    memcpy(&pre, &h_counters[4], 8);
-    g_last_select_prepass_pairs = p.ivf ? (double)pre : 0.0;
-    g_last_select_engine = p.b3 ? 1 : 0;
-  }
-  SCAMD_REQUIRE(h_counters[6] == 0, SCAMD_EINTERNAL, "knn: a query block of the pruned sweep got no launch slot (XCD-aware order)");
-  int n_flag = h_counters[0];
-  const int* flag_list = b.flag_list;
-  g_last_second_tier = 0;
-  // second tier: the float32 engine on what the bf16 engine's certificate rejected (SCAMD_KNN_TIER2_MIN, default 256
-  // queries: below that the float64 scan of a few queries is cheaper than a second image)
-  if (p.ivf && p.b3 && n_flag > env_int("SCAMD_KNN_TIER2_MIN", 256)) {
-    int n_flag2 = 0;
-    if (int rc = run_ivf_tier2(p, b, call, k, cert_scale, n_flag, ivf_layout[0], out_idx, out_dist, &n_flag2)) return rc;
-    g_last_second_tier = n_flag;
-    n_flag = n_flag2;
-    flag_list = b.flag_list2;
-  }
-  if (n_fallback_host) *n_fallback_host = n_flag;
-  // float64 scan of what is left; a query whose table overflowed comes back with a tighter bound (knn_fallback_rank_kernel)
-  int n_todo = n_flag;
-  const int* todo = flag_list;
-  if (n_todo > 0) SCAMD_HIP_CHECK(hipMemsetAsync(b.kth_idx, 0xff, sizeof(int) * (size_t)n_query, s));
-  for (int round = 0; n_todo > 0; ++round) {
-    int* retry = b.fb_retry[round & 1];
-    SCAMD_HIP_CHECK(hipMemsetAsync(b.counters + 1, 0, sizeof(int), s));
-    for (int begin = 0; begin < n_todo; begin += FALLBACK_CHUNK) {
-      int count = std::min(FALLBACK_CHUNK, n_todo - begin);
-      SCAMD_HIP_CHECK(hipMemsetAsync(b.fb_counts, 0, sizeof(int) * count, s));
-      if (p.ivf) {
-        const int nc = p.n_cells;
-        const CellTables t = cell_tables(b, nc);
-        // (few queries: one workgroup per cell and query -- a launch lasts as long as its busiest workgroup)
-        hipLaunchKernelGGL(knn_fallback_scan_cells_kernel, dim3(count <= 128 ? nc : std::min(nc, 64), count), dim3(256), 0, s, x, d, ld_x, q_begin,
-                           todo, begin, b.kth_d2, b.kth_idx, b.scratch_d, b.scratch_i, b.fb_counts, b.cent,
-                           t.radius, t.tile0, t.ntiles, b.perm, nc);
-      } else {
-        const int chunks = (int)std::max<int64_t>(1, std::min<int64_t>(FALLBACK_ROW_CHUNKS, n / 2048));
-        hipLaunchKernelGGL(knn_fallback_scan_kernel, dim3(chunks, count), dim3(256), 0, s, x, n, d, ld_x, q_begin,
-                           todo, begin, b.kth_d2, b.kth_idx, b.scratch_d, b.scratch_i, b.fb_counts);
-      }
-      SCAMD_LAUNCH_CHECK();
-      hipLaunchKernelGGL(knn_fallback_rank_kernel, dim3(count), dim3(256), 0, s, k, todo, begin, b.scratch_d,
-                         b.scratch_i, b.fb_counts, out_idx, out_dist, b.kth_d2, b.kth_idx, retry, b.counters + 1,
-                         b.counters + 7);
-      SCAMD_LAUNCH_CHECK();
-    }
-    SCAMD_READBACK_NOW(h_counters, b.counters, 32, s);
-    // every round lowers the bound key of every query it sends back (knn_fallback_rank_kernel), so the loop ends; a round
-    // that did not is a defect and is reported at once instead of being repeated
-    SCAMD_REQUIRE(h_counters[7] == 0, SCAMD_EINTERNAL, "knn: float64 scan round %d made no progress on %d of %d queries",
-                  round, h_counters[7], n_todo);
-    n_todo = h_counters[1];
-    todo = retry;
-  }
-  return SCAMD_OK;
 }
 
 // ------------------------------------------------------------------------------------------------

@@ -71,6 +71,24 @@ DUPLICATE_GROUPS = (10, 16, 33, 100, 600)
 DUPLICATE_CASES = ((50, 15), (20, 15), (50, 30), (100, 15))
 FALLBACK_CAP = 2048  # csrc/knn.hip: rows the float64 scan's table holds per query
 
+# cert_scale = 1e30 (no query can be certified) on every path that follows the sweep: (n, d, k, environment, query shard
+# (q_begin, n_query) or None = all rows, queries the second tier must report).  Without pruning one case per re-rank kernel:
+# the row-wise one of the register-list kernels and knn_rerank_kernel<32 | 64 | 128 | 288>, then the plain float64 scan.
+# With pruning the row-wise re-rank in slot order and the scan over cells, once past the second tier (its threshold out of
+# reach) and once through it (threshold 0: it re-ranks every query and rejects every one again).
+_BRUTE, _PRUNED = {"SCAMD_KNN_IVF": "0"}, {"SCAMD_KNN_IVF": "1", "SCAMD_KNN_CELL_ROWS": "512"}
+FORCED_SCAN_CASES = (
+    (700, 20, 10, _BRUTE, None, 0),
+    (700, 100, 15, _BRUTE, None, 0),
+    (700, 50, 30, _BRUTE, None, 0),
+    (700, 24, 100, _BRUTE, None, 0),
+    (700, 10, 200, _BRUTE, None, 0),
+    (4300, 50, 15, {**_PRUNED, "SCAMD_KNN_TIER2_MIN": str(2 ** 30)}, (0, 256), 0),
+    (4300, 50, 15, {**_PRUNED, "SCAMD_KNN_TIER2_MIN": "0"}, (0, 256), 256),
+)
+FORCED_SCAN_IDS = [f"n{n}-d{d}-k{k}-" + ("brute" if e is _BRUTE else f"pruned-tier2min{e['SCAMD_KNN_TIER2_MIN']}")
+                   for n, d, k, e, _, _ in FORCED_SCAN_CASES]
+
 
 def assert_every_instantiation_has_a_case(already_run_elsewhere):
     """`already_run_elsewhere`: the (n, d, k) list of test_gpu_kernels.py::test_knn_vs_sklearn.  Every (H, KP) of the LDS-list
@@ -195,6 +213,25 @@ def check_against_f64(x: np.ndarray, k: int, rows: np.ndarray, idx: np.ndarray, 
     if tie_fraction is not None:
         assert differ <= tie_fraction * m, f"{label}: {differ} of {m} rows needed the tie exemption"
     return differ
+
+
+def check_forced_scan(knn, second_tier_queries, case, label=""):
+    """one row of FORCED_SCAN_CASES (its environment already set).  knn(x, k, q_begin, n_query, cert_scale) -> (idx, dist,
+    n_fallback) as numpy; second_tier_queries() -> scamd_knn_last_second_tier_queries().  With cert_scale = 1e30 every query
+    goes through the float64 scan, the lists are the float64 brute force's, and they are BITWISE those of the same call at
+    cert_scale = 1: both routes sum (q - c)^2 by fma in coordinate order and order by the key (distance, row), and a
+    certified list holds every row at or below its k-th distance."""
+    n, d, k, _, shard, tier2 = case
+    q_begin, n_query = shard if shard else (0, n)
+    x = clustered(n, d, 7 * d + k, PRUNED_SPREAD)
+    i1, d1, _ = knn(x, k, q_begin, n_query, 1.0)
+    i2, d2, n_scan = knn(x, k, q_begin, n_query, 1e30)
+    assert n_scan == n_query, f"{label}: {n_scan} of {n_query} queries reached the float64 scan"
+    assert second_tier_queries() == tier2, f"{label}: second tier saw {second_tier_queries()} queries, expected {tier2}"
+    assert plan(d, k)[4] or not shard
+    check_against_f64(x, k, np.arange(q_begin, q_begin + n_query), i2, d2, n_fallback=n_scan, n_query=n_query, label=label)
+    assert i1.tobytes() == i2.tobytes(), f"{label}: index lists differ between cert_scale 1 and 1e30"
+    assert d1.tobytes() == d2.tobytes(), f"{label}: distances differ bitwise between cert_scale 1 and 1e30"
 
 
 def check_duplicate_groups(groups, k: int, idx: np.ndarray, dist: np.ndarray, label="", q_begin: int = 0):

@@ -209,16 +209,34 @@ def test_knn_trace_dump_matches_its_parser(emu, monkeypatch, tmp_path):
     assert (tr[:, 7] >= 1).all() and (tr[:, 7] <= 16).all() and cell.min() >= 0 and cell.max() < 16
 
 
-def test_knn_float64_fallback_scan(emu):
-    """cert_scale = 1e30: no query can be certified, every one goes through the float64 scan"""
+def _forced_scan_cases():
+    import knn_shape_cases as S
+
+    return [pytest.param(None, id="blobs-700x20-k10")] + [pytest.param(c, id=i) for c, i in zip(S.FORCED_SCAN_CASES, S.FORCED_SCAN_IDS)]
+
+
+@pytest.mark.parametrize("case", _forced_scan_cases())
+def test_knn_float64_fallback_scan(emu, monkeypatch, case):
+    """cert_scale = 1e30: no query can be certified, every one goes through the float64 scan -- after every re-rank kernel,
+    past and through the second tier, over all rows and over cells (knn_shape_cases.FORCED_SCAN_CASES)"""
     from oracle import compare as cmp
 
     H, lib = emu
-    x = _blobs(700, 20, 4, 3)
-    idx, dist, n_fallback = H.knn(lib, x, 10, cert_scale=1e30)
-    ei, ed = oknn.knn_exact_f64(x, np.arange(700), 10)
-    assert n_fallback == 700
-    assert cmp.knn_rows_differing_beyond_ties(idx, dist, ei, ed)[0] == 0
+    if case is None:
+        x = _blobs(700, 20, 4, 3)
+        idx, dist, n_fallback = H.knn(lib, x, 10, cert_scale=1e30)
+        ei, ed = oknn.knn_exact_f64(x, np.arange(700), 10)
+        assert n_fallback == 700
+        assert cmp.knn_rows_differing_beyond_ties(idx, dist, ei, ed)[0] == 0
+        return
+    import knn_shape_cases as S
+
+    for name, value in case[3].items():
+        monkeypatch.setenv(name, value)
+    lib.emu_reset_stats()
+    S.check_forced_scan(lambda x, k, qb, nq, cs: H.knn(lib, x, k, q_begin=qb, n_query=nq, cert_scale=cs),
+                        lambda: int(lib.scamd_knn_last_second_tier_queries()), case, label="emu forced scan")
+    _no_partial_wave_collectives(H, lib)
 
 
 @pytest.mark.parametrize("small", ["1", "0"])

@@ -2,8 +2,10 @@
 
 The search the reference runs is sklearn's exact brute force (src/scanpy/neighbors/__init__.py:754-768); ours filters with
 three bf16 MFMA products per pair and certifies every query in float64 against an error bound
-(csrc/knn.hip: knn_rerank_rows_kernel).  A bound that is too small stays invisible on friendly data -- round 3 shipped one
-2-4x under-priced for a while and every test stayed green.  Three kinds of test close that hole:
+(csrc/knn.hip: certify(), ONE function called by both re-rank kernels: knn_rerank_rows_kernel, which the shapes below
+take, and knn_rerank_kernel<KP> for k > 24 or d > 64 -- the bound attacked here is the bound of both).  A bound that is
+too small stays invisible on friendly data -- round 3 shipped one 2-4x under-priced for a while and every test stayed
+green.  Three kinds of test close that hole:
 
 (a) inputs the centring cannot remove (clusters at +-3000 along different axes, rows with one huge coordinate, near-duplicate
     pairs far from the origin, and the split's own worst-case values) at n >= 100k, so the pruned sweep runs, against a

@@ -1,7 +1,7 @@
 """Every template instantiation of the exact kNN search (`scamd_knn_l2_f32`, csrc/knn.hip) against the float64 brute force
 (run with -m gpu): the LDS-list kernels test_gpu_kernels.py does not reach, the boundaries of `knn_plan()`, the cell-pruned
-sweep away from k = 15, query shards on the LDS-list kernels, a row stride larger than d, and groups of identical rows up
-to and beyond the float64 scan's table.  Tables and checker: tests/knn_shape_cases.py (shared with the emulator's
+sweep away from k = 15, query shards on the LDS-list kernels, a row stride larger than d, groups of identical rows up
+to and beyond the float64 scan's table, and the float64 scan forced behind every path that follows the sweep.  Tables and checker: tests/knn_shape_cases.py (shared with the emulator's
 counterparts in test_emu_cpu.py).
 """
 from __future__ import annotations
@@ -159,6 +159,18 @@ def test_query_shards_on_the_lds_list_kernels(K, d, k):
         np.testing.assert_array_equal(d_all[qb:qb + nq], d_s, err_msg=f"shard ({qb}, {nq})")
     rows = np.arange(1031, 1031 + 129)
     S.check_against_f64(x, k, rows, i_all[rows], d_all[rows], label=f"shard rows d={d} k={k}")
+
+
+# ---------------------------------------------------------------------------------------------------------------------
+@pytest.mark.parametrize("case", S.FORCED_SCAN_CASES, ids=S.FORCED_SCAN_IDS)
+def test_forced_float64_scan_on_every_path_after_the_sweep(K, monkeypatch, case):
+    """cert_scale = 1e30 behind every re-rank kernel, past and through the second tier, over all rows and over cells: every
+    query is scanned, the lists are the float64 brute force's and bitwise those of the certified call"""
+    for name, value in case[3].items():
+        monkeypatch.setenv(name, value)
+    lib = K._lib.load()
+    S.check_forced_scan(lambda x, k, qb, nq, cs: _knn(K, _dev(x), k, q_begin=qb, n_query=nq, cert_scale=cs),
+                        lambda: int(lib.scamd_knn_last_second_tier_queries()), case, label=f"forced scan {case[:3]}")
 
 
 # ---------------------------------------------------------------------------------------------------------------------
