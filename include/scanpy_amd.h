@@ -494,6 +494,35 @@ int scamd_pp_scale_dense_f32(const int64_t* indptr, const int32_t* indices, cons
                              const uint8_t* row_mask, void* out, int out_is_f64, scamd_stream_t stream);
 
 /* ------------------------------------------------------------------------------------------
+ * Quality-control metrics: the device half of pp.calculate_qc_metrics (reference: `describe_obs`, `describe_var`,
+ * `top_segment_proportions` and `top_segment_proportions_sparse_csr` in src/scanpy/preprocessing/_qc.py; csrc/qc.hip,
+ * DESIGN.md 3.10).  Input as for the normalisation chain: CSR float32 on the device, a dense matrix as the full pattern.
+ * A stored 0.0 / -0.0 is no entry (the reference calls eliminate_zeros; the matrix is not rewritten).  Values are assumed
+ * finite.  No workspace: the caller owns every output.  Arguments are checked before any HIP call and a rejected call
+ * writes nothing; n = 0 and g = 0 are legal.
+ *
+ * scamd_pp_qc_sweep_f32: one sweep.  Per row: row_nnz [n] = stored non-zeros, row_total [n] = their sum in float64 and,
+ *   for n_masks > 0, row_masked [n_masks x n] (mask-major: row_masked[k * n + r]) = the sum over the genes c with bit k of
+ *   gene_mask[c] set (gene_mask uint32 [g]; n_masks <= 32, SCAMD_EUNSUPPORTED beyond).  Per gene (col_nnz and col_sum both
+ *   given, or both NULL): col_nnz [g] = stored non-zeros, col_sum [g] = their sum in float64; zeroed here.  flags [1]:
+ *   bit 0 = a negative value was seen; zeroed here.  `indices` is read only when a mask or the per-gene outputs are asked
+ *   for.  The per-row outputs are bitwise reproducible; the per-gene sums are float64 atomics: bitwise reproducible on
+ *   integer-valued matrices (partial sums below 2^53), ~1e-15 relative otherwise.
+ * scamd_pp_qc_top_f32: top [n x n_positions] (row-major), top[r, j] = top(positions[j]) of row r under THE RULE: take the
+ *   stored non-zero values of the row, pad them with zeros up to n_max = positions[last] elements; top(p) is the sum, in
+ *   float64, of the p largest elements of that multiset.  The result does not depend on how ties are broken and is
+ *   bitwise reproducible; on integer-valued rows with totals below 2^53 it is exact.  positions_host: HOST pointer,
+ *   1 <= positions[0] < positions[1] < ... (SCAMD_EINVAL otherwise); n_positions <= 16 and positions[last] <= 4096
+ *   (SCAMD_EUNSUPPORTED beyond).  Rows of any length are handled.
+ * ---------------------------------------------------------------------------------------- */
+int scamd_pp_qc_sweep_f32(const int64_t* indptr, const int32_t* indices, const float* data, int64_t n, int64_t g,
+                          int64_t nnz, const uint32_t* gene_mask /* may be NULL */, int n_masks, int32_t* row_nnz,
+                          double* row_total, double* row_masked /* may be NULL */, int64_t* col_nnz /* may be NULL */,
+                          double* col_sum /* may be NULL */, uint32_t* flags, scamd_stream_t stream);
+int scamd_pp_qc_top_f32(const int64_t* indptr, const float* data, int64_t n, int64_t nnz, const int32_t* positions_host,
+                        int n_positions, double* top, scamd_stream_t stream);
+
+/* ------------------------------------------------------------------------------------------
  * Marker genes: the device half of tl.rank_genes_groups (reference: `_RankGenes` in
  * src/scanpy/tools/_rank_genes_groups.py -- `_aggregate_group_stats`, `_ranks`, `_tiecorrect`, `wilcoxon`; csrc/rank_genes.hip,
  * DESIGN.md 3.8).  Input: the CSC copy of the cells x genes matrix as scamd_csr_transpose_f32 writes it (t_indptr int64[g + 1],

@@ -737,6 +737,38 @@ def pp_scale_dense(indptr, indices, data, n: int, g: int, mean: torch.Tensor, st
     return out
 
 
+# ---- quality-control metrics (csrc/qc.hip) -----------------------------------------------------------------------
+def pp_qc_sweep(indptr, indices, data, n: int, g: int, *, gene_mask: torch.Tensor | None = None, n_masks: int = 0,
+                per_gene: bool = True):
+    """-> (row_nnz int32 [n], row_total float64 [n], row_masked float64 [n_masks, n] or None, col_nnz int64 [g] or None,
+    col_sum float64 [g] or None, flags int32 [1]); gene_mask: int32 [g] holding the uint32 bit masks."""
+    dev = require_gpu()
+    row_nnz = _empty(n, dtype=torch.int32, device=dev)
+    row_total = _empty(n, dtype=torch.float64, device=dev)
+    row_masked = _empty((n_masks, n), dtype=torch.float64, device=dev) if n_masks else None
+    col_nnz = _empty(g, dtype=torch.int64, device=dev) if per_gene else None
+    col_sum = _empty(g, dtype=torch.float64, device=dev) if per_gene else None
+    flags = _empty(1, dtype=torch.int32, device=dev)
+    if gene_mask is not None:
+        assert gene_mask.dtype == torch.int32 and gene_mask.numel() == g
+    rc = _lib.load().scamd_pp_qc_sweep_f32(ptr(indptr), ptr(indices), ptr(data), n, g, data.numel(), ptr(gene_mask), int(n_masks),
+                                           ptr(row_nnz), ptr(row_total), ptr(row_masked), ptr(col_nnz), ptr(col_sum), ptr(flags),
+                                           stream_ptr())
+    _check(rc, "scamd_pp_qc_sweep_f32")
+    return row_nnz, row_total, row_masked, col_nnz, col_sum, flags
+
+
+def pp_qc_top(indptr, data, n: int, positions) -> torch.Tensor:
+    """-> top float64 [n, len(positions)]: the sum of the positions[j] largest values of every row (rule: include/scanpy_amd.h)"""
+    dev = require_gpu()
+    pos = (C.c_int32 * len(positions))(*(int(p) for p in positions))
+    out = _empty((n, len(positions)), dtype=torch.float64, device=dev)
+    rc = _lib.load().scamd_pp_qc_top_f32(ptr(indptr), ptr(data), n, data.numel(), C.cast(pos, C.c_void_p), len(positions),
+                                         ptr(out), stream_ptr())
+    _check(rc, "scamd_pp_qc_top_f32")
+    return out
+
+
 # ---- UMAP layout (csrc/umap.hip) -----------------------------------------------------------------------------------
 def rank_genes_group_stats(t_indptr, t_indices, t_data, n: int, g: int, codes: torch.Tensor, n_groups: int, *,
                            expm1_scale: float | None = None):

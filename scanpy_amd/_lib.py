@@ -84,6 +84,8 @@ SIGNATURES = {
     "scamd_pp_col_stats_clip_f32": (_i32, [_vp, _vp, _vp, _i64, _i64, _i64, _vp, _vp, _vp, _vp, _vp]),
     "scamd_pp_scale_csr_f32": (_i32, [_vp, _vp, _vp, _i64, _i64, _vp, _f64, _i32, _vp, _vp]),
     "scamd_pp_scale_dense_f32": (_i32, [_vp, _vp, _vp, _i64, _i64, _i64, _vp, _vp, _f64, _i32, _vp, _vp, _i32, _vp]),
+    "scamd_pp_qc_sweep_f32": (_i32, [_vp, _vp, _vp, _i64, _i64, _i64, _vp, _i32, _vp, _vp, _vp, _vp, _vp, _vp, _vp]),
+    "scamd_pp_qc_top_f32": (_i32, [_vp, _vp, _i64, _i64, _vp, _i32, _vp, _vp]),
     "scamd_rank_genes_workspace_bytes": (_sz, [_i64, _i64, _i64, _i32]),
     "scamd_rank_genes_chunk_entries": (_i32, [_i32]),
     "scamd_rank_genes_group_stats_f32": (_i32, [_vp, _vp, _vp, _i64, _i64, _vp, _i32, _i32, _f64, _vp, _vp, _vp, _vp, _sz, _vp]),

@@ -111,6 +111,27 @@ class GpuPPBackend:
                                           expm1_scale=expm1_scale, count_positive=count_positive)
         return s.cpu().numpy(), sq.cpu().numpy(), None if npos is None else npos.cpu().numpy()
 
+    def qc_sweep(self, m: DeviceMatrix, *, gene_masks=None, positions=(), per_gene: bool = True) -> dict:
+        """The device half of `pp.calculate_qc_metrics` (csrc/qc.hip): one sweep for the per-cell and per-gene primitives,
+        one selection pass when `positions` (sorted, 1-based) are asked for.  gene_masks: bool [k, g], k <= 32.
+        -> row_nnz int64 [n], row_total float64 [n], row_masked float64 [k, n], col_nnz int64 [g] / col_sum float64 [g]
+        (None without per_gene), negative (a stored value below zero was seen), top float64 [n, len(positions)] or None."""
+        import torch
+
+        n, g = m.n_major, m.shape[1]
+        masks = np.zeros((0, g), dtype=bool) if gene_masks is None else np.asarray(gene_masks, dtype=bool).reshape(-1, g)
+        bits = None
+        if masks.shape[0]:
+            packed = (masks.astype(np.uint32) << np.arange(masks.shape[0], dtype=np.uint32)[:, None]).sum(axis=0, dtype=np.uint32)
+            bits = torch.from_numpy(packed.view(np.int32)).to(self.device)
+        nz, tot, mk, cn, cs, flags = self.K.pp_qc_sweep(m.indptr, m.indices, m.data, n, g, gene_mask=bits,
+                                                        n_masks=masks.shape[0], per_gene=per_gene)
+        top = self.K.pp_qc_top(m.indptr, m.data, n, positions).cpu().numpy() if len(positions) else None
+        return {"row_nnz": nz.cpu().numpy().astype(np.int64), "row_total": tot.cpu().numpy(),
+                "row_masked": np.zeros((0, n)) if mk is None else mk.cpu().numpy(),
+                "col_nnz": None if cn is None else cn.cpu().numpy(), "col_sum": None if cs is None else cs.cpu().numpy(),
+                "negative": bool(int(flags.cpu()[0]) & 1), "top": top}
+
     def nonnegative_integers(self, m: DeviceMatrix) -> bool:
         """`check_nonnegative_integers` (src/scanpy/_utils/__init__.py:761-773) on the stored values, on the device"""
         import torch
@@ -155,12 +176,13 @@ def default_backend():
 
 def in_memory(x):
     """The upstream chain works on a matrix in memory (most of its passes rewrite it); an on-disk matrix
-    (`read_h5ad` / `read_zarr(..., backed='r')`) streams through `pp.pca` and `pp.highly_variable_genes`;
+    (`read_h5ad` / `read_zarr(..., backed='r')`) streams through `pp.pca`, `pp.highly_variable_genes` and
+    `pp.calculate_qc_metrics`;
     `pp.normalize_total` / `pp.log1p` turn into pending transforms of it."""
     if getattr(x, "is_backed", False):
         raise NotImplementedError(
             "this function needs the matrix in memory: load it with `adata.X = adata.X.to_memory()` (or read without "
-            "backed='r'); on a backed matrix only normalize_total, log1p, highly_variable_genes and pca are offered")
+            "backed='r'); on a backed matrix only calculate_qc_metrics, normalize_total, log1p, highly_variable_genes and pca are offered")
     return x
 
 
