@@ -398,9 +398,12 @@ int scamd_leiden_csr_nw_f32(const int64_t* indptr, const int32_t* indices, const
  *   levels_reused / quiet_reuse_iterations: levels that took their coarse graph from the stored hierarchy / iterations that
  *       ran on it to its end without a move; overflow_pass_vertices / hub_pass_vertices: rows too long for the main tier of
  *       a 16- / 32-lane decide launch / rows longer than the wave table (block and giant tier together; see
- *       scamd_leiden_tier_bounds). */
+ *       scamd_leiden_tier_bounds);
+ *   out[14], which has no key: walks of the level-0 graph for a quality (after a polish pass that moved something, of a given
+ *       start partition, for the modularity report of a CPM run).  A run from singletons needs none for its iterations: their
+ *       quality is taken from the last level of each. */
 void scamd_leiden_last_stats(int32_t* out, int n);
-/* Key of statistics slot `slot` (a static string); NULL for the unused slot 14 and outside [0, 20). */
+/* Key of statistics slot `slot` (a static string); NULL for slot 14, which has none, and outside [0, 20). */
 const char* scamd_leiden_stat_name(int slot);
 /* The longest rows the tiers of a Leiden decide step take when its main tier gives a vertex `lanes` (16, 32 or 64) lanes: up
  * to *main_max entries the main tier, up to *wave_max a wave per row, up to *block_max a 256-thread workgroup per row inside

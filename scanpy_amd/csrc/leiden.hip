@@ -41,6 +41,10 @@ namespace scamd {
 //   ST_LEVELS_REUSED               levels that took their coarse graph from the stored hierarchy (StoredLevel) instead of
 //                                   refining and aggregating
 //   ST_QUIET_REUSE_ITERS           iterations that ran on the stored hierarchy to its end without a move at any level
+//   ST_L0_QUALITY_WALKS            launches of ld_internal_kernel over the level-0 graph (the quality after a polish pass, of a
+//                                   given start partition, of an iteration that ended on level 0, the modularity report of a
+//                                   CPM run); slot 14 has no key: the key
+//                                   set is part of the Python layers' dicts, the slot is read by its number
 //   ST_OVERFLOW_VERTICES / ST_HUB_VERTICES  rows too long for the main tier of a 16- / 32-lane decide launch (the wave-per-row
 //                                   tier takes them, or a workgroup tier) / rows longer than the wave table: block tier and
 //                                   giant tier together (decide_tiers: local moving, polish and refinement together; the
@@ -48,10 +52,10 @@ namespace scamd {
 enum LdStat : int {
   ST_ITERATIONS = 0, ST_LAUNCHES, ST_ROUND_TRIPS, ST_POLISH_FULL_SWEEPS, ST_POLISH_ROUNDS, ST_POLISH_MOVES,
   ST_POLISH_SKIPPED_PROVEN, ST_LEVELS_FIRST_ITER, ST_LM_SWEEPS, ST_LM_SWEEP_MB, ST_POLISH_SPLITS, ST_ENDED_BY_ITER_CAP,
-  ST_POLISH_ROUND_CAP, ST_ITER_CAP, ST_UNUSED_14, ST_DEVICE_FILLS, ST_LEVELS_REUSED, ST_QUIET_REUSE_ITERS,
+  ST_POLISH_ROUND_CAP, ST_ITER_CAP, ST_L0_QUALITY_WALKS, ST_DEVICE_FILLS, ST_LEVELS_REUSED, ST_QUIET_REUSE_ITERS,
   ST_OVERFLOW_VERTICES, ST_HUB_VERTICES, LD_NSTATS
 };
-static_assert(LD_NSTATS == 20 && ST_UNUSED_14 == 14, "the slot numbers are part of the C ABI (scamd_leiden_last_stats)");
+static_assert(LD_NSTATS == 20 && ST_L0_QUALITY_WALKS == 14, "the slot numbers are part of the C ABI (scamd_leiden_last_stats)");
 struct LdStatName {
   int slot;
   const char* key;
@@ -153,11 +157,37 @@ __device__ __forceinline__ long long readlane_i64(long long v, int l) {
 }
 
 // ---- small utility kernels -----------------------------------------------------------------------
-__global__ void ld_quantize_kernel(const float* __restrict__ w, int64_t nnz, long long* __restrict__ wq) {
-  int64_t e = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
-  if (e < nnz) {
-    double v = (double)w[e];
-    wq[e] = (v > 0.0) ? (long long)llrint(v * WSCALE) : 0ll;
+// Level 0 in one pass over the graph, sixteen lanes per row (four rows in flight per wave): wq = the weights in fixed point
+// (llrint(w * 2^32), 0 for w <= 0: what ld_quantize_kernel did in a pass of its own),
+// k[v] = sum of row v, diag[0] += the stored diagonal entries (the internal weight of the singleton partition; zeroed by the
+// caller; integer: order free)
+__global__ __launch_bounds__(256) void ld_level0_setup_kernel(const int64_t* __restrict__ indptr, const int* __restrict__ indices,
+                                                              const float* __restrict__ w, int n, long long* __restrict__ wq,
+                                                              long long* __restrict__ k, unsigned long long* __restrict__ diag) {
+  const int lane = threadIdx.x & 63, sub = threadIdx.x & 15;
+  const int v = blockIdx.x * 16 + (threadIdx.x >> 4);
+  long long s = 0, d = 0;
+  if (v < n) {
+    const int64_t end = indptr[v + 1];
+    for (int64_t e = indptr[v] + sub; e < end; e += 16) {
+      const double x = (double)w[e];
+      const long long q = (x > 0.0) ? (long long)llrint(x * WSCALE) : 0ll;
+      wq[e] = q;
+      s += q;
+      if (indices[e] == v) d += q;
+    }
+  }
+#pragma unroll
+  for (int o = 8; o > 0; o >>= 1) s += __shfl_xor(s, o);
+  if (v < n && sub == 0) k[v] = s;
+#pragma unroll
+  for (int o = 32; o > 0; o >>= 1) d += __shfl_xor(d, o);
+  __shared__ long long sh_d[4];
+  if (lane == 0) sh_d[threadIdx.x >> 6] = d;
+  __syncthreads();
+  if (threadIdx.x == 0) {
+    const long long tot = sh_d[0] + sh_d[1] + sh_d[2] + sh_d[3];
+    if (tot != 0) atomicAdd(diag, (unsigned long long)tot);
   }
 }
 
@@ -2057,6 +2087,10 @@ struct SmallArgs {
   int lm_stop_permille;
   int seq_n;               // levels of at most this many vertices move one vertex at a time
   int* info;               // counters + PH_SMALL_INFO: [SM_INFO_LEVELS], [SM_INFO_MOVES], [SM_INFO_MERGES], [SM_INFO_NODES] of the last level
+  // what the quality of the result needs, taken from the last level: totals[c], c < n, = the total vertex weight of
+  // community c of the last level (0 from its vertex count on), internal[0] = the weight of its stored entries inside a community
+  unsigned long long* totals;
+  unsigned long long* internal;
 };
 
 struct SmallLds {
@@ -2092,6 +2126,7 @@ struct SmallLds {
   int rset[SM_WAVES];
   int scan_w[SM_WAVES];
   int s_n_act, s_moved, s_merged, s_nn;
+  unsigned long long s_internal;
 };
 static_assert(sizeof(SmallLds) <= 160 * 1024, "SmallLds must fit the 160 KB of LDS");
 
@@ -2507,7 +2542,28 @@ __global__ __launch_bounds__(SM_THREADS) void ld_small_levels_kernel(SmallArgs a
   }
   __syncthreads();
   for (int i = t; i < n_in; i += SM_THREADS) a.comm[i] = L.comm[L.tail_of[i]];
+  // ---- the last level's community totals and internal weight.  Coarse graphs are P^T W P entry for entry and all weights are
+  // integers: these ARE the totals and the internal weight of the partition just written, on the entry graph and on level 0.
+  for (int c = t; c < n_in; c += SM_THREADS) L.Ktot[c] = 0ull;
+  if (t == 0) L.s_internal = 0ull;
+  __syncthreads();
+  for (int v = t; v < n; v += SM_THREADS) atomicAdd(&L.Ktot[L.comm[v]], (unsigned long long)L.kk[v]);
+  for (int v0 = 0; v0 < n; v0 += SM_WAVES) {
+    const int v = v0 + wv;
+    if (v < n) {
+      const int ca = L.comm[v];
+      long long s = 0;
+      for (int e = L.ip[v] + lane; e < L.ip[v + 1]; e += 64)
+        if (L.comm[ix[e]] == ca) s += wq[e];  // (self entries included)
+#pragma unroll
+      for (int o = 32; o > 0; o >>= 1) s += __shfl_xor(s, o);
+      if (lane == 0 && s != 0) atomicAdd(&L.s_internal, (unsigned long long)s);
+    }
+  }
+  __syncthreads();
+  for (int c = t; c < n_in; c += SM_THREADS) a.totals[c] = L.Ktot[c];
   if (t == 0) {
+    a.internal[0] = L.s_internal;
     a.info[SM_INFO_LEVELS] = levels;
     a.info[SM_INFO_MOVES] = tot_moves;
     a.info[SM_INFO_MERGES] = tot_merges;
@@ -2799,7 +2855,11 @@ struct IterHierarchy {
   int built = 0;       // its levels 1 .. built sit in the pool one behind the other (-1: a level did not fit)
   int end_level = -1, end_kind = 0;
   bool quiet = false;  // it ran on the stored hierarchy to its end and no separate-kernel level moved anything
-  int small_moves = 0; // moves inside ld_small_levels_kernel (fetched when quiet, handed out by evaluate()'s sync)
+  int small_moves = 0; // moves inside ld_small_levels_kernel (fetched when quiet, handed out by the sync of iteration_quality())
+  // the pair (graph, partition in b.comm) the iteration ended on; in_small: inside ld_small_levels_kernel, which has left the
+  // totals of its last level in b.Ktot[0 .. top.n) and the internal weight in b.total[1] (top: the level it was entered at)
+  LevelGraph top{};
+  bool in_small = false;
   // what the stored hierarchy is once the iteration's partition has been accepted as b.memb: what it built or reused
   Hierarchy accepted() const { return Hierarchy{std::max(built, 0), end_level, end_kind}; }
 };
@@ -2823,6 +2883,7 @@ struct LeidenCtx {
   double inv_beta = 0.0;  // 1 / (beta * 2^32): randomness of the refinement's merge rule (0 = greedy)
   int iter = 0;           // outer iteration: part of the refinement's noise seed
   unsigned int seed;
+  unsigned long long diag0 = 0;  // sum of the stored diagonal entries of level 0: the internal weight of the singleton partition
   int l0_moves = -1;          // moves of the last iteration's level-0 local moving (0: its input was node optimal)
   int n_levels = 0;           // levels the last iteration went through
   // ---- the SCAMD_LEIDEN_* switches, all read by read_knobs() once per call (tools and tests flip them inside one process) ----
@@ -2947,7 +3008,27 @@ static int compute_totals(LeidenCtx& cx, const LevelGraph& g, const int* comm, F
 
 // quality of `comm` on level graph g (needs Ktot up to date): modularity, or the CPM objective in the same units
 // (b.total[1], the accumulator of the internal weight, was zeroed by the ld_totals_kernel launch of compute_totals)
+// the quality from its two sums: `totals[0 .. n)` the total vertex weight per community (zeros add exactly nothing: the sum
+// over the slots of a coarse level is bit for bit the sum over the level-0 array, whose other slots are empty), and the
+// internal weight -- `internal_host`, or b.total[1] when that is NULL.  One synchronisation.
+static int quality_from_sums(LeidenCtx& cx, int n, const unsigned long long* totals, const unsigned long long* internal_host, double* q) {
+  // (CPM: sum of squared community SIZES, unnormalised)
+  hipLaunchKernelGGL(ld_sumsq_kernel, dim3(SUMSQ_BLOCKS), dim3(1024), 0, cx.s, n, totals, cx.cpm ? cx.nw_scale : cx.m2, cx.b.dscratch + 4);
+  SCAMD_LAUNCH_CHECK();
+  hipLaunchKernelGGL(ld_sumsq_final_kernel, dim3(1), dim3(1024), 0, cx.s, cx.b.dscratch + 4, cx.b.dscratch);
+  SCAMD_LAUNCH_CHECK();
+  unsigned long long internal = internal_host ? *internal_host : 0ull;
+  double sumsq = 0;
+  if (!internal_host) LD_FETCH(&internal, cx.b.total + 1, sizeof(internal), cx.s);
+  LD_FETCH(&sumsq, cx.b.dscratch, sizeof(double), cx.s);
+  LD_SYNC(cx.s);
+  *q = cx.cpm ? ((double)(long long)internal - cx.gamma * WSCALE * sumsq) / cx.m2
+              : (double)(long long)internal / cx.m2 - cx.gamma * sumsq;
+  return SCAMD_OK;
+}
+
 static int quality(LeidenCtx& cx, const LevelGraph& g, const int* comm, double* q) {
+  if (g.wq == cx.b.wq0) ++g_ld_stats[ST_L0_QUALITY_WALKS];
   // (a group walks its vertices one after the other, three dependent loads each: the more groups, the fewer steps of that
   // walk -- and one same-word atomic per workgroup at the end)
   constexpr int qgrid = 2048;
@@ -2957,19 +3038,7 @@ static int quality(LeidenCtx& cx, const LevelGraph& g, const int* comm, double* 
                        g.indptr, g.indices, g.wq, comm, cx.b.total + 1);
   });
   SCAMD_LAUNCH_CHECK();
-  // (CPM: sum of squared community SIZES, unnormalised)
-  hipLaunchKernelGGL(ld_sumsq_kernel, dim3(SUMSQ_BLOCKS), dim3(1024), 0, cx.s, g.n, cx.b.Ktot, cx.cpm ? cx.nw_scale : cx.m2, cx.b.dscratch + 4);
-  SCAMD_LAUNCH_CHECK();
-  hipLaunchKernelGGL(ld_sumsq_final_kernel, dim3(1), dim3(1024), 0, cx.s, cx.b.dscratch + 4, cx.b.dscratch);
-  SCAMD_LAUNCH_CHECK();
-  unsigned long long internal = 0;
-  double sumsq = 0;
-  LD_FETCH(&internal, cx.b.total + 1, sizeof(internal), cx.s);
-  LD_FETCH(&sumsq, cx.b.dscratch, sizeof(double), cx.s);
-  LD_SYNC(cx.s);
-  *q = cx.cpm ? ((double)(long long)internal - cx.gamma * WSCALE * sumsq) / cx.m2
-              : (double)(long long)internal / cx.m2 - cx.gamma * sumsq;
-  return SCAMD_OK;
+  return quality_from_sums(cx, g.n, cx.b.Ktot, nullptr, q);
 }
 
 // Ktot / csize and the quality of `comm` on g
@@ -3594,7 +3663,7 @@ static int small_levels(LeidenCtx& cx, const LevelGraph& g, int level) {
   int* info = b.counters + PH_SMALL_INFO;
   // (first_dst = 0: the entry level lives in the pool or is the caller's graph)
   const SmallArgs a{g.indptr, g.indices, g.wq, g.k, g.n, {b.sm_ix[0], b.sm_ix[1]}, {b.sm_w[0], b.sm_w[1]}, /*first_dst=*/0, b.comm,
-                    cx.gscale(), cx.inv_beta, cx.seed, cx.iter, LM_STOP_PERMILLE, SMALL_SEQ_N, info};
+                    cx.gscale(), cx.inv_beta, cx.seed, cx.iter, LM_STOP_PERMILLE, SMALL_SEQ_N, info, b.Ktot, b.total + 1};
   hipLaunchKernelGGL(ld_small_levels_kernel, dim3(1), dim3(SM_THREADS), sizeof(SmallLds), cx.s, a);
   SCAMD_LAUNCH_CHECK();
   if (cx.debug) {
@@ -3630,7 +3699,8 @@ static int leiden_iteration(LeidenCtx& cx, const LevelGraph& g0) {
       if (rcs != SCAMD_OK) return rcs;
       tr.say("[leiden] small levels %.2f ms\n", tr.lap());
       cx.it.end_level = level;
-      if (quiet && level >= 1 && reused == level) {  // (its move count: handed out by the synchronisation of the evaluate() that follows)
+      cx.it.in_small = true;
+      if (quiet && level >= 1 && reused == level) {  // (its move count: handed out by the synchronisation of iteration_quality())
         cx.it.quiet = true;
         LD_FETCH(&cx.it.small_moves, b.counters + PH_SMALL_INFO + SM_INFO_MOVES, sizeof(int), cx.s);
       }
@@ -3685,9 +3755,19 @@ static int leiden_iteration(LeidenCtx& cx, const LevelGraph& g0) {
     cx.it.end_level = -1;
     g = gn;
   }
+  cx.it.top = g;
   hipLaunchKernelGGL(ld_gather_kernel, GRID1(g0.n), 0, cx.s, g0.n, b.comm, b.node_of, b.memb_work);
   SCAMD_LAUNCH_CHECK();
   return SCAMD_OK;
+}
+
+// Quality of the partition leiden_iteration() has just written to b.memb_work, from the level it ended on instead of a walk
+// over level 0: b.memb_work = comm_top[node_of] and every coarse graph is P^T W P in integers, so the internal weight and the
+// community totals of (top level, b.comm) are those of (level 0, b.memb_work) -- the same integers, and the same float64 sum
+// of squares (quality_from_sums).
+static int iteration_quality(LeidenCtx& cx, double* q) {
+  if (cx.it.in_small) return quality_from_sums(cx, cx.it.top.n, cx.b.Ktot, nullptr, q);
+  return evaluate(cx, cx.it.top, cx.b.comm, q);
 }
 
 // b.memb (values < n) relabelled to consecutive ids ordered by (size desc, first member asc) -> out (the caller's buffer)
@@ -3724,15 +3804,12 @@ static int renumber(LeidenCtx& cx, int n, int* n_comm, int* out) {
 static int setup_level0(LeidenCtx& cx, const int64_t* indptr, const int32_t* indices, const float* weights, int64_t n,
                         int64_t nnz, LevelGraph* g0) {
   LeidenBuffers& b = cx.b;
-  if (nnz > 0) {
-    hipLaunchKernelGGL(ld_quantize_kernel, dim3((unsigned)ceil_div(nnz, 256)), dim3(256), 0, cx.s, weights, nnz, b.wq0);
-    SCAMD_LAUNCH_CHECK();
-  }
   {
     const int rcf = run_fill(cx, Filler().add(b.total, sizeof(unsigned long long) * 4).add(b.counters, sizeof(int) * 16));
     if (rcf != SCAMD_OK) return rcf;
   }
-  hipLaunchKernelGGL(ld_strength_kernel, GRIDW(n), 0, cx.s, indptr, b.wq0, (int)n, b.k0);
+  hipLaunchKernelGGL(ld_level0_setup_kernel, dim3((unsigned)ceil_div(n, 16)), dim3(256), 0, cx.s, indptr, indices, weights, (int)n,
+                     b.wq0, b.k0, b.total + 2);
   SCAMD_LAUNCH_CHECK();
   hipLaunchKernelGGL(ld_sum_kernel, dim3(256), dim3(256), 0, cx.s, b.k0, (int)n, b.total);
   SCAMD_LAUNCH_CHECK();
@@ -3742,6 +3819,7 @@ static int setup_level0(LeidenCtx& cx, const int64_t* indptr, const int32_t* ind
   int max_deg = 0;
   LD_FETCH(&tot, b.total, sizeof(tot), cx.s);
   LD_FETCH(&max_deg, b.counters + PH_MAX_DEG, sizeof(int), cx.s);
+  LD_FETCH(&cx.diag0, b.total + 2, sizeof(cx.diag0), cx.s);
   LD_SYNC(cx.s);
   cx.m2 = (double)tot;
   *g0 = LevelGraph{(int)n, max_deg, nnz, indptr, indices, b.wq0, b.k0};
@@ -3799,7 +3877,7 @@ static int accept_iteration(LeidenCtx& cx, const LevelGraph& g0, int it, double*
   g_ld_stats[ST_ITERATIONS] = it + 1;
   double q = 0.0;
   int rc = leiden_iteration(cx, g0);
-  if (rc == SCAMD_OK) rc = evaluate(cx, g0, b.memb_work, &q);
+  if (rc == SCAMD_OK) rc = iteration_quality(cx, &q);
   if (rc != SCAMD_OK) return rc;
   if (cx.debug) fprintf(stderr, "[leiden] iteration %d: Q = %.10f (best before %.10f), level-0 moves %d\n", it, q, *q_best, cx.l0_moves);
   if (cx.it.quiet && cx.it.small_moves == 0) ++g_ld_stats[ST_QUIET_REUSE_ITERS];
@@ -3865,7 +3943,9 @@ static int leiden_run(const LeidenCall& c) {
   }
   double q_best = 0.0;
   if (cx.m2 > 0.0) {
-    rc = evaluate(cx, g0, b.memb, &q_best);
+    // (singletons: the totals are the vertex weights themselves, the internal weight is the stored diagonal)
+    rc = c.initial_membership ? evaluate(cx, g0, b.memb, &q_best)
+                              : quality_from_sums(cx, g0.n, reinterpret_cast<const unsigned long long*>(g0.k), &cx.diag0, &q_best);
     if (rc != SCAMD_OK) return rc;
     // b.memb is ALWAYS the best partition seen (the input of the next iteration); an iteration writes into b.memb_work and
     // the two change places when it improved -- no copies (round 5: two 4-byte-per-vertex blits per iteration)
