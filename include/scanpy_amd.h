@@ -526,6 +526,39 @@ int scamd_pp_qc_top_f32(const int64_t* indptr, const float* data, int64_t n, int
                         int n_positions, double* top, scamd_stream_t stream);
 
 /* ------------------------------------------------------------------------------------------
+ * Regressing out observation annotations: the device half of pp.regress_out (reference: `regress_out`,
+ * `numpy_regress_out`, `_create_regressor_categorical`, `_regress_out_chunk` in src/scanpy/preprocessing/_simple.py:468-681;
+ * csrc/regress.hip).  Input as for the normalisation chain: canonical CSR float32 on the device (no column
+ * twice in a row), a dense matrix as the full pattern; an implicit zero is the value 0.  Both branches of the reference are
+ * one model, out[i, j] = x_ij - sum_k W[i, k] * T[k, j], with m table rows:
+ *   numeric keys (w given, codes NULL):     w float64 [n x m] row-major, m <= 17 (the ones and 16 keys);
+ *   a categorical key (codes given, w NULL): codes int32 [n], 0 <= code < m <= 65536; W is the one-hot of the code.
+ * Exactly one of w / codes (SCAMD_EINVAL otherwise); more rows than that: SCAMD_EUNSUPPORTED.  g < 2^31.  Arguments are
+ * checked before any HIP call and a rejected call writes nothing; n = 0 and g = 0 are legal.
+ *
+ * scamd_pp_regress_sums_f32: sums [m x g] (row-major, float64) = W^T X; col_min / col_max [g] = the smallest / largest
+ *   value of every gene over all n cells, implicit zeros included (both 0 for n = 0); flags [1]: bit 0 = a stored value
+ *   was not finite (such values take part in nothing), bit 1 = a code outside [0, m) (such rows take part in nothing);
+ *   zeroed here.  wbound float64 [m] (device): wbound[k] >= sum_i |W[i, k]| -- n for a column of ones, the number of cells
+ *   of category k.  Every term is rounded once to 64-bit fixed point at the scale 2^62 / (2^ew 2^ea), 2^ew > wbound[k],
+ *   2^ea > max_i |x_ij|, and added with integer atomics: the result does not depend on the order of addition and is
+ *   bitwise reproducible.  |sums[k, j] - exact| <= (n 2^-61 + 2^-52) wbound[k] max_i |x_ij|.  A wbound that is too small
+ *   makes the sums of that row meaningless (nothing else).  Workspace: scamd_pp_regress_workspace_bytes(g, m).
+ * scamd_pp_regress_resid_f32: out [n x g] row-major, float64 (out_is_f64 != 0) or float32:
+ *   out[i, j] = x_ij - sum_k W[i, k] table[k, j] computed in float64 (k ascending) and rounded once, for the genes with
+ *   keep[j] != 0; x_ij for the others.  table float64 [m x g].  One pass; every element is written exactly once.
+ * ---------------------------------------------------------------------------------------- */
+size_t scamd_pp_regress_workspace_bytes(int64_t g, int32_t m);
+int scamd_pp_regress_sums_f32(const int64_t* indptr, const int32_t* indices, const float* data, int64_t n, int64_t g,
+                              int64_t nnz, const double* w /* or NULL */, const int32_t* codes /* or NULL */, int32_t m,
+                              const double* wbound, double* sums, float* col_min, float* col_max, uint32_t* flags,
+                              void* workspace, size_t workspace_bytes, scamd_stream_t stream);
+int scamd_pp_regress_resid_f32(const int64_t* indptr, const int32_t* indices, const float* data, int64_t n, int64_t g,
+                               int64_t nnz, const uint8_t* keep, const double* table, const double* w /* or NULL */,
+                               const int32_t* codes /* or NULL */, int32_t m, void* out, int out_is_f64,
+                               scamd_stream_t stream);
+
+/* ------------------------------------------------------------------------------------------
  * Marker genes: the device half of tl.rank_genes_groups (reference: `_RankGenes` in
  * src/scanpy/tools/_rank_genes_groups.py -- `_aggregate_group_stats`, `_ranks`, `_tiecorrect`, `wilcoxon`; csrc/rank_genes.hip,
  * DESIGN.md 3.8).  Input: the CSC copy of the cells x genes matrix as scamd_csr_transpose_f32 writes it (t_indptr int64[g + 1],

@@ -769,6 +769,52 @@ def pp_qc_top(indptr, data, n: int, positions) -> torch.Tensor:
     return out
 
 
+# ---- regress_out (csrc/regress.hip) --------------------------------------------------------------------------------
+def _regress_model(n: int, w, codes, m: int):
+    assert (w is None) != (codes is None), "exactly one of w (numeric keys) and codes (a categorical key)"
+    if w is not None:
+        assert w.dtype == torch.float64 and w.is_contiguous() and tuple(w.shape) == (n, m)
+    else:
+        assert codes.dtype == torch.int32 and codes.numel() == n
+
+
+def pp_regress_sums(indptr, indices, data, n: int, g: int, *, w: torch.Tensor | None = None, codes: torch.Tensor | None = None,
+                    m: int, wbound: torch.Tensor):
+    """-> (sums float64 [m, g] = W^T X in order-independent fixed point, col_min float32 [g], col_max float32 [g] over all n
+    cells, flags int32 [1]: bit 0 a stored value was not finite, bit 1 a code outside [0, m)); W: include/scanpy_amd.h"""
+    dev = require_gpu()
+    lib = _lib.load()
+    _regress_model(n, w, codes, m)
+    assert wbound.dtype == torch.float64 and wbound.numel() == m
+    sums = _empty((m, g), dtype=torch.float64, device=dev)
+    col_min = _empty(g, dtype=torch.float32, device=dev)
+    col_max = _empty(g, dtype=torch.float32, device=dev)
+    flags = _empty(1, dtype=torch.int32, device=dev)
+    nbytes = int(lib.scamd_pp_regress_workspace_bytes(g, m))
+    ws = _empty(max(nbytes, 1), dtype=torch.uint8, device=dev)
+    rc = lib.scamd_pp_regress_sums_f32(ptr(indptr), ptr(indices), ptr(data), n, g, data.numel(), ptr(w), ptr(codes), int(m),
+                                       ptr(wbound), ptr(sums), ptr(col_min), ptr(col_max), ptr(flags), ptr(ws), nbytes, stream_ptr())
+    _check(rc, "scamd_pp_regress_sums_f32")
+    return sums, col_min, col_max, flags
+
+
+def pp_regress_resid(indptr, indices, data, n: int, g: int, keep: torch.Tensor, table: torch.Tensor, *,
+                     w: torch.Tensor | None = None, codes: torch.Tensor | None = None,
+                     out_dtype: torch.dtype = torch.float64) -> torch.Tensor:
+    """-> out [n, g]: x - W @ table in float64, rounded once to out_dtype, for the genes with keep != 0; x for the others"""
+    dev = require_gpu()
+    m = int(table.shape[0])
+    _regress_model(n, w, codes, m)
+    assert table.dtype == torch.float64 and table.is_contiguous() and tuple(table.shape) == (m, g)
+    assert keep.dtype == torch.uint8 and keep.numel() == g and out_dtype in (torch.float32, torch.float64)
+    out = _empty((n, g), dtype=out_dtype, device=dev)
+    rc = _lib.load().scamd_pp_regress_resid_f32(ptr(indptr), ptr(indices), ptr(data), n, g, data.numel(), ptr(keep), ptr(table),
+                                                ptr(w), ptr(codes), m, ptr(out), 1 if out_dtype == torch.float64 else 0,
+                                                stream_ptr())
+    _check(rc, "scamd_pp_regress_resid_f32")
+    return out
+
+
 # ---- UMAP layout (csrc/umap.hip) -----------------------------------------------------------------------------------
 def rank_genes_group_stats(t_indptr, t_indices, t_data, n: int, g: int, codes: torch.Tensor, n_groups: int, *,
                            expm1_scale: float | None = None):

@@ -86,6 +86,9 @@ SIGNATURES = {
     "scamd_pp_scale_dense_f32": (_i32, [_vp, _vp, _vp, _i64, _i64, _i64, _vp, _vp, _f64, _i32, _vp, _vp, _i32, _vp]),
     "scamd_pp_qc_sweep_f32": (_i32, [_vp, _vp, _vp, _i64, _i64, _i64, _vp, _i32, _vp, _vp, _vp, _vp, _vp, _vp, _vp]),
     "scamd_pp_qc_top_f32": (_i32, [_vp, _vp, _i64, _i64, _vp, _i32, _vp, _vp]),
+    "scamd_pp_regress_workspace_bytes": (_sz, [_i64, _i32]),
+    "scamd_pp_regress_sums_f32": (_i32, [_vp, _vp, _vp, _i64, _i64, _i64, _vp, _vp, _i32, _vp, _vp, _vp, _vp, _vp, _vp, _sz, _vp]),
+    "scamd_pp_regress_resid_f32": (_i32, [_vp, _vp, _vp, _i64, _i64, _i64, _vp, _vp, _vp, _vp, _i32, _vp, _i32, _vp]),
     "scamd_rank_genes_workspace_bytes": (_sz, [_i64, _i64, _i64, _i32]),
     "scamd_rank_genes_chunk_entries": (_i32, [_i32]),
     "scamd_rank_genes_group_stats_f32": (_i32, [_vp, _vp, _vp, _i64, _i64, _vp, _i32, _i32, _f64, _vp, _vp, _vp, _vp, _sz, _vp]),

@@ -169,6 +169,40 @@ class GpuPPBackend:
                                     row_mask=mask, out_dtype=torch.float64 if out_f64 else torch.float32)
         return out.cpu().numpy()
 
+    def _regress_model(self, w, codes):
+        import torch
+
+        wd = None if w is None else torch.from_numpy(np.ascontiguousarray(w, dtype=np.float64)).to(self.device)
+        cd = None if codes is None else torch.from_numpy(np.ascontiguousarray(codes, dtype=np.int32)).to(self.device)
+        return wd, cd
+
+    def regress_sums(self, m: DeviceMatrix, *, w=None, codes=None, n_table: int, wbound: np.ndarray) -> dict:
+        """The first device half of `pp.regress_out` (csrc/regress.hip): W^T X for W = `w` (float64 [n, n_table]) or the
+        one-hot of `codes` (int32 [n], n_table categories); wbound[k] >= sum_i |W[i, k]|.
+        -> sums float64 [n_table, g], col_min / col_max float32 [g] over all cells (implicit zeros included),
+        nonfinite (a stored value was NaN or infinite), bad_code (a code outside [0, n_table))."""
+        import torch
+
+        wd, cd = self._regress_model(w, codes)
+        wb = torch.from_numpy(np.ascontiguousarray(wbound, dtype=np.float64)).to(self.device)
+        s, lo, hi, flags = self.K.pp_regress_sums(m.indptr, m.indices, m.data, m.n_major, m.shape[1], w=wd, codes=cd,
+                                                  m=int(n_table), wbound=wb)
+        f = int(flags.cpu()[0])
+        return {"sums": s.cpu().numpy(), "col_min": lo.cpu().numpy(), "col_max": hi.cpu().numpy(),
+                "nonfinite": bool(f & 1), "bad_code": bool(f & 2)}
+
+    def regress_resid(self, m: DeviceMatrix, table: np.ndarray, keep: np.ndarray, *, w=None, codes=None,
+                      out_f64: bool = True) -> np.ndarray:
+        """The second half: the dense x - W @ table (float64 arithmetic, rounded once) for the genes with keep, x for the others"""
+        import torch
+
+        wd, cd = self._regress_model(w, codes)
+        t = torch.from_numpy(np.ascontiguousarray(table, dtype=np.float64)).to(self.device)
+        kp = torch.from_numpy(np.ascontiguousarray(keep, dtype=np.uint8)).to(self.device)
+        out = self.K.pp_regress_resid(m.indptr, m.indices, m.data, m.n_major, m.shape[1], kp, t, w=wd, codes=cd,
+                                      out_dtype=torch.float64 if out_f64 else torch.float32)
+        return out.cpu().numpy()
+
 
 def default_backend():
     return GpuPPBackend()
