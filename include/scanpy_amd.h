@@ -559,6 +559,44 @@ int scamd_pp_regress_resid_f32(const int64_t* indptr, const int32_t* indices, co
                                scamd_stream_t stream);
 
 /* ------------------------------------------------------------------------------------------
+ * Scrublet: the device passes of pp.scrublet / pp.scrublet_simulate_doublets that are not PCA, projection or kNN (reference:
+ * `Scrublet.simulate_doublets`, `_nearest_neighbor_classifier` in src/scanpy/preprocessing/_scrublet/core.py; csrc/scrublet.hip,
+ * DESIGN.md 3.12).  Arguments are checked before any HIP call and a rejected call writes nothing.
+ *
+ * ROW-PAIR SUMS, a two-phase protocol.  Input: canonical CSR float32 on the device (sorted, unique columns; n, g, n_sim < 2^31,
+ * SCAMD_EUNSUPPORTED beyond), pairs int32 [n_sim x 2] with values in [0, n).  Output row r is row pairs[r, 0] + row pairs[r, 1]:
+ * the sorted union of their columns, values added where both store the column (the float32 sum), nothing dropped for being
+ * zero.  A pair (i, i) gives row i doubled.  No atomics: the output is a pure function of the input, bit for bit.
+ *   1. scamd_pp_scrublet_pair_count: out_indptr int64 [n_sim + 1] (device) = the exclusive scan of the output row lengths;
+ *      *out_nnz (HOST) = out_indptr[n_sim], by one pinned read-back (the call synchronises the stream); total_sim [n_sim] =
+ *      row_total[a] + row_total[b], float64 (row_total_is_f64 != 0) or float32 like row_total [n].
+ *      Workspace: scamd_pp_scrublet_workspace_bytes(n_sim).
+ *   2. scamd_pp_scrublet_pair_fill_f32: the caller allocates out_indices int32 / out_data float32 [out_nnz] and passes the
+ *      out_indptr of phase 1; every element is written exactly once.
+ * flags [1] (device, zeroed by each phase): bit 0 = an output value above 2^24 in magnitude (sums of integer counts are exact in
+ * float32 up to there; phase 2), bit 1 = a pair outside [0, n) or a row pointer outside [0, nnz]: that output row is empty,
+ * bit 2 = an output position outside [0, out_nnz): out_indptr does not belong to these inputs, nothing is written there.
+ * n_sim = 0 is legal (out_indptr[0] = 0).
+ *
+ * scamd_scrublet_scores_f64: idx int32 [n_all x k] = the neighbour lists of the concatenated manifold, observed rows first (the
+ * layout scamd_knn_l2_f32 writes; the self column counts).  n_sim_neigh[i] = |{j : idx[i, j] >= n_obs}|; with nd that count,
+ * N = k:  q = (nd + 1) / (N + 2),  score = q rho / r / (1 - rho - q (1 - rho - rho / r)),
+ * se_q = sqrt(q (1 - q) / (N + 3)),  score_err = q rho / r / (1 - rho - q (1 - rho - rho / r))^2 *
+ * sqrt((se_q / q (1 - rho))^2 + (se_rho / rho (1 - q))^2): float64, in the reference's operation order (the bits numpy gives).
+ * 0 <= n_obs <= n_all < 2^31, k >= 1.
+ * ---------------------------------------------------------------------------------------- */
+size_t scamd_pp_scrublet_workspace_bytes(int64_t n_sim);
+int scamd_pp_scrublet_pair_count(const int64_t* indptr, const int32_t* indices, int64_t n, int64_t g, int64_t nnz,
+                                 const int32_t* pairs, int64_t n_sim, const void* row_total, int row_total_is_f64,
+                                 int64_t* out_indptr, void* total_sim, uint32_t* flags, int64_t* out_nnz /* host */,
+                                 void* workspace, size_t workspace_bytes, scamd_stream_t stream);
+int scamd_pp_scrublet_pair_fill_f32(const int64_t* indptr, const int32_t* indices, const float* data, int64_t n, int64_t g,
+                                    int64_t nnz, const int32_t* pairs, int64_t n_sim, const int64_t* out_indptr, int64_t out_nnz,
+                                    int32_t* out_indices, float* out_data, uint32_t* flags, scamd_stream_t stream);
+int scamd_scrublet_scores_f64(const int32_t* idx, int64_t n_all, int32_t k, int64_t n_obs, double rho, double r, double se_rho,
+                              int32_t* n_sim_neigh, double* score, double* score_err, scamd_stream_t stream);
+
+/* ------------------------------------------------------------------------------------------
  * Marker genes: the device half of tl.rank_genes_groups (reference: `_RankGenes` in
  * src/scanpy/tools/_rank_genes_groups.py -- `_aggregate_group_stats`, `_ranks`, `_tiecorrect`, `wilcoxon`; csrc/rank_genes.hip,
  * DESIGN.md 3.8).  Input: the CSC copy of the cells x genes matrix as scamd_csr_transpose_f32 writes it (t_indptr int64[g + 1],

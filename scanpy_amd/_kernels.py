@@ -815,6 +815,49 @@ def pp_regress_resid(indptr, indices, data, n: int, g: int, keep: torch.Tensor, 
     return out
 
 
+# ---- scrublet (csrc/scrublet.hip) ----------------------------------------------------------------------------------
+def pp_scrublet_pairs(indptr, indices, data, n: int, g: int, pairs: torch.Tensor, row_total: torch.Tensor):
+    """Row-pair sums: output row r = row pairs[r, 0] + row pairs[r, 1] of a canonical CSR matrix.  Count phase, device scan,
+    one read-back of the total, allocation, fill phase.
+    -> (out_indptr int64 [n_sim + 1], out_indices int32, out_data float32, total_sim like row_total [n_sim], flags int)"""
+    dev = require_gpu()
+    lib = _lib.load()
+    assert pairs.dtype == torch.int32 and pairs.is_contiguous() and pairs.dim() == 2 and pairs.shape[1] == 2
+    assert row_total.dtype in (torch.float32, torch.float64) and row_total.numel() == n
+    n_sim = int(pairs.shape[0])
+    out_indptr = _empty(n_sim + 1, dtype=torch.int64, device=dev)
+    total_sim = _empty(n_sim, dtype=row_total.dtype, device=dev)
+    flags = _empty(1, dtype=torch.int32, device=dev)
+    ws, wsz = _ws(lib.scamd_pp_scrublet_workspace_bytes(n_sim), dev)
+    total = C.c_int64(-1)
+    rc = lib.scamd_pp_scrublet_pair_count(ptr(indptr), ptr(indices), n, g, data.numel(), ptr(pairs), n_sim, ptr(row_total),
+                                          1 if row_total.dtype == torch.float64 else 0, ptr(out_indptr), ptr(total_sim), ptr(flags),
+                                          C.byref(total), ptr(ws), wsz, stream_ptr())
+    _check(rc, "scamd_pp_scrublet_pair_count")
+    out_nnz = int(total.value)
+    f = int(flags.cpu()[0])
+    out_indices = _empty(out_nnz, dtype=torch.int32, device=dev)
+    out_data = _empty(out_nnz, dtype=torch.float32, device=dev)
+    rc = lib.scamd_pp_scrublet_pair_fill_f32(ptr(indptr), ptr(indices), ptr(data), n, g, data.numel(), ptr(pairs), n_sim,
+                                             ptr(out_indptr), out_nnz, ptr(out_indices), ptr(out_data), ptr(flags), stream_ptr())
+    _check(rc, "scamd_pp_scrublet_pair_fill_f32")
+    return out_indptr, out_indices, out_data, total_sim, f | int(flags.cpu()[0])
+
+
+def scrublet_scores(idx: torch.Tensor, n_obs: int, *, rho: float, r: float, se_rho: float):
+    """idx int32 [n_all, k], observed rows first -> (n_sim_neigh int32 [n_all], score float64 [n_all], score_err float64 [n_all])"""
+    dev = require_gpu()
+    assert idx.dtype == torch.int32 and idx.is_contiguous() and idx.dim() == 2
+    n_all, k = idx.shape
+    cnt = _empty(n_all, dtype=torch.int32, device=dev)
+    score = _empty(n_all, dtype=torch.float64, device=dev)
+    err = _empty(n_all, dtype=torch.float64, device=dev)
+    rc = _lib.load().scamd_scrublet_scores_f64(ptr(idx), n_all, int(k), int(n_obs), float(rho), float(r), float(se_rho), ptr(cnt),
+                                               ptr(score), ptr(err), stream_ptr())
+    _check(rc, "scamd_scrublet_scores_f64")
+    return cnt, score, err
+
+
 # ---- UMAP layout (csrc/umap.hip) -----------------------------------------------------------------------------------
 def rank_genes_group_stats(t_indptr, t_indices, t_data, n: int, g: int, codes: torch.Tensor, n_groups: int, *,
                            expm1_scale: float | None = None):

@@ -89,6 +89,10 @@ SIGNATURES = {
     "scamd_pp_regress_workspace_bytes": (_sz, [_i64, _i32]),
     "scamd_pp_regress_sums_f32": (_i32, [_vp, _vp, _vp, _i64, _i64, _i64, _vp, _vp, _i32, _vp, _vp, _vp, _vp, _vp, _vp, _sz, _vp]),
     "scamd_pp_regress_resid_f32": (_i32, [_vp, _vp, _vp, _i64, _i64, _i64, _vp, _vp, _vp, _vp, _i32, _vp, _i32, _vp]),
+    "scamd_pp_scrublet_workspace_bytes": (_sz, [_i64]),
+    "scamd_pp_scrublet_pair_count": (_i32, [_vp, _vp, _i64, _i64, _i64, _vp, _i64, _vp, _i32, _vp, _vp, _vp, C.POINTER(_i64), _vp, _sz, _vp]),
+    "scamd_pp_scrublet_pair_fill_f32": (_i32, [_vp, _vp, _vp, _i64, _i64, _i64, _vp, _i64, _vp, _i64, _vp, _vp, _vp, _vp]),
+    "scamd_scrublet_scores_f64": (_i32, [_vp, _i64, _i32, _i64, _f64, _f64, _f64, _vp, _vp, _vp, _vp]),
     "scamd_rank_genes_workspace_bytes": (_sz, [_i64, _i64, _i64, _i32]),
     "scamd_rank_genes_chunk_entries": (_i32, [_i32]),
     "scamd_rank_genes_group_stats_f32": (_i32, [_vp, _vp, _vp, _i64, _i64, _vp, _i32, _i32, _f64, _vp, _vp, _vp, _vp, _sz, _vp]),

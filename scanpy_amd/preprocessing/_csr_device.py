@@ -203,6 +203,77 @@ class GpuPPBackend:
                                       out_dtype=torch.float64 if out_f64 else torch.float32)
         return out.cpu().numpy()
 
+    # ---- scrublet (csrc/scrublet.hip; the matrices stay on the device between these calls) --------------------
+    def scrublet_simulate(self, m: DeviceMatrix, pairs: np.ndarray, row_total: np.ndarray):
+        """Row-pair sums of the resident counts: -> (DeviceMatrix [n_sim, g] of the simulated doublets, total_sim numpy like
+        row_total, inexact: a sum left the range in which float32 holds integers exactly)"""
+        import torch
+
+        pd_ = torch.from_numpy(np.ascontiguousarray(pairs, dtype=np.int32).reshape(-1, 2)).to(self.device)
+        rt = np.ascontiguousarray(row_total)
+        rt = rt if rt.dtype in (np.float32, np.float64) else rt.astype(np.float64)
+        rd = torch.from_numpy(rt).to(self.device)
+        indptr, indices, data, total, flags = self.K.pp_scrublet_pairs(m.indptr, m.indices, m.data, m.n_major, m.shape[1], pd_, rd)
+        if flags & 6:
+            raise RuntimeError(f"scrublet row-pair kernel: flags {flags} (a parent index outside the matrix, or a bad row pointer)")
+        sim = DeviceMatrix("csr", (int(pd_.shape[0]), m.shape[1]), indptr, indices, data, None)
+        return sim, total.cpu().numpy().astype(np.asarray(row_total).dtype, copy=False), bool(flags & 1)
+
+    def scrublet_download(self, m: DeviceMatrix) -> sparse.csr_matrix:
+        return sparse.csr_matrix((m.data.cpu().numpy(), m.indices.cpu().numpy(), m.indptr.cpu().numpy()), shape=m.shape)
+
+    def scrublet_call(self, m_obs: DeviceMatrix, m_sim: DeviceMatrix, *, log_transform: bool, renormalize: bool, mean_center: bool,
+                      normalize_variance: bool, n_prin_comps: int, k_adj: int, metric: str, rho: float, r: float, se_rho: float,
+                      want_neighbors: bool = False, want_manifold: bool = False) -> dict:
+        """The resident stage of `pp.scrublet`; both matrices are rewritten in place.  (log1p) -> (normalize_total 1e6, each
+        matrix by its own row sums) -> (1 / sigma scaling of both by the observed matrix's statistics) -> PCA / truncated SVD
+        fitted on the observed matrix -> both projected by one spmm with the shift mean . V -> exact kNN on the concatenated
+        manifold -> scores.  -> n_sim_neigh int32, score, score_err float64 [n_obs + n_sim] (+ neighbors int32, manifold float32)"""
+        import torch
+
+        K = self.K
+        n_obs, g = m_obs.shape
+        for m in (m_obs, m_sim):
+            if log_transform:
+                K.pp_log1p_(m.data)
+            if renormalize:
+                # the factor is numpy's float32 division, as `normalize_total` makes it (a device division by a scalar is a
+                # multiplication by its reciprocal: other bits); the n row sums make the round trip, the matrix stays
+                factor = K.pp_row_sums(m.indptr, m.indices, m.data, m.n_major).cpu().numpy() / 1e6
+                K.pp_row_divide_(m.indptr, m.data, m.n_major, torch.from_numpy(factor).to(self.device))
+        if normalize_variance:
+            s, sq, _ = K.pp_col_stats(m_obs.indptr, m_obs.indices, m_obs.data, n_obs, g, count_positive=False)
+            _, var = mean_var_from_sums(s, sq, n_obs, correction=1)
+            std = torch.sqrt(var)
+            flat = int((~(std > 0)).sum())
+            if flat:
+                raise ValueError(f"{flat} of {g} genes have zero variance over the observed cells: their z-score is undefined. "
+                                 "Filter them out first (`filter_genes`) or pass `normalize_variance=False`.")
+            for m in (m_obs, m_sim):
+                K.pp_scale_csr_(m.indptr, m.indices, m.data, m.n_major, std)
+        _, comps, _, _, mean, _ = K.pca_csr(m_obs.indptr, m_obs.indices, m_obs.data, n_obs, g, int(n_prin_comps),
+                                            zero_center=bool(mean_center), seed=0)
+        v = comps.t().contiguous()
+        shift = (mean @ v) if mean_center else None
+        manifold = torch.cat([K.spmm(m.indptr, m.indices, m.data, m.n_major, g, v, shift) for m in (m_obs, m_sim)], dim=0)
+        rows = manifold
+        if metric in ("cosine", "correlation"):  # as `neighbors` prepares its rows
+            x64 = manifold.to(torch.float64)
+            if metric == "correlation":
+                x64 = x64 - x64.mean(dim=1, keepdim=True)
+            norm = torch.linalg.norm(x64, dim=1, keepdim=True)
+            if bool((norm == 0).any()):
+                raise ValueError(f"metric={metric!r} is undefined for " + ("all-zero rows" if metric == "cosine" else "constant rows"))
+            rows = (x64 / norm).to(torch.float32).contiguous()
+        idx, _, _ = K.knn(rows, int(k_adj))
+        cnt, score, err = K.scrublet_scores(idx, n_obs, rho=rho, r=r, se_rho=se_rho)
+        out = {"n_sim_neigh": cnt.cpu().numpy(), "score": score.cpu().numpy(), "score_err": err.cpu().numpy()}
+        if want_neighbors:
+            out["neighbors"] = idx.cpu().numpy()
+        if want_manifold:
+            out["manifold"] = manifold.cpu().numpy()
+        return out
+
 
 def default_backend():
     return GpuPPBackend()
