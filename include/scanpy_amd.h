@@ -78,8 +78,12 @@ int scamd_knn_l2_f32(const float* x, int64_t n, int d, int64_t ld_x,
  * output conventions as scamd_knn_l2_f32, plus
  *   nprobe   every query sees the rows of the nprobe cells of the k-means quantiser nearest (centroid distance) to its
  *            own cell -- ~2048 rows per cell, at most 1024 cells.  Inside the probed cells the search IS the exact one
- *            (same kernels, float64 re-rank, certificate): the lists are the true nearest neighbours among the probed
- *            rows, recall < 1 comes from unprobed cells only.  nprobe <= 0 or >= the cell count: the exact search.
+ *            (same kernels, float64 re-rank, certificate): a list is the true nearest neighbours among the probed rows,
+ *            OR BETTER -- a query whose certificate fails (n_fallback_host counts them) is scanned in float64 over every
+ *            cell within its bound, probed or not, and comes back with its exact list over all rows.  So at every rank the
+ *            distance is at most that of the best list of the probed rows, at most n_fallback_host lists differ from that
+ *            list, and recall < 1 comes from unprobed cells only (tests/knn_cell_cases.py: check_promise).  nprobe <= 0: the
+ *            exact search; nprobe >= the cell count: every cell is probed, the exact lists.
  * Answered exactly as well: n < 4096, k > 24, d > 64 (shapes outside the register-list kernel).  Workspace:
  * scamd_knn_workspace_bytes (one figure for both entry points). */
 int scamd_knn_l2_ivf_f32(const float* x, int64_t n, int d, int64_t ld_x,
@@ -122,6 +126,21 @@ size_t scamd_knn_debug_b3_scores_workspace_bytes(int64_t n);
 int scamd_knn_debug_b3_scores_f32(const float* x, int64_t n, int d, int64_t ld_x, int64_t q0, int nq, int64_t c0, int nc,
                                   float* out_scores, float* out_mu, float* out_cmax, void* workspace,
                                   size_t workspace_bytes, scamd_stream_t stream);
+/* Test entry: the cell tables a pruned or approximate search used (tests/knn_cell_cases.py).  `workspace` is the workspace
+ * of a scamd_knn_l2_f32 / scamd_knn_l2_ivf_f32 call that has just returned SCAMD_OK, the shape arguments, nprobe (0 for the
+ * exact entry) and the SCAMD_KNN_* environment are that call's.  The tables are located by the call's own plan and copied out
+ * device to device; no kernel of the search runs.  SCAMD_EINVAL when that plan has no cells (brute force, or a shape the
+ * approximate entry answers exactly), before anything is read.  Sizes come from the host-only companion
+ * scamd_knn_debug_cell_tables_sizes: the cell count nc and the upper bound n_img_max of the image rows.
+ *   out_labels [n] the quantiser's cell of every row, out_row_cell [n] = out_cell_map[out_labels[i]] (small cells are folded
+ *   into their nearest big cell), out_cell_map [nc], out_cent [nc, d], out_radius [nc], out_tile0 / out_ntiles [nc] (tiles of
+ *   64 image rows), out_order / out_lb2 [nc, nc] (row a: the cells in a's sweep order and their squared lower bounds),
+ *   out_perm [n_img_max] of which the first *n_img_rows_host entries are written (image row -> row of x, -1 = padding). */
+int scamd_knn_debug_cell_tables_sizes(int64_t n, int d, int64_t n_query, int k, int nprobe, int* n_cells, int64_t* n_img_max);
+int scamd_knn_debug_cell_tables(int64_t n, int d, int64_t n_query, int k, int nprobe, const void* workspace,
+                                size_t workspace_bytes, int32_t* out_labels, int32_t* out_row_cell, int32_t* out_cell_map,
+                                float* out_cent, float* out_radius, int32_t* out_tile0, int32_t* out_ntiles, int32_t* out_order,
+                                float* out_lb2, int32_t* out_perm, int64_t* n_img_rows_host, scamd_stream_t stream);
 
 /* ------------------------------------------------------------------------------------------
  * Fuzzy simplicial set -- umap connectivities from a kNN result.

@@ -3172,8 +3172,12 @@ extern "C" int scamd_knn_l2_f32(const float* x, int64_t n, int d, int64_t ld_x, 
 // approximate too, src/scanpy/neighbors/__init__.py:734-739, 769-781): every query sees the rows of the nprobe cells
 // nearest to its own cell (centroid distance) of the same k-means quantiser the exact search prunes with.  Inside those
 // cells the search is the exact one (same kernels, same float64 re-rank and certificate), so the lists are the true
-// nearest neighbours AMONG THE PROBED ROWS: recall < 1 comes from unprobed cells only.  nprobe <= 0 or >= the cell count:
-// the exact search.  Shapes the register-list kernel does not take (k > 24, d > 64) and n < 4096 are answered exactly.
+// nearest neighbours AMONG THE PROBED ROWS, OR BETTER: the float64 scan of a query whose certificate failed
+// (knn_fallback_scan_cells_kernel) visits every cell within its bound, probed or not, so that query gets its exact list over
+// all rows.  The second tier sweeps the probed cells again and stays among them.  At every rank a list's distance is at most
+// that of the best list of the probed rows, at most n_fallback lists differ from it, recall < 1 comes from unprobed cells
+// only (tests/knn_cell_cases.py: check_promise, run_scan_case).  nprobe <= 0: the exact search; >= the cell count: every cell
+// is probed.  Shapes the register-list kernel does not take (k > 24, d > 64) and n < 4096 are answered exactly.
 extern "C" int scamd_knn_l2_ivf_f32(const float* x, int64_t n, int d, int64_t ld_x, int64_t q_begin,
                                     int64_t n_query, int k, int nprobe, int32_t* out_idx, double* out_dist,
                                     int64_t* n_fallback_host, void* workspace, size_t workspace_bytes,
@@ -3255,6 +3259,89 @@ extern "C" int scamd_knn_debug_b3_scores_f32(const float* x, int64_t n, int d, i
   SCAMD_LAUNCH_CHECK();
   if (out_mu) SCAMD_HIP_CHECK(hipMemcpyAsync(out_mu, mu, sizeof(float) * 128, hipMemcpyDeviceToDevice, s));
   if (out_cmax) SCAMD_HIP_CHECK(hipMemcpyAsync(out_cmax, cmax, sizeof(float), hipMemcpyDeviceToDevice, s));
+  return SCAMD_OK;
+}
+
+// ------------------------------------------------------------------------------------------------
+// Test entry for the cell tables of the pruned and of the approximate search: what a call that has just returned left in its
+// workspace, located by the same knn_plan / knn_carve / cell_tables the call used (same shape, same nprobe, same SCAMD_KNN_*
+// environment), copied out device to device.  No kernel of the search runs; the one kernel here gathers cell_map[labels[i]]
+// (and the read-back of the image's end publishes through its own).
+// Nothing after the sweep writes these buffers with other values: the second tier (run_ivf_tier2) rewrites qpos, block_cell and
+// block_perm -- none of them handed out -- and runs ivf_pack_image_kernel again, whose atomicMax puts the same radii on
+// radius_bits; the float64 scan only reads.  So the tables are read as they lie, none is rebuilt.
+// Sizes: scamd_knn_debug_cell_tables_sizes (host only) gives the cell count and the bound of the image rows.
+// tests/knn_cell_cases.py checks the tables against float64 and the approximate lists against the rows they name.
+// ------------------------------------------------------------------------------------------------
+namespace scamd {
+__global__ void knn_debug_row_cell_kernel(const int* __restrict__ labels, const int* __restrict__ cell_map, int64_t n, int n_cells,
+                                          int32_t* __restrict__ row_cell) {
+  const int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
+  if (i >= n) return;
+  const int c = labels[i];  // (a workspace that is not the call's holds anything: no index is followed unchecked)
+  row_cell[i] = (c >= 0 && c < n_cells) ? cell_map[c] : -1;
+}
+}  // namespace scamd
+
+extern "C" int scamd_knn_debug_cell_tables_sizes(int64_t n, int d, int64_t n_query, int k, int nprobe, int* n_cells,
+                                                 int64_t* n_img_max) {
+  SCAMD_REQUIRE(n_cells && n_img_max, SCAMD_EINVAL, "knn debug cell tables: null pointer");
+  *n_cells = 0;
+  *n_img_max = 0;
+  KnnPlan p;
+  SCAMD_REQUIRE(n >= 1 && d >= 1 && n_query >= 1 && n_query <= n && k >= 1 && knn_plan(n, d, n_query, k, &p, nprobe > 0 ? nprobe : 0),
+                SCAMD_EINVAL, "knn debug cell tables: bad shape n=%lld d=%d n_query=%lld k=%d", (long long)n, d, (long long)n_query, k);
+  SCAMD_REQUIRE(p.ivf && p.n_cells > 0, SCAMD_EINVAL, "knn debug cell tables: the plan of this call has no cells");
+  *n_cells = p.n_cells;
+  *n_img_max = p.n_img_max;
+  return SCAMD_OK;
+}
+
+extern "C" int scamd_knn_debug_cell_tables(int64_t n, int d, int64_t n_query, int k, int nprobe, const void* workspace,
+                                           size_t workspace_bytes, int32_t* out_labels, int32_t* out_row_cell, int32_t* out_cell_map,
+                                           float* out_cent, float* out_radius, int32_t* out_tile0, int32_t* out_ntiles,
+                                           int32_t* out_order, float* out_lb2, int32_t* out_perm, int64_t* n_img_rows_host,
+                                           scamd_stream_t stream) {
+  int nc = 0;
+  int64_t n_img_max = 0;
+  if (int rc = scamd_knn_debug_cell_tables_sizes(n, d, n_query, k, nprobe, &nc, &n_img_max)) return rc;
+  SCAMD_REQUIRE(workspace && out_labels && out_row_cell && out_cell_map && out_cent && out_radius && out_tile0 && out_ntiles &&
+                    out_order && out_lb2 && out_perm && n_img_rows_host,
+                SCAMD_EINVAL, "knn debug cell tables: null pointer");
+  KnnPlan p;
+  knn_plan(n, d, n_query, k, &p, nprobe > 0 ? nprobe : 0);
+  Workspace ws(const_cast<void*>(workspace), workspace_bytes);
+  KnnBuffers b;
+  knn_carve(ws, p, n_query, &b);
+  SCAMD_REQUIRE(ws.ok, SCAMD_EWORKSPACE, "knn debug cell tables: workspace %zu < required %zu", workspace_bytes, ws.used());
+  const CellTables t = cell_tables(b, (size_t)nc);
+  hipStream_t s = stream;
+  int last[2] = {0, 0};  // the image ends with the last cell's tiles (ivf_cell_layout)
+  {
+    const HostReadbackScope scope;
+    SCAMD_READBACK(&last[0], t.tile0 + nc - 1, sizeof(int), s);
+    SCAMD_READBACK(&last[1], t.ntiles + nc - 1, sizeof(int), s);
+    if (int rc = host_readback().sync(s)) return rc;
+  }
+  const int64_t rows = ((int64_t)last[0] + last[1]) * 64;
+  SCAMD_REQUIRE(last[0] >= 0 && last[1] >= 0 && rows <= n_img_max, SCAMD_EINTERNAL,
+                "knn debug cell tables: %lld image rows exceed the plan's %lld (is this the workspace of the same call?)", (long long)rows,
+                (long long)n_img_max);
+  *n_img_rows_host = rows;
+  const size_t cell_bytes = sizeof(int) * (size_t)nc;
+  const auto d2d = [&](void* dst, const void* src, size_t bytes) { return hipMemcpyAsync(dst, src, bytes, hipMemcpyDeviceToDevice, s); };
+  SCAMD_HIP_CHECK(d2d(out_labels, b.labels, sizeof(int) * (size_t)n));
+  SCAMD_HIP_CHECK(d2d(out_cell_map, t.cell_map, cell_bytes));
+  SCAMD_HIP_CHECK(d2d(out_cent, b.cent, sizeof(float) * (size_t)nc * d));
+  SCAMD_HIP_CHECK(d2d(out_radius, t.radius, cell_bytes));
+  SCAMD_HIP_CHECK(d2d(out_tile0, t.tile0, cell_bytes));
+  SCAMD_HIP_CHECK(d2d(out_ntiles, t.ntiles, cell_bytes));
+  SCAMD_HIP_CHECK(d2d(out_order, b.cell_order, cell_bytes * nc));
+  SCAMD_HIP_CHECK(d2d(out_lb2, b.cell_lb2, cell_bytes * nc));
+  if (rows > 0) SCAMD_HIP_CHECK(d2d(out_perm, b.perm, sizeof(int) * (size_t)rows));
+  hipLaunchKernelGGL(scamd::knn_debug_row_cell_kernel, dim3((unsigned)ceil_div(n, 256)), dim3(256), 0, s, b.labels, t.cell_map, n, nc,
+                     out_row_cell);
+  SCAMD_LAUNCH_CHECK();
   return SCAMD_OK;
 }
 

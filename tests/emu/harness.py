@@ -355,6 +355,51 @@ class Abi:
         z = max(int(nnz.value), 0)
         return rc, m.get(indptr), m.get(indices)[:z].copy(), m.get(data)[:z].copy()
 
+    # ---- the kNN search with the cell tables it used (csrc/knn.hip: scamd_knn_debug_cell_tables; tests/knn_cell_cases.py) ----
+    def knn_cell_sizes(self, n, d, n_query, k, nprobe):
+        """-> (rc, cell count, upper bound of the image rows): host only"""
+        nc, img = C.c_int(-1), C.c_int64(-1)
+        rc = self.lib.scamd_knn_debug_cell_tables_sizes(n, d, n_query, k, int(nprobe), C.byref(nc), C.byref(img))
+        return rc, int(nc.value), int(img.value)
+
+    def knn_with_cells(self, x, k, *, nprobe=0, d=None, q_begin=0, n_query=None, ws_short=0, null_ws=False):
+        """x [n, ld] float32, of which the first d columns are the data.  One search (the approximate entry when nprobe > 0), then
+        the debug entry on the workspace the search left.  -> (idx, dist, n_fallback, rc of the debug entry, tables or None);
+        tables: dict of numpy arrays labels, row_cell [n], cell_map, radius, tile0, ntiles [nc], cent [nc, d], order, lb2 [nc, nc],
+        perm [image rows], and nc.  ws_short / null_ws: the workspace the DEBUG entry is told about (its argument checks)."""
+        m, lib, p = self.mem, self.lib, self.mem.ptr
+        x = np.ascontiguousarray(x, dtype=np.float32)
+        n, ld = x.shape
+        d = ld if d is None else d
+        nq = n if n_query is None else n_query
+        dx = m.put(x, np.float32)
+        idx, dist = m.full((nq, k), np.int32, -7), m.full((nq, k), np.float64, np.nan)
+        ws, wsz = self._ws(lib.scamd_knn_workspace_bytes(n, d, nq, k))
+        nfb = C.c_int64(-1)
+        if nprobe:
+            rc = lib.scamd_knn_l2_ivf_f32(p(dx), n, d, ld, q_begin, nq, k, int(nprobe), p(idx), p(dist), C.byref(nfb), p(ws), wsz, m.stream)
+        else:
+            rc = lib.scamd_knn_l2_f32(p(dx), n, d, ld, q_begin, nq, k, p(idx), p(dist), 1.0, C.byref(nfb), p(ws), wsz, m.stream)
+        m.sync()
+        _check(lib, rc, "knn")
+        rc, nc, img = self.knn_cell_sizes(n, d, nq, k, nprobe)
+        nc_a, img_a = max(nc, 1), max(img, 1)  # (a plan without cells: the entry must refuse before it touches these)
+        i32 = lambda shape: m.full(shape, np.int32, -7)  # noqa: E731
+        f32 = lambda shape: m.full(shape, np.float32, np.nan)  # noqa: E731
+        out = dict(labels=i32(n), row_cell=i32(n), cell_map=i32(nc_a), cent=f32((nc_a, d)), radius=f32(nc_a), tile0=i32(nc_a),
+                   ntiles=i32(nc_a), order=i32((nc_a, nc_a)), lb2=f32((nc_a, nc_a)), perm=i32(img_a))
+        rows = C.c_int64(-1)
+        rc = lib.scamd_knn_debug_cell_tables(n, d, nq, k, int(nprobe), C.c_void_p(0) if null_ws else p(ws), max(wsz - ws_short, 0),
+                                             *(p(out[key]) for key in out), C.byref(rows), m.stream)
+        m.sync()
+        idx, dist = m.get(idx), m.get(dist)
+        if rc != 0:
+            return idx, dist, int(nfb.value), rc, None
+        tables = {key: m.get(a) for key, a in out.items()}
+        tables["perm"] = tables["perm"][: int(rows.value)]
+        tables["nc"] = nc
+        return idx, dist, int(nfb.value), rc, tables
+
     def _csr(self, x):
         m = self.mem
         return m.put(x.indptr, np.int64), m.put(x.indices, np.int32), m.put(x.data, np.float32)

@@ -1,9 +1,11 @@
 """The approximate IVF search (`scamd_knn_l2_ivf_f32`; BASELINE configs[4], the reference's own default above 8192 cells is
 approximate: src/scanpy/neighbors/__init__.py:734-739, 769-781) against the exact engine on the same embedding.
 
-What is asserted is what the mode promises: the lists are the true nearest neighbours AMONG THE PROBED ROWS (self first,
-exact float64 distances, ascending), recall rises with nprobe and reaches the exact lists once every cell is probed; and
-the front-ends (`pp.neighbors(transformer='ivf')`, `MI355XKNNTransformer(nprobe=)`) reach it.  Recall figures at the
+What the mode promises: a list is the true nearest neighbours AMONG THE PROBED ROWS, or better (a query whose certificate
+fails is scanned over every cell within its bound and gets its exact list).  That promise itself -- every list against the rows
+the cell tables say its query could see -- is checked by tests/test_gpu_knn_cells.py.  Asserted here is what follows from it
+without the tables: self first, exact float64 distances, ascending, recall rises with nprobe and reaches the exact lists once
+every cell is probed; and the front-ends (`pp.neighbors(transformer='ivf')`, `MI355XKNNTransformer(nprobe=)`) reach it.  Recall figures at the
 bench's size are measured by bench.py (`knn_approx`)."""
 from __future__ import annotations
 
