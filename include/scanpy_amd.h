@@ -462,6 +462,50 @@ int scamd_modularity_csr_f32(const int64_t* indptr, const int32_t* indices, cons
                              scamd_stream_t stream);
 
 /* ------------------------------------------------------------------------------------------
+ * Graph autocorrelation: the device half of metrics.morans_i and metrics.gearys_c (reference: `_morans_i_mtx` / `_morans_i_vec_w`,
+ * metrics/_morans_i.py:134-181, and `_gearys_c_mtx` / `_gearys_c_vec_W`, metrics/_gearys_c.py:145-244, which walk every stored
+ * graph entry once per feature on the CPU; csrc/graph_autocorr.hip).  Graph: square CSR on the device, indptr
+ * int64 [n + 1], indices int32, weights float32 or float64 (weights_is_f64); it need not be symmetric, sorted or free of
+ * duplicates, and explicit zeros, self-loops and negative weights are ordinary entries.  A column id outside [0, n) takes no
+ * part.  1 <= n < 2^31 (SCAMD_EUNSUPPORTED beyond).  All arithmetic is float64; no atomics: every sum is added in a fixed order
+ * that depends on n and nnz alone, so two calls give the same bits and a feature's result does not depend on its slab or lane.
+ * Arguments are checked before any HIP call and a rejected call writes nothing.
+ *
+ * scamd_graph_autocorr_slab_{f32,f64}: slab = the values, cell-major: slab[j * ld + l] is feature l of cell j, l < ncols <= 64,
+ *   ld >= ncols (a dense cell-major array is read in place).  Outputs float64 [ncols] (device), per feature: mean = sum / n,
+ *   z2 = sum_i (x_i - mean)^2, moran = sum_ij w_ij z_i z_j, geary = sum_ij w_ij (x_i - x_j)^2 (from the differences as
+ *   written: exactly 0 for a feature constant on every connected component), min, max (NaN ignored).  A feature is constant
+ *   exactly when min == max; a feature with a non-finite value has a non-finite mean and leaves the others alone.  The caller
+ *   divides: I = n / W_sum * moran / z2, C = (n - 1) / (2 W_sum) * geary / z2.  Workspace: scamd_graph_autocorr_workspace_bytes.
+ * scamd_graph_autocorr_part_entries: the stored entries one wave of the edge sweep takes at that nnz (the sweep is split by
+ *   entries, not rows: a longer row is shared by several waves).
+ * scamd_graph_weight_sum_f64: out[0] (device) = W_sum, the float64 sum of all stored weights in a fixed order (replaces
+ *   `g.data.sum()`).  Workspace: the same function (8 KiB are used).
+ * scamd_csr_dense_slab_f32: columns [c0, c0 + ncols) of a canonical cell-major CSR float32 (sorted, unique columns) as a slab,
+ *   implicit zeros written as 0 (replaces `.toarray()` of a block of genes); every element slab[i * ld + l], l < ncols, is written.
+ * scamd_transpose_slab_{f32,f64}: feature-major dense rows vals[f * ldv + j] (f < ncols, j < n) -> slab[j * ld + f]
+ *   (replaces the `.T` copy of a block of features).
+ * ---------------------------------------------------------------------------------------- */
+size_t scamd_graph_autocorr_workspace_bytes(int64_t n, int64_t nnz);
+int scamd_graph_autocorr_part_entries(int64_t nnz);
+int scamd_graph_autocorr_slab_f32(const int64_t* indptr, const int32_t* indices, const void* weights, int weights_is_f64,
+                                  int64_t n, int64_t nnz, const float* slab, int64_t ld, int32_t ncols, double* out_mean,
+                                  double* out_z2, double* out_moran, double* out_geary, double* out_min, double* out_max,
+                                  void* workspace, size_t workspace_bytes, scamd_stream_t stream);
+int scamd_graph_autocorr_slab_f64(const int64_t* indptr, const int32_t* indices, const void* weights, int weights_is_f64,
+                                  int64_t n, int64_t nnz, const double* slab, int64_t ld, int32_t ncols, double* out_mean,
+                                  double* out_z2, double* out_moran, double* out_geary, double* out_min, double* out_max,
+                                  void* workspace, size_t workspace_bytes, scamd_stream_t stream);
+int scamd_graph_weight_sum_f64(const void* weights, int weights_is_f64, int64_t nnz, double* out, void* workspace,
+                               size_t workspace_bytes, scamd_stream_t stream);
+int scamd_csr_dense_slab_f32(const int64_t* indptr, const int32_t* indices, const float* data, int64_t n, int64_t g,
+                             int64_t nnz, int64_t c0, int32_t ncols, float* slab, int64_t ld, scamd_stream_t stream);
+int scamd_transpose_slab_f32(const float* vals, int64_t ldv, int64_t n, int32_t ncols, float* slab, int64_t ld,
+                             scamd_stream_t stream);
+int scamd_transpose_slab_f64(const double* vals, int64_t ldv, int64_t n, int32_t ncols, double* slab, int64_t ld,
+                             scamd_stream_t stream);
+
+/* ------------------------------------------------------------------------------------------
  * Upstream normalisation chain: normalize_total -> log1p -> highly_variable_genes -> scale on a
  * CSR float32 matrix resident on the device.  One HBM-bound sweep each; no workspace (the caller owns every output).
  * A dense matrix is passed as a CSR with the full pattern (indptr[i] = i*g, indices = column ids).

@@ -1007,3 +1007,61 @@ def harmony_correct(x: torch.Tensor, codes: torch.Tensor, n_levels: int, r: torc
                                        ptr(z_hat), ptr(z_norm), ptr(lam), ptr(ws), wsz, stream_ptr())
     _check(rc, "scamd_harmony_correct_f64")
     return z_hat, z_norm, lam
+
+
+# ---- graph autocorrelation (csrc/graph_autocorr.hip) ----------------------------------------------------------------
+def graph_autocorr_part_entries(nnz: int) -> int:
+    return int(_lib.load().scamd_graph_autocorr_part_entries(int(nnz)))
+
+
+def graph_weight_sum(weights: torch.Tensor) -> float:
+    """W_sum: the float64 sum of the stored weights (float32 or float64) in a fixed order"""
+    dev = require_gpu()
+    lib = _lib.load()
+    assert weights.dtype in (torch.float32, torch.float64) and weights.is_contiguous()
+    out = _empty(1, dtype=torch.float64, device=dev)
+    ws, wsz = _ws(lib.scamd_graph_autocorr_workspace_bytes(1, weights.numel()), dev)
+    rc = lib.scamd_graph_weight_sum_f64(ptr(weights), int(weights.dtype == torch.float64), weights.numel(), ptr(out), ptr(ws), wsz,
+                                        stream_ptr())
+    _check(rc, "scamd_graph_weight_sum_f64")
+    return float(out.cpu()[0])
+
+
+def graph_autocorr_slab(indptr, indices, weights, n: int, slab: torch.Tensor, ld: int, ncols: int, *, offset: int = 0):
+    """slab: float32 / float64 tensor holding the cell-major values; feature l of cell j at element offset + j * ld + l.
+    -> (mean, z2, moran, geary, min, max), float64 [ncols] each"""
+    dev = require_gpu()
+    lib = _lib.load()
+    assert slab.dtype in (torch.float32, torch.float64) and slab.is_contiguous() and weights.dtype in (torch.float32, torch.float64)
+    assert 1 <= ncols <= ld and offset >= 0 and offset + (n - 1) * ld + ncols <= slab.numel()
+    outs = [_empty(ncols, dtype=torch.float64, device=dev) for _ in range(6)]
+    nnz = indices.numel()
+    ws, wsz = _ws(lib.scamd_graph_autocorr_workspace_bytes(n, nnz), dev)
+    entry = lib.scamd_graph_autocorr_slab_f64 if slab.dtype == torch.float64 else lib.scamd_graph_autocorr_slab_f32
+    base = C.c_void_p(slab.data_ptr() + offset * slab.element_size())
+    rc = entry(ptr(indptr), ptr(indices), ptr(weights), int(weights.dtype == torch.float64), n, nnz, base, int(ld), int(ncols),
+               *(ptr(o) for o in outs), ptr(ws), wsz, stream_ptr())
+    _check(rc, "scamd_graph_autocorr_slab")
+    return tuple(outs)
+
+
+def csr_dense_slab(indptr, indices, data, n: int, g: int, c0: int, ncols: int, out: torch.Tensor | None = None) -> torch.Tensor:
+    """columns [c0, c0 + ncols) of a canonical CSR float32 as a dense float32 [n, 64] slab (the first ncols columns are written)"""
+    dev = require_gpu()
+    slab = _empty((n, 64), dtype=torch.float32, device=dev) if out is None else out
+    rc = _lib.load().scamd_csr_dense_slab_f32(ptr(indptr), ptr(indices), ptr(data), n, g, data.numel(), int(c0), int(ncols), ptr(slab),
+                                              64, stream_ptr())
+    _check(rc, "scamd_csr_dense_slab_f32")
+    return slab
+
+
+def transpose_slab(rows: torch.Tensor, out: torch.Tensor | None = None) -> torch.Tensor:
+    """rows [b <= 64, n] feature-major (contiguous) -> the cell-major slab [n, 64] of the same dtype (the first b columns are written)"""
+    dev = require_gpu()
+    lib = _lib.load()
+    assert rows.dtype in (torch.float32, torch.float64) and rows.is_contiguous() and rows.dim() == 2 and rows.shape[0] <= 64
+    b, n = rows.shape
+    slab = _empty((n, 64), dtype=rows.dtype, device=dev) if out is None else out
+    entry = lib.scamd_transpose_slab_f64 if rows.dtype == torch.float64 else lib.scamd_transpose_slab_f32
+    _check(entry(ptr(rows), n, n, b, ptr(slab), 64, stream_ptr()), "scamd_transpose_slab")
+    return slab

@@ -78,6 +78,14 @@ SIGNATURES = {
     "scamd_leiden_debug_level_f32": (_i32, [_vp, _vp, _vp, _i64, _i64, _vp, _vp, _f64, _f64, _u64, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp,
                                             C.POINTER(_i64), _vp, _sz, _vp]),
     "scamd_modularity_csr_f32": (_i32, [_vp, _vp, _vp, _i64, _i64, _vp, _f64, C.POINTER(_f64), _vp, _sz, _vp]),
+    "scamd_graph_autocorr_workspace_bytes": (_sz, [_i64, _i64]),
+    "scamd_graph_autocorr_part_entries": (_i32, [_i64]),
+    "scamd_graph_autocorr_slab_f32": (_i32, [_vp, _vp, _vp, _i32, _i64, _i64, _vp, _i64, _i32, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _sz, _vp]),
+    "scamd_graph_autocorr_slab_f64": (_i32, [_vp, _vp, _vp, _i32, _i64, _i64, _vp, _i64, _i32, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _sz, _vp]),
+    "scamd_graph_weight_sum_f64": (_i32, [_vp, _i32, _i64, _vp, _vp, _sz, _vp]),
+    "scamd_csr_dense_slab_f32": (_i32, [_vp, _vp, _vp, _i64, _i64, _i64, _i64, _i32, _vp, _i64, _vp]),
+    "scamd_transpose_slab_f32": (_i32, [_vp, _i64, _i64, _i32, _vp, _i64, _vp]),
+    "scamd_transpose_slab_f64": (_i32, [_vp, _i64, _i64, _i32, _vp, _i64, _vp]),
     "scamd_pp_row_sums_f32": (_i32, [_vp, _vp, _vp, _i64, _i64, _vp, _vp, _vp]),
     "scamd_pp_row_count_positive_f32": (_i32, [_vp, _vp, _i64, _i64, _vp, _vp]),
     "scamd_pp_count_high_f32": (_i32, [_vp, _vp, _vp, _i64, _i64, _i64, _vp, C.c_float, _vp, _vp]),

@@ -10,7 +10,41 @@ import pandas as pd
 from scipy import sparse
 
 from .._anndata import is_anndata
-from .._utils import choose_graph
+from .._utils import choose_graph, natsorted_str
+
+
+def _label_order(labels: pd.Series) -> np.ndarray:
+    """the categories of a categorical, else the unique values in natural order (`natsorted`)"""
+    if isinstance(labels.dtype, pd.CategoricalDtype):
+        return np.array(labels.cat.categories)
+    uniq = list(pd.unique(labels))
+    return np.array(natsorted_str(uniq) if all(isinstance(v, str) for v in uniq) else sorted(uniq))
+
+
+def confusion_matrix(orig, new, data=None, *, normalize: bool = True) -> pd.DataFrame:
+    """Given an original and a new set of labels, a labelled confusion matrix (drop-in for
+    `scanpy.metrics.confusion_matrix`, src/scanpy/metrics/_metrics.py:29-105; host only).  `orig` and `new` are arrays of the
+    same size or, with `data`, names of its columns.  normalize: every row is divided by its sum (a row of zeros stays)."""
+    if data is not None:
+        if isinstance(orig, str):
+            orig = data[orig]
+        if isinstance(new, str):
+            new = data[new]
+    orig, new = pd.Series(orig), pd.Series(new)
+    assert len(orig) == len(new)
+    unique_labels = pd.unique(np.concatenate((orig.to_numpy(), new.to_numpy())))
+    k = len(unique_labels)
+    oc = pd.Categorical(orig.to_numpy(), categories=unique_labels).codes.astype(np.int64)
+    nc = pd.Categorical(new.to_numpy(), categories=unique_labels).codes.astype(np.int64)
+    mtx = np.bincount(oc * k + nc, minlength=k * k).reshape(k, k).astype(np.int64)
+    if normalize:
+        sums = mtx.sum(axis=1)[:, np.newaxis]
+        mtx = mtx.astype(np.float64)
+        np.divide(mtx, sums, where=sums != 0, out=mtx)
+    orig_name = "Original labels" if orig.name is None else orig.name
+    new_name = "New Labels" if new.name is None else new.name
+    df = pd.DataFrame(mtx, index=pd.Index(unique_labels, name=orig_name), columns=pd.Index(unique_labels, name=new_name))
+    return df.loc[_label_order(orig), _label_order(new)]
 
 
 def _codes(labels) -> np.ndarray:
