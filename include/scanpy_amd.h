@@ -775,6 +775,60 @@ int scamd_umap_optimize_f32(const int64_t* indptr, const int32_t* indices, const
                             void* workspace, size_t workspace_bytes, scamd_stream_t stream);
 
 /* ------------------------------------------------------------------------------------------
+ * Collapsing cells into groups: the device half of get.aggregate (reference: `aggregate`, `Aggregate.{sum, count_nonzero,
+ * mean_var, median}` in src/scanpy/get/_aggregated.py, the sweeps of src/scanpy/get/_kernels.py and sklearn's
+ * csc_median_axis_0; csrc/aggregate.hip).  Input as for the normalisation chain: canonical CSR float32 on the
+ * device, a dense matrix as the full pattern; an implicit zero is the value 0, and so is a stored +-0.0.
+ *   codes int32 [n]: the group of every row, 0 <= code < n_groups, or -1 for a row that takes no part (the host folds the mask
+ *     and missing categories into -1);
+ *   order int32 [n_order]: the rows that take part, sorted by group (a counting sort of codes; any order inside a group);
+ *   group_sizes int64 [n_groups] (device): the rows of every group; a group may have size 0; their sum is n_order.
+ * Outputs are group-major [n_groups x g], out[k * g + j], with 64-bit offsets; n_groups <= n is the only bound on the number
+ * of groups.  n, g < 2^31.  Arguments are checked before any HIP call and a rejected call writes nothing; n = 0, g = 0,
+ * n_order = 0 and n_groups = 0 are legal.
+ *
+ * scamd_aggregate_moments_f32: per (group, gene) sum (float64), count_nonzero and count_negative (int64) and, when m2 is not
+ *   NULL, m2 (float64) = the sum over ALL cells of the group of (x - mean)^2 with mean = sum / size, implicit zeros included
+ *   (the deviations are taken from the final mean in sweeps of their own; sumsq - sum^2 / n is never formed; 0 for an empty
+ *   group).  flags [1], zeroed here: bit 0 = a stored value of a row that takes part was not finite (such values take part in
+ *   nothing), bit 1 = a code outside [-1, n_groups) (such rows take part in nothing), bit 2 = order, codes, group_sizes or a
+ *   column index contradict each other (such rows / entries take part in nothing; nothing is written out of bounds).
+ *   Every value is rounded once to 64-bit fixed point and added in integers (no float atomics): every output is bitwise
+ *   reproducible and independent of the order of rows, lanes, waves and workgroups.  With size the rows of the group and
+ *   amax the largest finite |x| of the gene over the rows that take part:
+ *     |sum - exact| <= (size 2^-61 + 2^-53) size amax        (integers of magnitude <= 2^24: exact)
+ *     |m2 - exact|  <= size^2 D^2 2^-60 + 2^-50 m2 + size ((size 2^-61 + 2^-52) amax)^2,
+ *                      D = max |x - mean| over the stored non-zero values of the pair, D <= 2 amax
+ *   A column that is constant and fully stored within a group has m2 == 0.0 exactly.
+ * scamd_aggregate_median_f32: median [n_groups x g] (float64) = the exact median of the `size` values of every pair, from
+ *   count_nonzero / count_negative as the moments wrote them.  An even size gives (lo + hi) / 2: the sum formed in float32
+ *   and halved when mid_in_f32 != 0 (numpy's and sklearn's arithmetic on float32 data), in float64 otherwise (integer data).
+ *   A zero result is +0.0; a group of size 0 gives NaN.  g <= 40944 (the transpose), SCAMD_EUNSUPPORTED beyond.
+ *   info_host (host, may be NULL) int64 [3]: pairs decided from the counts alone, pairs searched by one wave, by a workgroup.
+ * The sizing rules, for the tests that straddle them (host only, no device needed):
+ *   scamd_aggregate_part_entries(nnz): stored entries of one part of the sweep (the split is by entries, not rows or groups);
+ *   scamd_aggregate_lanes_per_row(n, nnz): lanes that share a row (8, 16, 32 or 64, from the mean row length);
+ *   scamd_aggregate_tier_bounds: genes of one LDS window; entries from which a run (one group inside one part) is summed in
+ *     LDS (a shorter one adds to the global table directly); the longest segment the in-wave median takes; the longest whose
+ *     keys a workgroup stages in LDS (a longer one is read from global memory in every radix pass).
+ *   scamd_aggregate_workspace_bytes(n, g, nnz, n_groups): serves both entry points (SCAMD_EWORKSPACE below it).
+ * ---------------------------------------------------------------------------------------- */
+size_t scamd_aggregate_workspace_bytes(int64_t n, int64_t g, int64_t nnz, int64_t n_groups);
+int scamd_aggregate_part_entries(int64_t nnz);
+int scamd_aggregate_lanes_per_row(int64_t n, int64_t nnz);
+int scamd_aggregate_tier_bounds(int* gene_window, int* lds_min_run, int* median_wave_max, int* median_chunk);
+int scamd_aggregate_moments_f32(const int64_t* indptr, const int32_t* indices, const float* data, int64_t n, int64_t g,
+                                int64_t nnz, const int32_t* codes, const int32_t* order, int64_t n_order,
+                                const int64_t* group_sizes, int64_t n_groups, double* sum, int64_t* count_nonzero,
+                                int64_t* count_negative, double* m2 /* may be NULL */, uint32_t* flags, void* workspace,
+                                size_t workspace_bytes, scamd_stream_t stream);
+int scamd_aggregate_median_f32(const int64_t* indptr, const int32_t* indices, const float* data, int64_t n, int64_t g,
+                               int64_t nnz, const int32_t* order, int64_t n_order, const int64_t* group_sizes,
+                               int64_t n_groups, const int64_t* count_nonzero, const int64_t* count_negative,
+                               int mid_in_f32, double* median, int64_t* info_host /* may be NULL */, void* workspace,
+                               size_t workspace_bytes, scamd_stream_t stream);
+
+/* ------------------------------------------------------------------------------------------
  * Host-side byte codecs of the on-disk readers (csrc/hostio.cpp).  No device work: callable on a
  * host without a GPU, from many threads at once.  They replace what the reference gets from h5py's bundled filters
  * when it reads `.h5ad` / 10x `.h5` files (src/scanpy/readwrite.py:15-29, 235-243; `compression='lzf'` is one of

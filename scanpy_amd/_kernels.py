@@ -1065,3 +1065,37 @@ def transpose_slab(rows: torch.Tensor, out: torch.Tensor | None = None) -> torch
     entry = lib.scamd_transpose_slab_f64 if rows.dtype == torch.float64 else lib.scamd_transpose_slab_f32
     _check(entry(ptr(rows), n, n, b, ptr(slab), 64, stream_ptr()), "scamd_transpose_slab")
     return slab
+
+
+def aggregate(indptr, indices, data, n: int, g: int, codes, order, group_sizes, *, want_m2: bool = False,
+              want_median: bool = False, mid_in_f32: bool = True) -> dict:
+    """per (group, gene) of a canonical CSR float32 [n, g]: sum (float64), count_nonzero, count_negative (int64), on request m2
+    (float64, centred) and median (float64), each [n_groups, g]; flags (int) and, with the median, info = pairs decided from the
+    counts / searched by a wave / by a workgroup.  codes int32 [n], order int32 = the rows with a group sorted by group,
+    group_sizes int64 [n_groups] (csrc/aggregate.hip)."""
+    dev = require_gpu()
+    lib = _lib.load()
+    nnz, n_groups, n_order = data.numel(), group_sizes.numel(), order.numel()
+    assert codes.dtype == torch.int32 and order.dtype == torch.int32 and group_sizes.dtype == torch.int64 and codes.numel() == n
+    shape = (n_groups, g)
+    out = {"sum": _empty(shape, dtype=torch.float64, device=dev), "count_nonzero": _empty(shape, dtype=torch.int64, device=dev),
+           "count_negative": _empty(shape, dtype=torch.int64, device=dev)}
+    if want_m2:
+        out["m2"] = _empty(shape, dtype=torch.float64, device=dev)
+    flags = _empty(1, dtype=torch.int32, device=dev)
+    ws, wsz = _ws(lib.scamd_aggregate_workspace_bytes(n, g, nnz, n_groups), dev)
+    rc = lib.scamd_aggregate_moments_f32(ptr(indptr), ptr(indices), ptr(data), n, g, nnz, ptr(codes), ptr(order), n_order,
+                                         ptr(group_sizes), n_groups, ptr(out["sum"]), ptr(out["count_nonzero"]),
+                                         ptr(out["count_negative"]), ptr(out["m2"]) if want_m2 else None, ptr(flags), ptr(ws), wsz,
+                                         stream_ptr())
+    _check(rc, "scamd_aggregate_moments_f32")
+    if want_median:
+        out["median"] = _empty(shape, dtype=torch.float64, device=dev)
+        info = (C.c_int64 * 3)()
+        rc = lib.scamd_aggregate_median_f32(ptr(indptr), ptr(indices), ptr(data), n, g, nnz, ptr(order), n_order, ptr(group_sizes),
+                                            n_groups, ptr(out["count_nonzero"]), ptr(out["count_negative"]), int(bool(mid_in_f32)),
+                                            ptr(out["median"]), info, ptr(ws), wsz, stream_ptr())
+        _check(rc, "scamd_aggregate_median_f32")
+        out["info"] = [int(v) for v in info]
+    out["flags"] = int(flags.cpu()[0])
+    return out

@@ -108,7 +108,15 @@ SIGNATURES = {
     "scamd_rank_genes_chunk_entries": (_i32, [_i32]),
     "scamd_rank_genes_group_stats_f32": (_i32, [_vp, _vp, _vp, _i64, _i64, _vp, _i32, _i32, _f64, _vp, _vp, _vp, _vp, _sz, _vp]),
     "scamd_rank_genes_wilcoxon_f32": (_i32, [_vp, _vp, _vp, _i64, _i64, _vp, _i32, _vp, _i32, _vp, _vp, _vp, _sz, _vp]),
-    "scamd_harmony_permutation_workspace_bytes": (_sz, [_i64]),
+    "scamd_aggregate_workspace_bytes": (_sz, [_i64, _i64, _i64, _i64]),
+    "scamd_aggregate_part_entries": (_i32, [_i64]),
+    "scamd_aggregate_lanes_per_row": (_i32, [_i64, _i64]),
+    "scamd_aggregate_tier_bounds": (_i32, [C.POINTER(_i32), C.POINTER(_i32), C.POINTER(_i32), C.POINTER(_i32)]),
+    "scamd_aggregate_moments_f32": (_i32, [_vp, _vp, _vp, _i64, _i64, _i64, _vp, _vp, _i64, _vp, _i64, _vp, _vp, _vp, _vp, _vp, _vp, _sz,
+                                           _vp]),
+    "scamd_aggregate_median_f32": (_i32, [_vp, _vp, _vp, _i64, _i64, _i64, _vp, _i64, _vp, _i64, _vp, _vp, _i32, _vp, C.POINTER(_i64),
+                                          _vp, _sz, _vp]),
+    "scamd_harmony_permutation_workspace_bytes":(_sz, [_i64]),
     "scamd_harmony_permutation_i32": (_i32, [_i64, _u64, _u64, _vp, _vp, _sz, _vp]),
     "scamd_harmony_normalize_f64": (_i32, [_vp, _i64, _i32, _vp, _vp]),
     "scamd_harmony_kmeans_workspace_bytes": (_sz, [_i64, _i32, _i32]),

@@ -1,9 +1,12 @@
-"""`sc.get`: host-only accessors of stored results (reference: src/scanpy/get/get.py)."""
+"""`sc.get`: host-only accessors of stored results (reference: src/scanpy/get/get.py) and `aggregate`, the grouping of cells on the
+device (reference: src/scanpy/get/_aggregated.py; `_get_aggregate.py`, csrc/aggregate.hip)."""
 from __future__ import annotations
 
 import pandas as pd
 
-__all__ = ["rank_genes_groups_df"]
+from ._get_aggregate import aggregate
+
+__all__ = ["aggregate", "rank_genes_groups_df"]
 
 
 def rank_genes_groups_df(adata, group, *, key: str = "rank_genes_groups", pval_cutoff: float | None = None,
