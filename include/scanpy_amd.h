@@ -141,6 +141,15 @@ int scamd_knn_debug_cell_tables(int64_t n, int d, int64_t n_query, int k, int np
                                 size_t workspace_bytes, int32_t* out_labels, int32_t* out_row_cell, int32_t* out_cell_map,
                                 float* out_cent, float* out_radius, int32_t* out_tile0, int32_t* out_ntiles, int32_t* out_order,
                                 float* out_lb2, int32_t* out_perm, int64_t* n_img_rows_host, scamd_stream_t stream);
+/* TEST ENTRY: the tables only the exact pruned search builds (nprobe <= 0; SCAMD_EINVAL after a call of the approximate
+ * mode), read from the same workspace in the same way, copies only.  The exact sweep follows max(ball bound, projection
+ * bound) between cells: out_reach [nc, nc], reach[p][o] = max over the members x of p of (x - c_p).(c_o - c_p) for the cells
+ * o of p's short list and +inf elsewhere; out_list_len [nc], the short list of p being the first out_list_len[p] entries of
+ * p's ball row (out_order above); out_sweep_order / out_sweep_lb2 [nc, nc], the rows the sweep followed, under the
+ * conventions of out_order / out_lb2. */
+int scamd_knn_debug_sweep_tables(int64_t n, int d, int64_t n_query, int k, int nprobe, const void* workspace,
+                                 size_t workspace_bytes, float* out_reach, int32_t* out_list_len, int32_t* out_sweep_order,
+                                 float* out_sweep_lb2, scamd_stream_t stream);
 
 /* ------------------------------------------------------------------------------------------
  * Fuzzy simplicial set -- umap connectivities from a kNN result.

@@ -34,6 +34,7 @@ SIGNATURES = {
     "scamd_knn_debug_cell_tables_sizes": (_i32, [_i64, _i32, _i64, _i32, _i32, C.POINTER(_i32), C.POINTER(_i64)]),
     "scamd_knn_debug_cell_tables": (_i32, [_i64, _i32, _i64, _i32, _i32, _vp, _sz, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp,
                                            C.POINTER(_i64), _vp]),
+    "scamd_knn_debug_sweep_tables": (_i32, [_i64, _i32, _i64, _i32, _i32, _vp, _sz, _vp, _vp, _vp, _vp, _vp]),
     "scamd_fuzzy_workspace_bytes": (_sz, [_i64, _i32]),
     "scamd_fuzzy_simplicial_set_f32": (_i32, [_vp, _vp, _i64, _i32, _vp, _vp, _vp, _i64, _vp, _vp, C.POINTER(_i64), _vp, _sz, _vp]),
     "scamd_fuzzy_weights_f32": (_i32, [_vp, _vp, _i64, _i32, _i64, _i64, _vp, _vp, _vp, _vp, _vp, _vp]),

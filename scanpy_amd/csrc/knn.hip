@@ -1314,6 +1314,46 @@ __global__ __launch_bounds__(256, WPS) void knn_select_reg_kernel(const float* _
   }
 }
 
+// The two steps the builders of a cell's sweep row share (ivf_cell_order_kernel, ivf_sweep_order_kernel; blocks of 256).
+// Bitonic sort of the row's npow entries in LDS by (bound, cell): ascending bounds, ties in cell order.
+__device__ __forceinline__ void cell_row_sort(float* lb2, int* order, int npow, int tid) {
+  for (int kk = 2; kk <= npow; kk <<= 1) {
+    for (int j = kk >> 1; j > 0; j >>= 1) {
+      for (int i = tid; i < npow; i += 256) {
+        const int p = i ^ j;
+        if (p > i) {
+          const bool up = (i & kk) == 0;
+          const float vi = lb2[i], vp = lb2[p];
+          const int oi = order[i], op = order[p];
+          const bool gt = vi > vp || (vi == vp && oi > op);
+          if (gt == up) {
+            lb2[i] = vp;
+            lb2[p] = vi;
+            order[i] = op;
+            order[p] = oi;
+          }
+        }
+      }
+      __syncthreads();
+    }
+  }
+}
+// Expected sweep length of a block of cell a (a ranking, not a bound: only the launch order and the choice of the coarse stage
+// use it): the tiles of the cells whose lower bound is within the cell's own radius -- in a clustered embedding, the cells
+// of the same cluster.  Neighbour distances are of the order of the radius of a ~2000-row cell in 50 dimensions.
+__device__ __forceinline__ void cell_row_work(const float* lb2, const int* order, const int* __restrict__ cell_ntiles, int n_cells,
+                                              int a, float ra, int tid, int* __restrict__ work_out) {
+  __shared__ int s_work;
+  if (tid == 0) s_work = 0;
+  __syncthreads();
+  int wsum = 0;
+  for (int i = tid; i < n_cells; i += 256)
+    if (lb2[i] <= ra * ra) wsum += cell_ntiles[order[i]];
+  atomicAdd(&s_work, wsum);
+  __syncthreads();
+  if (tid == 0) work_out[a] = cell_ntiles[a] > 0 ? s_work : 0;
+}
+
 // Per-cell sweep order of the cell-pruned search: block a sorts all cells by the lower bound
 // LB(a,b) = max(0, |c_a - c_b| (1 - 1e-4) - r_a - r_b) on the distance between any member of a and any member of b
 // (own cell first, empty cells last with LB = INF) and writes row a of order / order_lb2 (LB squared).
@@ -1348,26 +1388,7 @@ __global__ __launch_bounds__(256) void ivf_cell_order_kernel(const float* __rest
     order[b] = b;
   }
   __syncthreads();
-  for (int kk = 2; kk <= npow; kk <<= 1) {  // bitonic sort by (lb2, cell)
-    for (int j = kk >> 1; j > 0; j >>= 1) {
-      for (int i = tid; i < npow; i += 256) {
-        const int p = i ^ j;
-        if (p > i) {
-          const bool up = (i & kk) == 0;
-          const float vi = lb2[i], vp = lb2[p];
-          const int oi = order[i], op = order[p];
-          const bool gt = vi > vp || (vi == vp && oi > op);
-          if (gt == up) {
-            lb2[i] = vp;
-            lb2[p] = vi;
-            order[i] = op;
-            order[p] = oi;
-          }
-        }
-      }
-      __syncthreads();
-    }
-  }
+  cell_row_sort(lb2, order, npow, tid);
   if (nprobe > 0) {  // (every thread rewrites its own entries; the own cell keeps -1)
     for (int i = tid; i < npow; i += 256)
       if (i > 0) lb2[i] = (i < nprobe && lb2[i] < INFINITY) ? 0.f : INFINITY;
@@ -1377,19 +1398,219 @@ __global__ __launch_bounds__(256) void ivf_cell_order_kernel(const float* __rest
     order_out[(int64_t)a * n_cells + i] = order[i];
     lb2_out[(int64_t)a * n_cells + i] = lb2[i];
   }
-  // expected sweep length of a block of this cell (a ranking, not a bound: only the launch order uses it): the tiles
-  // of the cells whose lower bound is within the cell's own radius -- in a clustered embedding, the cells of the same
-  // cluster.  Neighbour distances are of the order of the radius of a ~2000-row cell in 50 dimensions.
   // (approximate mode: the tiles of the nprobe cells, exactly)
-  __shared__ int s_work;
-  if (tid == 0) s_work = 0;
+  cell_row_work(lb2, order, cell_ntiles, n_cells, a, ra, tid, work_out);
+}
+
+// Projection bound between cells.  For a member q of cell a, a member x of cell b and w = c_b - c_a,
+//   |x - q| >= (x - q).w / |w| = |w| - ((q - c_a).w + (x - c_b).(-w)) / |w| >= |w| - (R[a][b] + R[b][a]) / |w|,
+//   R[p][o] = max over the members x of p of (x - c_p).(c_o - c_p):
+// the gap between the two cells' extents along the line through their centroids.  It holds for whatever rows a cell
+// has (folded-in rows included, no Voronoi assumption) and uses the spread of ONE coordinate where the ball bound
+// subtracts the full radius of both cells.  R is taken about the cell's own centroid: the rows and the centroids may lie
+// far from the origin (coordinates ~1000), their differences do not, so nothing cancels in the dot product.
+//
+// ivf_reach_init_kernel: block p fixes p's SHORT LIST -- the head of p's ball row (ascending ball bound, own cell first):
+// every non-empty cell whose squared ball bound is <= fl(fl(1.5 r_p)^2), and the first REACH_MIN_LIST entries in any case (a
+// degenerate cell of radius 0 gets neighbours that way), REACH_MAX_LIST at most (two passes of ivf_reach_kernel).  A cell
+// whose rule names more than REACH_MAX_LIST cells AND more than three quarters of all cells with rows gets NO list: the ball
+// bound separates it from next to nothing, the data has no clusters at the scale of the cells, every sweep visits every
+// cell whatever the bounds say, and the search must not pay for reaches there (1M weak / structure-less cells: 0.7 ms of
+// two passes for nothing).  The bounds ascend, so the list is a prefix; its length goes to list_len[p].  Row p of the reach table starts at -inf on the list and at REACH_NONE (+inf) off it: the sweep tables use
+// the ball-derived stand-in R[p][o] <= r_p |w| for those.
+// ivf_reach_kernel<DP>: a block takes REACH_TILES tiles of one cell (reach_chunks[p] = first block of cell p: the cells differ
+// 10x in size, and a block per cell ran as long as its largest -- 6 ms at 1M rows) and every direction of the cell's list,
+// REACH_DIRS at a time.  A LANE owns a direction: its w = c_o - c_p sits in DP registers (d padded to a multiple of 4:
+// 16 / 32 / 52 / 64), a tile's rows less the centroid are staged in LDS once and read back as broadcasts, the two halves of
+// a wave taking a row each -- a dot product is d fused multiply-adds in coordinate order, no cross-lane step (the first form,
+// 16 lanes per row and a shuffle tree per direction, took 1.0 ms at 1M rows against 0.67 ms saved in the sweep).  The eight
+// half-waves meet in LDS and the block issues ONE atomic maximum per direction.
+// The maximum is exact in any order and a row's sum has a fixed order, so the table is bit-identical from run to run
+// whatever order the scatter left the rows in.
+// float32 error: e_c = fl(x_c - c_p,c) and w_c = fl(c_o,c - c_p,c) carry one rounding each, the fused chain rounds a term at
+// most d times: |R_fl - R| <= (d + 2) u |x - c_p| |w| to first order.  ivf_sweep_order_kernel charges (d + REACH_ERR_PAD) u
+// r_p |w|, REACH_ERR_PAD = 4 (r_p >= |x - c_p|: the radii are inflated).
+#ifdef SCAMD_EMU
+constexpr int REACH_DIRS = 4;   // (the host emulation's 16 cells of 4 - 6 tiles: lists of 8 .. 16 take several passes,
+constexpr int REACH_TILES = 2;  // cells several blocks there too)
+#else
+constexpr int REACH_DIRS = 32;
+constexpr int REACH_TILES = 8;
+#endif
+constexpr int REACH_MIN_LIST = 8, REACH_MAX_LIST = 64;
+constexpr int REACH_ERR_PAD = 4;
+#define REACH_NONE INFINITY
+__global__ __launch_bounds__(256) void ivf_reach_init_kernel(const float* __restrict__ radius, const int* __restrict__ cell_ntiles,
+                                                             int n_cells, const int* __restrict__ order,
+                                                             const float* __restrict__ lb2, float* __restrict__ reach,
+                                                             int* __restrict__ list_len) {
+  __shared__ int s_len[2];
+  const int p = blockIdx.x, tid = threadIdx.x;
+  const int* orow = order + (int64_t)p * n_cells;
+  const float* brow = lb2 + (int64_t)p * n_cells;
+  if (tid < 2) s_len[tid] = 0;
   __syncthreads();
-  int wsum = 0;
-  for (int i = tid; i < n_cells; i += 256)
-    if (lb2[i] <= ra * ra) wsum += cell_ntiles[order[i]];
-  atomicAdd(&s_work, wsum);
+  const float t15 = 1.5f * radius[p];
+  const float t2 = t15 * t15;
+  int near = 0, finite = 0;
+  for (int i = tid; i < n_cells; i += 256) {
+    const float v = brow[i];
+    near += v <= t2 && v < INFINITY;
+    finite += v < INFINITY;
+  }
+  if (near) atomicAdd(&s_len[0], near);
+  if (finite) atomicAdd(&s_len[1], finite);
   __syncthreads();
-  if (tid == 0) work_out[a] = cell_ntiles[a] > 0 ? s_work : 0;
+  const bool no_structure = s_len[0] > REACH_MAX_LIST && 4 * s_len[0] > 3 * s_len[1];
+  const int len = (cell_ntiles[p] > 0 && !no_structure) ? min(max(s_len[0], min(REACH_MIN_LIST, s_len[1])), REACH_MAX_LIST) : 0;
+  if (tid == 0) list_len[p] = len;
+  for (int i = tid; i < n_cells; i += 256) reach[(int64_t)p * n_cells + orow[i]] = i < len ? -INFINITY : REACH_NONE;
+}
+// maximum of floats of either sign on the bits: the integer order for v >= 0, the reversed unsigned order below (the word
+// starts at -inf; -0 enters as +0)
+__device__ __forceinline__ void atomic_max_f32(float* addr, float v) {
+  if (v == 0.f) v = 0.f;
+  if (v >= 0.f) atomicMax(reinterpret_cast<int*>(addr), __float_as_int(v));
+  else atomicMin(reinterpret_cast<unsigned int*>(addr), __float_as_uint(v));
+}
+template <int DP>
+__global__ __launch_bounds__(256) void ivf_reach_kernel(const float* __restrict__ x, int d, int64_t ld,
+                                                        const float* __restrict__ centers,
+                                                        const int* __restrict__ cell_tile0,
+                                                        const int* __restrict__ cell_ntiles, int n_cells,
+                                                        const int* __restrict__ perm, const int* __restrict__ order,
+                                                        const int* __restrict__ list_len,
+                                                        const int* __restrict__ reach_chunks, float* __restrict__ reach) {
+  static_assert(DP % 4 == 0 && REACH_DIRS <= 32, "rows are read as float4; a half-wave holds the directions of a pass");
+  __shared__ __attribute__((aligned(16))) float s_x[64][DP];
+  __shared__ int s_src[64];
+  __shared__ float s_max[8][32];
+  const int tid = threadIdx.x, j = tid & 31, slot = tid >> 5;  // slot: the half-wave, 0 .. 7
+  // the cell of this block: the last p with reach_chunks[p] <= blockIdx.x (cells without tiles have no blocks and are stepped
+  // over: their successor starts at the same block)
+  int lo = 0, hi = n_cells - 1;
+  while (lo < hi) {
+    const int mid = (lo + hi + 1) >> 1;
+    if (reach_chunks[mid] <= (int)blockIdx.x) lo = mid;
+    else hi = mid - 1;
+  }
+  const int p = lo;
+  const int t_lo = ((int)blockIdx.x - reach_chunks[p]) * REACH_TILES, t_hi = min(t_lo + REACH_TILES, cell_ntiles[p]);
+  const int len = list_len[p];
+  if (t_lo >= t_hi) return;  // (never: the host lays the blocks out by the same tile counts)
+  const int* orow = order + (int64_t)p * n_cells;
+  float* rrow = reach + (int64_t)p * n_cells;
+  const float* cp = centers + p * d;
+  for (int j0 = 0; j0 < len; j0 += REACH_DIRS) {
+    const int nj = min(REACH_DIRS, len - j0);
+    const float* co = centers + (j < nj ? orow[j0 + j] : p) * d;  // (a lane without a direction: w = 0)
+    float w[DP];
+#pragma unroll
+    for (int c = 0; c < DP; ++c) w[c] = c < d ? co[c] - cp[c] : 0.f;
+    float m = -INFINITY;
+    // four threads per row; a padding row of the cell's last tile (perm = -1) is staged as zeros and kept out of the maximum.
+    // The next tile's values wait in registers while this tile is scored: one gather in flight under the arithmetic.
+    const int row4 = tid >> 2;
+    float nx[DP / 4];
+    int nsrc;
+    auto fetch = [&](int t) __attribute__((always_inline)) {
+      nsrc = t < t_hi ? perm[((int64_t)cell_tile0[p] + t) * 64 + row4] : -1;
+#pragma unroll
+      for (int k = 0; k < DP / 4; ++k) {
+        const int c = (tid & 3) + 4 * k;
+        nx[k] = (nsrc >= 0 && c < d) ? x[(int64_t)nsrc * ld + c] - cp[c] : 0.f;
+      }
+    };
+    fetch(t_lo);
+    for (int t = t_lo; t < t_hi; ++t) {
+      __syncthreads();  // the previous tile is read
+      if ((tid & 3) == 0) s_src[row4] = nsrc;
+#pragma unroll
+      for (int k = 0; k < DP / 4; ++k) s_x[row4][(tid & 3) + 4 * k] = nx[k];
+      __syncthreads();
+      fetch(t + 1);
+#pragma unroll 2
+      for (int i = 0; i < 8; ++i) {
+        const int row = i * 8 + slot;
+        float s = 0.f;
+#pragma unroll
+        for (int c = 0; c < DP; c += 4) {
+          const float4 v = *reinterpret_cast<const float4*>(&s_x[row][c]);
+          s = fmaf(v.x, w[c], s);
+          s = fmaf(v.y, w[c + 1], s);
+          s = fmaf(v.z, w[c + 2], s);
+          s = fmaf(v.w, w[c + 3], s);
+        }
+        m = s_src[row] >= 0 ? fmaxf(m, s) : m;
+      }
+    }
+    __syncthreads();  // (the previous pass's maxima are read)
+    s_max[slot][j] = m;
+    __syncthreads();
+    if (tid < nj) {
+      float v = s_max[0][tid];
+      for (int g = 1; g < 8; ++g) v = fmaxf(v, s_max[g][tid]);
+      if (v > -INFINITY) atomic_max_f32(&rrow[orow[j0 + tid]], v);
+    }
+  }
+}
+
+// Sweep tables of the exact search: row a of sweep_order / sweep_lb2 = max(ball bound, projection bound) of every cell,
+// sorted again under the conventions of ivf_cell_order_kernel (whose row a -- order / lb2 -- is the input: the ball bound
+// enters as the float32 value stored there, so the new entry is never below it).  A partner whose reach was not computed
+// (REACH_NONE: a is not on b's short list, or b not on a's) contributes the stand-in r |w| -- the bound stays valid, it is
+// one-sided.  The combination runs in float64 on the float32 centroids, radii and reaches, so that the only float32
+// error is the reaches' (ivf_reach_kernel): the bound is lowered by (d + REACH_ERR_PAD) u (r_a + r_b), by 1e-6 relative for the
+// float64 roundings and the final rounding of the square to float32, and is 0 where the centroids coincide (|w| = 0) or
+// the gap is not positive: never a division by zero, never NaN.
+// work_out: the launch order ranks the cells by the bounds the sweep really uses.
+__global__ __launch_bounds__(256) void ivf_sweep_order_kernel(const float* __restrict__ centers, int d,
+                                                              const float* __restrict__ radius,
+                                                              const int* __restrict__ cell_ntiles, int n_cells,
+                                                              const int* __restrict__ order, const float* __restrict__ lb2,
+                                                              const float* __restrict__ reach,
+                                                              int* __restrict__ sweep_order, float* __restrict__ sweep_lb2,
+                                                              int* __restrict__ work_out) {
+  extern __shared__ __attribute__((aligned(16))) float co_smem[];
+  int npow = 1;
+  while (npow < n_cells) npow <<= 1;
+  float* v2 = co_smem;                               // [npow]
+  int* ord = reinterpret_cast<int*>(co_smem + npow);  // [npow]
+  const int a = blockIdx.x, tid = threadIdx.x;
+  const float ra = radius[a];
+  for (int i = tid; i < npow; i += 256) {
+    float v = INFINITY;
+    int b = i;  // (entries beyond n_cells sort last in any case)
+    if (i < n_cells) {
+      b = order[(int64_t)a * n_cells + i];
+      v = lb2[(int64_t)a * n_cells + i];
+      if (b != a && v < INFINITY) {
+        double w2 = 0.0;
+        for (int c = 0; c < d; ++c) {
+          const double df = (double)centers[b * d + c] - (double)centers[a * d + c];
+          w2 += df * df;
+        }
+        if (w2 > 0.0) {
+          const double w = sqrt(w2), rb = (double)radius[b];
+          const float fab = reach[(int64_t)a * n_cells + b], fba = reach[(int64_t)b * n_cells + a];
+          const double err = (double)(d + REACH_ERR_PAD) * 0x1p-24;
+          const double rab = fab == REACH_NONE ? (double)ra * w : (double)fab + err * (double)ra * w;
+          const double rba = fba == REACH_NONE ? rb * w : (double)fba + err * rb * w;
+          const double gap = (w - (rab + rba) / w) * (1.0 - 1e-6);
+          if (gap > 0.0) v = fmaxf(v, (float)(gap * gap * (1.0 - 1e-6)));
+        }
+      }
+    }
+    v2[i] = v;
+    ord[i] = b;
+  }
+  __syncthreads();
+  cell_row_sort(v2, ord, npow, tid);
+  for (int i = tid; i < n_cells; i += 256) {
+    sweep_order[(int64_t)a * n_cells + i] = ord[i];
+    sweep_lb2[(int64_t)a * n_cells + i] = v2[i];
+  }
+  cell_row_work(v2, ord, cell_ntiles, n_cells, a, ra, tid, work_out);
 }
 
 // Launch order of the pruned sweep: cells by decreasing expected work (ties: cell id), every cell's blocks together.
@@ -2393,6 +2614,9 @@ struct KnnBuffers {
   int* labels; int* perm; int* qpos; int* block_cell; float* cent; float* centp; long long* sums; int* cell_ints;
   unsigned int* radius_bits; int* cell_order; float* cell_lb2; int* cell_aux; int* block_perm;
   int* qorder;  // [n_slot_max] query number of every query slot of the pruned sweep (-1 = padding): pass 2's order
+  // exact pruned search: projection reaches of the short lists, short-list lengths, and the rows the sweep really follows --
+  // max(ball bound, projection bound), sorted again (ivf_reach_kernel, ivf_sweep_order_kernel); not built when nprobe > 0
+  float* reach; int* list_len; int* reach_chunks; int* sweep_order; float* sweep_lb2;
   // second tier of the bf16 engine (float32 engine on the queries its certificate rejected)
   int* qrow; float* xp2; int* flag_list2; int* t2_cell; int* t2_pos; int* t2_ints;
 };
@@ -2432,6 +2656,11 @@ static void knn_carve(Workspace& ws, const KnnPlan& p, int64_t n_query, KnnBuffe
     b->cell_aux = ws.take<int>((size_t)p.n_cells * 3);
     b->block_perm = ws.take<int>(block_perm_capacity(p));
     b->qorder = ws.take<int>((size_t)p.n_slot_max);
+    b->reach = ws.take<float>((size_t)p.n_cells * p.n_cells);
+    b->list_len = ws.take<int>((size_t)p.n_cells);
+    b->reach_chunks = ws.take<int>((size_t)p.n_cells);  // first block of every cell in the grid of ivf_reach_kernel
+    b->sweep_order = ws.take<int>((size_t)p.n_cells * p.n_cells);
+    b->sweep_lb2 = ws.take<float>((size_t)p.n_cells * p.n_cells);
   }
   if (p.ivf && p.b3) {
     b->qrow = ws.take<int>((size_t)n_query);
@@ -2547,8 +2776,9 @@ struct HipRelease {
 };
 using EventOwner = std::unique_ptr<std::remove_pointer_t<hipEvent_t>, HipRelease>;
 
-// what every pruned sweep takes from the buffers and the cell tables; the caller adds pairs, qorder, prepass_*, trace, queue_ctr, n_slots
-static IvfArgs ivf_args(const KnnBuffers& b, const CellTables& t, int n_cells, int d) {
+// what every pruned sweep takes from the buffers and the cell tables; the caller adds pairs, qorder, prepass_*, trace, queue_ctr, n_slots.
+// The exact search (nprobe = 0) follows the sweep tables, the approximate mode the ball rows with its probed cells.
+static IvfArgs ivf_args(const KnnBuffers& b, const CellTables& t, int n_cells, int d, int nprobe) {
   IvfArgs iv{};
   iv.qpos = b.qpos;
   iv.block_cell = b.block_cell;
@@ -2556,8 +2786,8 @@ static IvfArgs ivf_args(const KnnBuffers& b, const CellTables& t, int n_cells, i
   iv.cell_ntiles = t.ntiles;
   iv.centers = b.cent;
   iv.radius = t.radius;
-  iv.order = b.cell_order;
-  iv.order_lb2 = b.cell_lb2;
+  iv.order = nprobe > 0 ? b.cell_order : b.sweep_order;
+  iv.order_lb2 = nprobe > 0 ? b.cell_lb2 : b.sweep_lb2;
   iv.perm = b.perm;
   iv.cmax_bits = b.cmax;
   iv.n_cells = n_cells;
@@ -2583,6 +2813,8 @@ static int64_t layout_query_blocks(const std::vector<int>& n_queries, std::vecto
 struct CellLayout {
   std::vector<int> cell_map, row_off, slot_off, tile0, ntiles, block_cell;
   std::vector<int> blocks;  // [first block | blocks] of every cell, 2 * nc
+  std::vector<int> reach_chunks;  // first block of every cell in the grid of ivf_reach_kernel (REACH_TILES tiles per block)
+  int n_reach_blocks = 0;
   int64_t rows = 0, slots = 0;
   int n_launch = 0, xcd_mode = 0;
 };
@@ -2623,6 +2855,8 @@ static CellLayout ivf_cell_layout(const std::vector<int>& h_cnt, const std::vect
     L.tile0.push_back((int)(L.rows / 64));
     L.ntiles.push_back((mc[c] + 63) / 64);
     L.rows += (int64_t)L.ntiles[c] * 64;
+    L.reach_chunks.push_back(L.n_reach_blocks);
+    L.n_reach_blocks += (L.ntiles[c] + REACH_TILES - 1) / REACH_TILES;
   }
   L.slots = layout_query_blocks(mq, &L.slot_off, &L.block_cell);
   L.blocks.resize(2 * nc);
@@ -2654,6 +2888,7 @@ struct IvfSelect {
   const KnnBuffers& b;
   const KnnCall& c;
   decltype(&ivf_assign_kernel<8>) assign_f32;
+  decltype(&ivf_reach_kernel<16>) reach;
   decltype(&knn_select_reg_kernel<8, 64, 3, true, false>) sweep[2];  // [0] plain, [1] with the coarse first stage
   size_t sweep_lds;
   const CellTables t = cell_tables(b, p.n_cells);
@@ -2735,7 +2970,8 @@ struct IvfSelect {
     hipStream_t s = c.s;
     const size_t cell_bytes = sizeof(int) * nc;
     const std::pair<int*, const std::vector<int>*> per_cell[] = {
-        {t.cell_map, &L.cell_map}, {t.row_off, &L.row_off}, {t.slot_off, &L.slot_off}, {t.tile0, &L.tile0}, {t.ntiles, &L.ntiles}};
+        {t.cell_map, &L.cell_map}, {t.row_off, &L.row_off}, {t.slot_off, &L.slot_off}, {t.tile0, &L.tile0}, {t.ntiles, &L.ntiles},
+        {b.reach_chunks, &L.reach_chunks}};
     for (const auto& [dst, src] : per_cell) SCAMD_HIP_CHECK(hipMemcpyAsync(dst, src->data(), cell_bytes, hipMemcpyHostToDevice, s));
     SCAMD_HIP_CHECK(hipMemcpyAsync(b.block_cell, L.block_cell.data(), sizeof(int) * L.block_cell.size(), hipMemcpyHostToDevice, s));
     SCAMD_HIP_CHECK(hipMemcpyAsync(t.first_block, L.blocks.data(), 2 * cell_bytes, hipMemcpyHostToDevice, s));
@@ -2767,6 +3003,19 @@ struct IvfSelect {
     hipLaunchKernelGGL(ivf_cell_order_kernel, dim3(nc), dim3(256), olds, s, b.cent, c.d, t.radius, t.ntiles, nc, b.cell_order, b.cell_lb2,
                        t.work, p.nprobe);
     SCAMD_LAUNCH_CHECK();
+    if (p.nprobe == 0) {  // the exact search sweeps by max(ball, projection): reaches of the short lists, then the rows re-sorted
+      hipLaunchKernelGGL(ivf_reach_init_kernel, dim3(nc), dim3(256), 0, s, t.radius, t.ntiles, nc, b.cell_order, b.cell_lb2, b.reach,
+                         b.list_len);
+      SCAMD_LAUNCH_CHECK();
+      hipLaunchKernelGGL(reach, dim3(L.n_reach_blocks), dim3(256), 0, s, c.x, c.d, c.ld, b.cent, t.tile0, t.ntiles, nc, b.perm,
+                         b.cell_order, b.list_len, b.reach_chunks, b.reach);
+      SCAMD_LAUNCH_CHECK();
+      SCAMD_HIP_CHECK(hipFuncSetAttribute(reinterpret_cast<const void*>(ivf_sweep_order_kernel),
+                                          hipFuncAttributeMaxDynamicSharedMemorySize, (int)olds));
+      hipLaunchKernelGGL(ivf_sweep_order_kernel, dim3(nc), dim3(256), olds, s, b.cent, c.d, t.radius, t.ntiles, nc, b.cell_order, b.cell_lb2,
+                         b.reach, b.sweep_order, b.sweep_lb2, t.work);
+      SCAMD_LAUNCH_CHECK();
+    }
     // launch order: longest expected sweeps first
     hipLaunchKernelGGL(ivf_block_order_kernel, dim3(1), dim3(1024), 0, s, t.work, t.first_block, t.n_blocks, nc, b.block_perm, L.n_launch,
                        L.xcd_mode, b.counters + KC_LAUNCH_ORDER_ERR);
@@ -2800,7 +3049,7 @@ struct IvfSelect {
     const auto kern = sweep[coarse];
     const size_t lds = sweep_lds + 64 + IVF_META_BYTES;
     SCAMD_HIP_CHECK(hipFuncSetAttribute(reinterpret_cast<const void*>(kern), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
-    IvfArgs iv = ivf_args(b, t, nc, c.d);
+    IvfArgs iv = ivf_args(b, t, nc, c.d, p.nprobe);
     iv.pairs = reinterpret_cast<unsigned long long*>(b.counters + KC_PAIRS);
     iv.qorder = b.qorder;
     // float32 engine, measured at 1M: 48 -> 29.3 ms, 24 / 12 -> 29.0, 6 -> 29.6, 2 -> 30.2; bf16 engine (the pre-pass
@@ -2872,7 +3121,7 @@ static int run_ivf_select(const KnnPlan& p, const KnnBuffers& b, const KnnCall& 
   // covers the other two's insertion stalls)
   // (the coarse sweep has COARSE = B3: the float32 engine has no such instantiation, and never chooses it)
   static_assert(C::NT == RegCfg<8>::NT, "every instantiation is launched with the same block size");
-  IvfSelect sel{p, b, c, ivf_assign_kernel<H>,
+  IvfSelect sel{p, b, c, ivf_assign_kernel<H>, ivf_reach_kernel<(2 * H + 3) / 4 * 4>,
                 {knn_select_reg_kernel<H, 64, 3, true, B3>, knn_select_reg_kernel<H, 64, 3, true, B3, B3>}, C::LDS_BYTES};
   return sel.run(ev0, ev1, rows_out);
 }
@@ -2966,7 +3215,7 @@ static int run_ivf_tier2(const KnnPlan& p, const KnnBuffers& b, const KnnCall& c
   const size_t lds = C::LDS_BYTES + 64 + IVF_META_BYTES;
   SCAMD_HIP_CHECK(hipFuncSetAttribute(reinterpret_cast<const void*>(kern), hipFuncAttributeMaxDynamicSharedMemorySize,
                                       (int)lds));
-  IvfArgs iv = ivf_args(b, t, nc, c.d);
+  IvfArgs iv = ivf_args(b, t, nc, c.d, p.nprobe);
   iv.pairs = reinterpret_cast<unsigned long long*>(ctr2 + KC_PAIRS);
   iv.prepass_tiles = 16;
   iv.prepass_min2 = 1;
@@ -3342,6 +3591,35 @@ extern "C" int scamd_knn_debug_cell_tables(int64_t n, int d, int64_t n_query, in
   hipLaunchKernelGGL(scamd::knn_debug_row_cell_kernel, dim3((unsigned)ceil_div(n, 256)), dim3(256), 0, s, b.labels, t.cell_map, n, nc,
                      out_row_cell);
   SCAMD_LAUNCH_CHECK();
+  return SCAMD_OK;
+}
+
+// Its sibling for the tables only the exact pruned search builds (nprobe <= 0; SCAMD_EINVAL for a call of the approximate
+// mode, whose sweep follows the ball rows): out_reach [nc, nc] -- reach[p][o] = max over the members x of p of
+// (x - c_p).(c_o - c_p) for the cells o of p's short list, +inf elsewhere --, out_list_len [nc] -- the short list of p is the
+// first out_list_len[p] entries of p's BALL row (scamd_knn_debug_cell_tables: out_order) --, out_sweep_order / out_sweep_lb2
+// [nc, nc]: the rows the sweep followed.  Copies only, no kernel.
+extern "C" int scamd_knn_debug_sweep_tables(int64_t n, int d, int64_t n_query, int k, int nprobe, const void* workspace,
+                                            size_t workspace_bytes, float* out_reach, int32_t* out_list_len, int32_t* out_sweep_order,
+                                            float* out_sweep_lb2, scamd_stream_t stream) {
+  int nc = 0;
+  int64_t n_img_max = 0;
+  if (int rc = scamd_knn_debug_cell_tables_sizes(n, d, n_query, k, nprobe, &nc, &n_img_max)) return rc;
+  SCAMD_REQUIRE(nprobe <= 0, SCAMD_EINVAL, "knn debug sweep tables: the approximate mode (nprobe=%d) builds none", nprobe);
+  SCAMD_REQUIRE(workspace && out_reach && out_list_len && out_sweep_order && out_sweep_lb2, SCAMD_EINVAL,
+                "knn debug sweep tables: null pointer");
+  KnnPlan p;
+  knn_plan(n, d, n_query, k, &p, 0);
+  Workspace ws(const_cast<void*>(workspace), workspace_bytes);
+  KnnBuffers b;
+  knn_carve(ws, p, n_query, &b);
+  SCAMD_REQUIRE(ws.ok, SCAMD_EWORKSPACE, "knn debug sweep tables: workspace %zu < required %zu", workspace_bytes, ws.used());
+  hipStream_t s = stream;
+  const size_t cell_bytes = sizeof(int) * (size_t)nc;
+  SCAMD_HIP_CHECK(hipMemcpyAsync(out_reach, b.reach, cell_bytes * nc, hipMemcpyDeviceToDevice, s));
+  SCAMD_HIP_CHECK(hipMemcpyAsync(out_list_len, b.list_len, cell_bytes, hipMemcpyDeviceToDevice, s));
+  SCAMD_HIP_CHECK(hipMemcpyAsync(out_sweep_order, b.sweep_order, cell_bytes * nc, hipMemcpyDeviceToDevice, s));
+  SCAMD_HIP_CHECK(hipMemcpyAsync(out_sweep_lb2, b.sweep_lb2, cell_bytes * nc, hipMemcpyDeviceToDevice, s));
   return SCAMD_OK;
 }
 
