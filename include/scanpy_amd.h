@@ -838,6 +838,38 @@ int scamd_aggregate_median_f32(const int64_t* indptr, const int32_t* indices, co
                                size_t workspace_bytes, scamd_stream_t stream);
 
 /* ------------------------------------------------------------------------------------------
+ * Analytic Pearson residuals (Lause et al. 2021): the device half of scanpy_amd.experimental.pp (reference:
+ * `_calculate_res_sparse` of src/scanpy/experimental/pp/_highly_variable_genes.py, `_pearson_residuals` of _normalization.py;
+ * csrc/pearson.hip).
+ *   mu_ij = (gene_sum[j] / total) * cell_total[i],  r_ij = clip((x_ij - mu_ij) / sqrt(mu_ij + mu_ij^2 * inv_theta), +-clip),
+ * all float64.  inv_theta = 1 / theta >= 0 (0: Poisson), clip >= 0 (infinity: none); SCAMD_EINVAL otherwise.  A NaN (a cell with
+ * total 0) is kept, nothing is special-cased.  All arguments are checked before any launch.
+ * scamd_pp_pearson_gene_var_f32: var_out [g] float64 = the population variance (divisor n_batch) of every gene's residuals, an
+ *   unstored entry counting as x = 0.  Input: the CSC copy of the cells x genes matrix as scamd_csr_transpose_f32 writes it
+ *   (t_indptr int64 [g + 1], t_rows int32, t_data float32; n_rows < 2^31 rows), cell_total float64 [n_rows], the DISTINCT cell
+ *   totals tot_u float64 [n_u] with their multiplicities mult_u float64 [n_u] (sum = n_batch; n_u <= n_batch <= n_rows,
+ *   SCAMD_EINVAL otherwise).  batch_codes (int32 [n_rows], may be NULL) and batch_id keep the stored entries of the rows with that
+ *   code only; gene_sum, total, tot_u, mult_u and n_batch are then that batch's.  A gene with gene_sum 0 gets 0.  Sums over the
+ *   totals: float64 in a fixed order; sums over the stored entries: 128-bit fixed point, so two runs and any order of the rows give
+ *   the same bits; the error bound is stated in csrc/pearson.hip.  Workspace: scamd_pp_pearson_workspace_bytes(g, nnz)
+ *   (SCAMD_EWORKSPACE below it).
+ * scamd_pp_pearson_residuals_f32: out [n x g] row-major, float64 (out_is_f64 != 0) or float32, every cell written once, from the
+ *   canonical CSR matrix (column indices ascending in every row); float64 arithmetic, rounded once on store.
+ * scamd_pp_pearson_limits: the stored entries of one gene per workgroup, the totals per pass of a workgroup, the columns of a
+ *   slice and the rows of a batch of the residual kernel (read-only, no device needed).
+ * ---------------------------------------------------------------------------------------- */
+int scamd_pp_pearson_limits(int32_t* chunk_entries, int32_t* totals_block, int32_t* slice_columns, int32_t* batch_rows);
+size_t scamd_pp_pearson_workspace_bytes(int64_t g, int64_t nnz);
+int scamd_pp_pearson_gene_var_f32(const int64_t* t_indptr, const int32_t* t_rows, const float* t_data, int64_t n_rows, int64_t g,
+                                  int64_t nnz, const double* gene_sum, const double* cell_total, double total, double inv_theta,
+                                  double clip, const double* tot_u, const double* mult_u, int64_t n_u, int64_t n_batch,
+                                  const int32_t* batch_codes /* may be NULL */, int32_t batch_id, double* var_out, void* workspace,
+                                  size_t workspace_bytes, scamd_stream_t stream);
+int scamd_pp_pearson_residuals_f32(const int64_t* indptr, const int32_t* indices, const float* data, int64_t n, int64_t g,
+                                   int64_t nnz, const double* gene_sum, const double* cell_total, double total, double inv_theta,
+                                   double clip, void* out, int out_is_f64, scamd_stream_t stream);
+
+/* ------------------------------------------------------------------------------------------
  * Host-side byte codecs of the on-disk readers (csrc/hostio.cpp).  No device work: callable on a
  * host without a GPU, from many threads at once.  They replace what the reference gets from h5py's bundled filters
  * when it reads `.h5ad` / 10x `.h5` files (src/scanpy/readwrite.py:15-29, 235-243; `compression='lzf'` is one of

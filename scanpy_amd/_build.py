@@ -20,7 +20,7 @@ LIBNAME = "libscanpy_amd.so"
 ARCH = "gfx950"
 
 SOURCES = ["capi.cpp", "hostio.cpp", "knn.hip", "fuzzy.hip", "pca.hip", "gram.hip", "dense.hip", "leiden.hip", "preprocess.hip", "umap.hip", "rank_genes.hip", "harmony.hip", "qc.hip", "regress.hip", "scrublet.hip",
-           "graph_autocorr.hip", "aggregate.hip"]
+           "graph_autocorr.hip", "aggregate.hip", "pearson.hip"]
 CXXFLAGS = ["-O3", "-std=c++17", "-fPIC", f"--offload-arch={ARCH}", "-Wall", "-Wno-unused-function", "-Wno-pass-failed",
             "-ffp-contract=off"]
 

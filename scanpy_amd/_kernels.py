@@ -1099,3 +1099,40 @@ def aggregate(indptr, indices, data, n: int, g: int, codes, order, group_sizes, 
         out["info"] = [int(v) for v in info]
     out["flags"] = int(flags.cpu()[0])
     return out
+
+
+# ---- analytic Pearson residuals (csrc/pearson.hip) ---------------------------------------------------------------------
+def pp_pearson_gene_var(t_indptr, t_rows, t_data, n_rows: int, g: int, gene_sum, cell_total, total: float, inv_theta: float,
+                        clip: float, tot_u, mult_u, n_batch: int, *, batch_codes: torch.Tensor | None = None,
+                        batch_id: int = 0) -> torch.Tensor:
+    """-> float64 [g]: the population variance of every gene's clipped Pearson residuals over the n_batch cells of the batch (all
+    rows without batch_codes).  (t_indptr, t_rows, t_data): the CSC copy `csr_transpose` makes; gene_sum float64 [g], cell_total
+    float64 [n_rows]; tot_u / mult_u float64: the distinct totals of the batch's cells and how often each occurs."""
+    dev = require_gpu()
+    lib = _lib.load()
+    nnz = t_data.numel()
+    for a in (gene_sum, cell_total, tot_u, mult_u):
+        assert a.dtype == torch.float64 and a.is_contiguous()
+    assert gene_sum.numel() == g and cell_total.numel() == n_rows and tot_u.numel() == mult_u.numel()
+    assert batch_codes is None or (batch_codes.dtype == torch.int32 and batch_codes.numel() == n_rows)
+    var = _empty(g, dtype=torch.float64, device=dev)
+    ws, wsz = _ws(lib.scamd_pp_pearson_workspace_bytes(g, nnz), dev)
+    rc = lib.scamd_pp_pearson_gene_var_f32(ptr(t_indptr), ptr(t_rows), ptr(t_data), n_rows, g, nnz, ptr(gene_sum), ptr(cell_total),
+                                           float(total), float(inv_theta), float(clip), ptr(tot_u), ptr(mult_u), tot_u.numel(),
+                                           int(n_batch), ptr(batch_codes), int(batch_id), ptr(var), ptr(ws), wsz, stream_ptr())
+    _check(rc, "scamd_pp_pearson_gene_var_f32")
+    return var
+
+
+def pp_pearson_residuals(indptr, indices, data, n: int, g: int, gene_sum, cell_total, total: float, inv_theta: float, clip: float, *,
+                         out_dtype: torch.dtype = torch.float64) -> torch.Tensor:
+    """-> out [n, g]: the clipped Pearson residual of every cell and gene, float64 arithmetic rounded once to out_dtype"""
+    dev = require_gpu()
+    assert gene_sum.dtype == torch.float64 and cell_total.dtype == torch.float64 and out_dtype in (torch.float32, torch.float64)
+    assert gene_sum.numel() == g and cell_total.numel() == n
+    out = _empty((n, g), dtype=out_dtype, device=dev)
+    rc = _lib.load().scamd_pp_pearson_residuals_f32(ptr(indptr), ptr(indices), ptr(data), n, g, data.numel(), ptr(gene_sum),
+                                                    ptr(cell_total), float(total), float(inv_theta), float(clip), ptr(out),
+                                                    1 if out_dtype == torch.float64 else 0, stream_ptr())
+    _check(rc, "scamd_pp_pearson_residuals_f32")
+    return out

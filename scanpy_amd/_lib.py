@@ -117,6 +117,11 @@ SIGNATURES = {
                                            _vp]),
     "scamd_aggregate_median_f32": (_i32, [_vp, _vp, _vp, _i64, _i64, _i64, _vp, _i64, _vp, _i64, _vp, _vp, _i32, _vp, C.POINTER(_i64),
                                           _vp, _sz, _vp]),
+    "scamd_pp_pearson_limits": (_i32, [C.POINTER(_i32), C.POINTER(_i32), C.POINTER(_i32), C.POINTER(_i32)]),
+    "scamd_pp_pearson_workspace_bytes": (_sz, [_i64, _i64]),
+    "scamd_pp_pearson_gene_var_f32": (_i32, [_vp, _vp, _vp, _i64, _i64, _i64, _vp, _vp, _f64, _f64, _f64, _vp, _vp, _i64, _i64, _vp, _i32,
+                                             _vp, _vp, _sz, _vp]),
+    "scamd_pp_pearson_residuals_f32": (_i32, [_vp, _vp, _vp, _i64, _i64, _i64, _vp, _vp, _f64, _f64, _f64, _vp, _i32, _vp]),
     "scamd_harmony_permutation_workspace_bytes":(_sz, [_i64]),
     "scamd_harmony_permutation_i32": (_i32, [_i64, _u64, _u64, _vp, _vp, _sz, _vp]),
     "scamd_harmony_normalize_f64": (_i32, [_vp, _i64, _i32, _vp, _vp]),

@@ -203,6 +203,56 @@ class GpuPPBackend:
                                       out_dtype=torch.float64 if out_f64 else torch.float32)
         return out.cpu().numpy()
 
+    # ---- analytic Pearson residuals (csrc/pearson.hip; `experimental.pp`) -------------------------------------
+    def row_totals64(self, m: DeviceMatrix) -> np.ndarray:
+        """the sum of every row in float64 (fixed order)"""
+        return self.K.csr_row_stats(m.indptr, m.data, m.n_major)[0].cpu().numpy()
+
+    def _csc_copy(self, m: DeviceMatrix):
+        """the CSC copy of the resident CSR matrix, made once per matrix: on the device up to the 40 944 columns of
+        `scamd_csr_transpose_f32`, beyond that by one pass on the host"""
+        import torch
+
+        if getattr(m, "csc", None) is None:
+            n, g = m.n_major, m.shape[1]
+            if g <= 40944:
+                m.csc = self.K.csr_transpose(m.indptr, m.indices, m.data, n, g)
+            else:
+                t = sparse.csr_matrix((m.data.cpu().numpy(), m.indices.cpu().numpy(), m.indptr.cpu().numpy()), shape=(n, g)).tocsc()
+                m.csc = (torch.from_numpy(t.indptr.astype(np.int64)).to(self.device), torch.from_numpy(t.indices.astype(np.int32)).to(self.device),
+                         torch.from_numpy(t.data).to(self.device))
+        return m.csc
+
+    def pearson_gene_var(self, m: DeviceMatrix, gene_sum: np.ndarray, cell_total: np.ndarray, total: float, *, inv_theta: float,
+                         clip: float, batch_codes=None, batch_id: int = 0, n_batch: int | None = None) -> np.ndarray:
+        """-> float64 [g]: the population variance of every gene's clipped Pearson residuals over the cells with
+        batch_codes == batch_id (all cells without codes); gene_sum and total are that batch's.  The distinct totals of the
+        batch's cells and their multiplicities are found on the device (`torch.unique`, ascending)."""
+        import torch
+
+        n, g = m.n_major, m.shape[1]
+        ct = torch.from_numpy(np.ascontiguousarray(cell_total, dtype=np.float64)).to(self.device)
+        gs = torch.from_numpy(np.ascontiguousarray(gene_sum, dtype=np.float64)).to(self.device)
+        codes = None if batch_codes is None else torch.from_numpy(np.ascontiguousarray(batch_codes, dtype=np.int32)).to(self.device)
+        own = ct if codes is None else ct[codes == int(batch_id)]
+        tot_u, mult_u = torch.unique(own, sorted=True, return_counts=True)
+        t_indptr, t_rows, t_data = self._csc_copy(m)
+        var = self.K.pp_pearson_gene_var(t_indptr, t_rows, t_data, n, g, gs, ct, float(total), float(inv_theta), float(clip),
+                                         tot_u.contiguous(), mult_u.to(torch.float64).contiguous(),
+                                         int(own.numel()) if n_batch is None else int(n_batch), batch_codes=codes, batch_id=int(batch_id))
+        return var.cpu().numpy()
+
+    def pearson_residuals(self, m: DeviceMatrix, gene_sum: np.ndarray, cell_total: np.ndarray, total: float, *, inv_theta: float,
+                          clip: float, out_f64: bool = True) -> np.ndarray:
+        """-> [n, g]: the dense matrix of clipped Pearson residuals, float64 arithmetic rounded once to the output type"""
+        import torch
+
+        ct = torch.from_numpy(np.ascontiguousarray(cell_total, dtype=np.float64)).to(self.device)
+        gs = torch.from_numpy(np.ascontiguousarray(gene_sum, dtype=np.float64)).to(self.device)
+        out = self.K.pp_pearson_residuals(m.indptr, m.indices, m.data, m.n_major, m.shape[1], gs, ct, float(total), float(inv_theta),
+                                          float(clip), out_dtype=torch.float64 if out_f64 else torch.float32)
+        return out.cpu().numpy()
+
     # ---- scrublet (csrc/scrublet.hip; the matrices stay on the device between these calls) --------------------
     def scrublet_simulate(self, m: DeviceMatrix, pairs: np.ndarray, row_total: np.ndarray):
         """Row-pair sums of the resident counts: -> (DeviceMatrix [n_sim, g] of the simulated doublets, total_sim numpy like
