@@ -463,6 +463,24 @@ int scamd_leiden_debug_level_f32(const int64_t* indptr, const int32_t* indices, 
                                  int32_t* refsize, int32_t* cid, int64_t* coarse_indptr, int32_t* coarse_indices,
                                  int64_t* coarse_wq, int64_t* coarse_k, int32_t* coarse_comm, int64_t* info_host,
                                  void* workspace, size_t workspace_bytes, scamd_stream_t stream);
+/* Test entry: the counters of one local-moving sweep on a given partition, by the functions and kernels the run itself uses:
+ * the community totals of `membership` (ids in [0, n), device), the class lists of a sweep with `n_cls` classes (a power of two,
+ * at most 32 for n <= 4096 and 8 beyond) and class hash salt `salt` over the vertices whose word in flags_in (device, [n]) is
+ * not zero -- flags_in == NULL: every vertex -- and one apply step per non-empty class with the caller's decisions (device, [n]:
+ * decision[v] >= 0 the community v moves to, -2 "blocked": v stays and is flagged again, anything else: v stays).
+ * Device outputs, the caller's: lists and tier_lists [n_cls * n] (class c at [c * n ..]: the vertices of the class; the list
+ * positions of its rows of the wave tier upwards from [c * n], of the block tier downwards from [c * n + n - 1]), giant_lists
+ * [n_cls * S], S = nnz / (block_max + 1) + 1 (scamd_leiden_tier_bounds), class c at [c * S ..]; Ktot_before / csize_before [n]:
+ * total vertex weight (strengths in units of 2^-32) and members per community; comm_after, Ktot_after, csize_after,
+ * flags_after [n]: the state after the apply steps.  counts_host [544]: [c] the length of class list c, [32 + 16 c + 8 / 9 /
+ * 10] the rows of its wave / block / giant tier.  info_host [4]: moved, blocked, S, lanes per vertex of the level's main tier.
+ * SCAMD_LEIDEN_COUNT_GRID and SCAMD_LEIDEN_QUAD apply as in a run.  Workspace: scamd_leiden_workspace_bytes. */
+int scamd_leiden_debug_counters_f32(const int64_t* indptr, const int32_t* indices, const float* weights, int64_t n,
+                                    int64_t nnz, const int32_t* membership, const int32_t* flags_in, int n_cls, uint32_t salt,
+                                    const int32_t* decision, int32_t* lists, int32_t* tier_lists, int32_t* giant_lists,
+                                    uint64_t* Ktot_before, int32_t* csize_before, int32_t* comm_after, uint64_t* Ktot_after,
+                                    int32_t* csize_after, int32_t* flags_after, int32_t* counts_host, int64_t* info_host,
+                                    void* workspace, size_t workspace_bytes, scamd_stream_t stream);
 /* Modularity of a given membership (replaces igraph Graph.modularity as used by
  * src/scanpy/metrics/_metrics.py:202-214). */
 int scamd_modularity_csr_f32(const int64_t* indptr, const int32_t* indices, const float* weights,

@@ -625,6 +625,47 @@ def leiden_debug_level(indptr: torch.Tensor, indices: torch.Tensor, weights: tor
     return res
 
 
+LEIDEN_COUNTS_WORDS = 32 + 16 * 32  # counts_host of scamd_leiden_debug_counters_f32: class list lengths, then 16 words per class
+
+
+def leiden_debug_counters(indptr: torch.Tensor, indices: torch.Tensor, weights: torch.Tensor, n: int, membership: torch.Tensor,
+                          decision: torch.Tensor, *, flags: torch.Tensor | None = None, n_cls: int = 8, salt: int = 0) -> dict:
+    """Test entry scamd_leiden_debug_counters_f32: the community totals of `membership`, the class lists of one sweep over the
+    flagged vertices (`flags` None: all) and one apply step per class with `decision` (per vertex: >= 0 move there, -2 blocked)
+    -> dict of device tensors (lists, tier_lists [n_cls, n], giant_lists [n_cls, S], Ktot_before, csize_before, comm_after,
+    Ktot_after, csize_after, flags_after [n]) plus the lists list_len [n_cls], tier_len [n_cls][3] and the integers moved,
+    blocked, giant_stride, lanes."""
+    dev = require_gpu()
+    lib = _lib.load()
+    indptr = indptr.to(torch.int64).contiguous()
+    indices = indices.to(torch.int32).contiguous()
+    weights = weights.to(torch.float32).contiguous()
+    membership = membership.to(device=dev, dtype=torch.int32).contiguous()
+    decision = decision.to(device=dev, dtype=torch.int32).contiguous()
+    given = None if flags is None else flags.to(device=dev, dtype=torch.int32).contiguous()
+    if membership.numel() != n or decision.numel() != n or (given is not None and given.numel() != n):
+        raise ValueError(f"membership / decision / flags must have {n} entries")
+    nnz = weights.numel()
+    stride = nnz // (leiden_tier_bounds(64)[2] + 1) + 1
+    i32 = lambda m: _empty(max(m, 1), dtype=torch.int32, device=dev)  # noqa: E731
+    i64 = lambda m: _empty(max(m, 1), dtype=torch.int64, device=dev)  # noqa: E731
+    out = dict(lists=i32(n_cls * n), tier_lists=i32(n_cls * n), giant_lists=i32(n_cls * stride), Ktot_before=i64(n), csize_before=i32(n),
+               comm_after=i32(n), Ktot_after=i64(n), csize_after=i32(n), flags_after=i32(n))
+    ws, wsz = _ws(lib.scamd_leiden_workspace_bytes(n, nnz), dev)
+    counts = (C.c_int32 * LEIDEN_COUNTS_WORDS)()
+    info = (C.c_int64 * 4)()
+    rc = lib.scamd_leiden_debug_counters_f32(ptr(indptr), ptr(indices), ptr(weights), n, nnz, ptr(membership), ptr(given), int(n_cls),
+                                             int(salt) & 0xFFFFFFFF, ptr(decision), *(ptr(out[key]) for key in out), counts, info,
+                                             ptr(ws), wsz, stream_ptr())
+    _check(rc, "scamd_leiden_debug_counters_f32")
+    res = {key: (val[:n] if key.endswith(("before", "after")) else val.view(n_cls, -1)) for key, val in out.items()}
+    res["list_len"] = [int(v) for v in counts[:n_cls]]
+    res["tier_len"] = [[int(counts[32 + 16 * c + 8 + t]) for t in range(3)] for c in range(n_cls)]
+    res.update(moved=int(info[0]), blocked=int(info[1]), giant_stride=int(info[2]), lanes=int(info[3]))
+    assert res["giant_stride"] == stride
+    return res
+
+
 def modularity(indptr: torch.Tensor, indices: torch.Tensor, weights: torch.Tensor, n: int, membership: torch.Tensor,
                *, resolution: float = 1.0) -> float:
     dev = require_gpu()

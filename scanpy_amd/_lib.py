@@ -78,6 +78,8 @@ SIGNATURES = {
     "scamd_leiden_debug_split_f32": (_i32, [_vp, _vp, _vp, _i64, _i64, _vp, C.POINTER(_i32), _vp, _sz, _vp]),
     "scamd_leiden_debug_level_f32": (_i32, [_vp, _vp, _vp, _i64, _i64, _vp, _vp, _f64, _f64, _u64, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp,
                                             C.POINTER(_i64), _vp, _sz, _vp]),
+    "scamd_leiden_debug_counters_f32": (_i32, [_vp, _vp, _vp, _i64, _i64, _vp, _vp, _i32, C.c_uint32, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp,
+                                               _vp, C.POINTER(_i32), C.POINTER(_i64), _vp, _sz, _vp]),
     "scamd_modularity_csr_f32": (_i32, [_vp, _vp, _vp, _i64, _i64, _vp, _f64, C.POINTER(_f64), _vp, _sz, _vp]),
     "scamd_graph_autocorr_workspace_bytes": (_sz, [_i64, _i64]),
     "scamd_graph_autocorr_part_entries": (_i32, [_i64]),

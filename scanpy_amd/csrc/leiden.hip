@@ -324,8 +324,13 @@ __global__ void ld_copy_membership_kernel(int n, const int* __restrict__ init, i
 // hash table (open addressing, <= 8 probes; a vertex that finds no slot goes to global memory directly) and then
 // issues one global atomic per distinct community it saw.  All reductions are integer (+, min): order free.
 constexpr int BH_SLOTS = 2048;
-constexpr int REDUCE_GRID = 256;  // workgroups of the per-community reductions (one per CU)
 constexpr int BH_EMPTY = -1;
+// Most workgroups that may touch one counter word in a launch, once each ("hot words"): the list
+// builders, the apply kernels and the coarse-id reductions.  Device-scope atomics on one address run one after the other
+// (~85 ns each), so a launch whose every workgroup ends on the same word lasts workgroups x 85 ns whatever it moves.
+// SCAMD_LEIDEN_COUNT_GRID (1 .. COUNT_GRID_MAX) overrides it, so that a test graph of a few thousand vertices has span boundaries.
+constexpr int COUNT_GRID = 128;
+constexpr int COUNT_GRID_MAX = 256;
 
 __device__ __forceinline__ int bh_find_slot(int* keys, int c) {
   unsigned int slot = hash32((unsigned int)c) & (BH_SLOTS - 1);
@@ -351,7 +356,7 @@ __global__ __launch_bounds__(1024) void ld_totals_kernel(const int* __restrict__
     cnt[i] = 0;
   }
   __syncthreads();
-  // (at most REDUCE_GRID workgroups walk the vertices: with a few dozen communities left, every workgroup ends with one
+  // (at most COUNT_GRID workgroups walk the vertices: with a few dozen communities left, every workgroup ends with one
   // global atomic per community on the same few lines -- 977 workgroups at 1M vertices took 85 us, round 5 profile)
   for (int v = blockIdx.x * 1024 + threadIdx.x; v < n; v += gridDim.x * 1024) {
     const int c = comm[v];
@@ -859,20 +864,31 @@ __global__ __launch_bounds__(256) void ld_move_kernel(MoveArgs ma) {
 
 // One thread per active vertex: apply the decided moves in place (integer atomics on the community totals); vertices
 // blocked by the direction rule stay active.  counters: [0] moved, [1] blocked
-__global__ __launch_bounds__(256) void ld_apply_kernel(int n_act, const int* __restrict__ list,
-                                                       const int* __restrict__ decision, const long long* __restrict__ k,
-                                                       int* __restrict__ comm, unsigned long long* __restrict__ Ktot,
-                                                       int* __restrict__ csize, int* __restrict__ flag,
-                                                       int* __restrict__ counters) {
-  __shared__ int s_moved, s_blocked;
-  if (threadIdx.x == 0) {
-    s_moved = 0;
-    s_blocked = 0;
+// At most COUNT_GRID workgroups of 1024 threads walk the list; moved and blocked are counted by ballot per wave, summed in
+// LDS and added ONCE per workgroup (a workgroup per 256 vertices, each ending on counters[PH_MOVED]: 489 workgroups of a
+// level-0 sub-round took 36 us over a few MB).
+constexpr int APPLY_THREADS = 1024;
+// the workgroup's two sums -> counters[PH_MOVED], counters[PH_BLOCKED]; every thread calls it, `moved` / `blocked` are its wave's
+__device__ __forceinline__ void ld_apply_count(int moved, int blocked, int* __restrict__ counters) {
+  __shared__ int s_sum[2];
+  if (threadIdx.x < 2) s_sum[threadIdx.x] = 0;
+  __syncthreads();
+  if ((threadIdx.x & 63) == 0) {
+    if (moved) atomicAdd(&s_sum[0], moved);
+    if (blocked) atomicAdd(&s_sum[1], blocked);
   }
   __syncthreads();
-  const int w = blockIdx.x * blockDim.x + threadIdx.x;
-  if (w < n_act) {
-    const int d = decision[w];
+  if (threadIdx.x < 2 && s_sum[threadIdx.x]) atomicAdd(&counters[threadIdx.x == 0 ? PH_MOVED : PH_BLOCKED], s_sum[threadIdx.x]);
+}
+__global__ __launch_bounds__(APPLY_THREADS) void ld_apply_kernel(int n_act, const int* __restrict__ list,
+                                                                 const int* __restrict__ decision, const long long* __restrict__ k,
+                                                                 int* __restrict__ comm, unsigned long long* __restrict__ Ktot,
+                                                                 int* __restrict__ csize, int* __restrict__ flag,
+                                                                 int* __restrict__ counters) {
+  int moved = 0, blocked = 0;  // of this wave
+  for (int w0 = blockIdx.x * APPLY_THREADS; w0 < n_act; w0 += gridDim.x * APPLY_THREADS) {
+    const int w = w0 + (int)threadIdx.x;
+    const int d = w < n_act ? decision[w] : -1;
     if (d >= 0) {
       const int v = list[w];
       const int a = comm[v];
@@ -882,17 +898,13 @@ __global__ __launch_bounds__(256) void ld_apply_kernel(int n_act, const int* __r
       atomicAdd(&Ktot[a], 0ull - kq);
       atomicAdd(&csize[d], 1);
       atomicSub(&csize[a], 1);
-      atomicAdd(&s_moved, 1);
     } else if (d == -2) {
       flag[list[w]] = 1;
-      atomicAdd(&s_blocked, 1);
     }
+    moved += __popcll(__ballot(d >= 0));
+    blocked += __popcll(__ballot(d == -2));
   }
-  __syncthreads();
-  if (threadIdx.x == 0) {
-    if (s_moved) atomicAdd(&counters[PH_MOVED], s_moved);
-    if (s_blocked) atomicAdd(&counters[PH_BLOCKED], s_blocked);
-  }
+  ld_apply_count(moved, blocked, counters);
 }
 
 // After ALL moves of the sub-round are applied: every mover re-activates its neighbours that are NOT in its new
@@ -984,44 +996,37 @@ __global__ __launch_bounds__(256) void ld_polish_lock_kernel(int n_act, const in
 }
 // winners move (as ld_apply_kernel), losers keep their flag and their decision becomes "stay" (the re-queue that follows
 // reads decision >= 0 as "moved").  counters: [0] moved, [1] lost a lock
-__global__ __launch_bounds__(256) void ld_polish_apply_kernel(int n_act, const int* __restrict__ list, int* __restrict__ decision,
-                                                              const long long* __restrict__ k, int* __restrict__ comm,
-                                                              unsigned long long* __restrict__ Ktot, int* __restrict__ csize,
-                                                              const unsigned long long* __restrict__ lock, unsigned int round,
-                                                              int* __restrict__ flag, int* __restrict__ counters) {
-  __shared__ int s_moved, s_lost;
-  if (threadIdx.x == 0) {
-    s_moved = 0;
-    s_lost = 0;
-  }
-  __syncthreads();
-  const int w = blockIdx.x * blockDim.x + threadIdx.x;
-  if (w < n_act) {
-    const int d = decision[w];
+__global__ __launch_bounds__(APPLY_THREADS) void ld_polish_apply_kernel(int n_act, const int* __restrict__ list, int* __restrict__ decision,
+                                                                        const long long* __restrict__ k, int* __restrict__ comm,
+                                                                        unsigned long long* __restrict__ Ktot, int* __restrict__ csize,
+                                                                        const unsigned long long* __restrict__ lock, unsigned int round,
+                                                                        int* __restrict__ flag, int* __restrict__ counters) {
+  int moved = 0, lost = 0;  // of this wave
+  for (int w0 = blockIdx.x * APPLY_THREADS; w0 < n_act; w0 += gridDim.x * APPLY_THREADS) {
+    const int w = w0 + (int)threadIdx.x;
+    const int d = w < n_act ? decision[w] : -1;
+    bool won = false;
     if (d >= 0) {
       const int v = list[w];
       const int a = comm[v];
       const unsigned long long key = ((unsigned long long)round << 32) | (unsigned long long)(0xffffffffu - (unsigned int)v);
-      if (lock[a] == key && lock[d] == key) {
+      won = lock[a] == key && lock[d] == key;
+      if (won) {
         comm[v] = d;
         const unsigned long long kq = (unsigned long long)k[v];
         atomicAdd(&Ktot[d], kq);
         atomicAdd(&Ktot[a], 0ull - kq);
         atomicAdd(&csize[d], 1);
         atomicSub(&csize[a], 1);
-        atomicAdd(&s_moved, 1);
       } else {
         decision[w] = -1;
         flag[v] = 1;
-        atomicAdd(&s_lost, 1);
       }
     }
+    moved += __popcll(__ballot(won));
+    lost += __popcll(__ballot(d >= 0 && !won));
   }
-  __syncthreads();
-  if (threadIdx.x == 0) {
-    if (s_moved) atomicAdd(&counters[PH_MOVED], s_moved);
-    if (s_lost) atomicAdd(&counters[PH_BLOCKED], s_lost);
-  }
+  ld_apply_count(moved, lost, counters);
 }
 
 // A vertex that leaves may have been the only link between two parts of its community.  After a polish that moved
@@ -1074,7 +1079,7 @@ __device__ __forceinline__ int lm_class(int v, unsigned int salt, int n_cls) {
 
 // flags -> n_cls class lists (lists[c * n ..]), counts in cls_count[0 .. n_cls); clears the flags.  flag == nullptr:
 // every vertex is active (first sweep of a level).  The order inside a list is irrelevant (every decision of a
-// sub-round reads the same snapshot).  One atomic per class and 1024-vertex block.
+// sub-round reads the same snapshot).  One atomic per class and workgroup (ld_build_class_lists).
 // Long rows of a class, listed while its list is built: the tier of a row is known from its length, so the decide step of
 // a sub-round finds the rows of every tier on a list of their own and runs the tiers side by side in one launch (until
 // then the main decide kernel appended them at run time, and the tiers ran one launch behind the other).  The list lengths
@@ -1093,10 +1098,12 @@ __device__ __forceinline__ int long_row_tier(int cls, int v, const TierDst& d) {
   const int deg = (int)(d.indptr[v + 1] - d.indptr[v]);
   return deg > BLK_MAX_DEG ? 3 : (deg > WH_MAX_DEG ? 2 : ((d.thr_mid >= 0 && deg > d.thr_mid) ? 1 : 0));
 }
-// w: the vertex's position in the list of its class.  One atomic per wave, class and tier (coarse levels of unstructured
-// graphs are mostly long rows); waves without long rows -- nearly all of a kNN graph's -- pay three ballots.  Every lane of
-// the wave calls it.
-__device__ __forceinline__ void list_long_rows(int cls, int tier, int w, int n, int lane, int* __restrict__ cls_count, const TierDst& d) {
+// Long rows of one wave's vertices, per tier and class (the same ballots in both passes of ld_build_class_lists; every lane
+// of the wave calls it; waves without long rows -- nearly all of a kNN graph's -- pay three ballots).  tcnt: the workgroup's
+// LDS words per (tier, class).  PLACE = false: count.  PLACE = true: tcnt holds the next free position of the workgroup's
+// range in the tier list; w, the vertex's position in the list of its class, is written there.
+template <bool PLACE>
+__device__ __forceinline__ void list_long_rows(int cls, int tier, int w, int n, int lane, int (*tcnt)[MAX_CLASSES], const TierDst& d) {
   for (int t = 1; t <= 3; ++t) {
     unsigned long long todo = __ballot(tier == t);
     while (todo) {  // (the same for every lane)
@@ -1104,59 +1111,116 @@ __device__ __forceinline__ void list_long_rows(int cls, int tier, int w, int n, 
       const unsigned long long m = __ballot(tier == t && cls == c);
       todo &= ~m;
       int base = 0;
-      if (lane == 0) base = atomicAdd(&cls_count[MAX_CLASSES + CTR_STRIDE * c + (t == 1 ? CTR_N_MID : (t == 2 ? CTR_N_BLK : CTR_N_GIANT))], __popcll(m));
-      base = __shfl(base, 0);
-      if (tier == t && cls == c) {
-        const int pos = base + __popcll(m & ((1ull << lane) - 1ull));
-        if (t == 1) d.lists[(size_t)c * n + pos] = w;
-        else if (t == 2) d.lists[(size_t)c * n + (n - 1 - pos)] = w;
-        else d.giant[(size_t)c * d.giant_stride + pos] = w;
+      if (lane == 0) base = atomicAdd(&tcnt[t - 1][c], __popcll(m));
+      if constexpr (PLACE) {
+        base = __shfl(base, 0);
+        if (tier == t && cls == c) {
+          const int pos = base + __popcll(m & ((1ull << lane) - 1ull));
+          if (t == 1) d.lists[(size_t)c * n + pos] = w;
+          else if (t == 2) d.lists[(size_t)c * n + (n - 1 - pos)] = w;
+          else d.giant[(size_t)c * d.giant_stride + pos] = w;
+        }
       }
     }
+  }
+}
+
+// The list builder of ld_compact_cls_kernel.  cls_of(v, second_pass): the class of vertex v, -1 when it is not listed; both
+// passes must answer the same.  (ld_refine_candidates_kernel keeps its one-pass builder: under this one its per-pass time did
+// not fall -- it waits for its four loads per vertex, not for its counters; profiles/leiden_hot_words_ab.log.)
+// A workgroup owns a contiguous span of whole 1024-vertex chunks, ceil(chunks / gridDim.x) of them (the last spans may be
+// short or empty), and walks it twice; wave i takes vertices [64 i, 64 i + 64) of every chunk.  Pass 1 counts the listed
+// vertices per wave and class (lane c of a wave holds its count for class c) and the span's long rows per (class, tier), and
+// reserves ONE range per word for the whole span: one returning atomic per word and workgroup -- the builders before it did
+// one per class and 1024 vertices and one per wave, class and tier, all on the same few words (977 workgroups at 1M vertices:
+// 81 us for ~20 MB).  The waves' shares of a range follow each other in wave order.  Pass 2 recomputes class, tier and rank
+// and writes the class lists and the tier lists; no barrier in it.  The order inside a list is now span order, not arrival
+// order; nobody observes it.  A wave skips the chunks in which it lists nothing, and pass 2 when it lists nothing at all (late
+// sweeps list a few hundred of a million vertices).
+constexpr int LIST_BATCH = 4;  // chunks whose classes pass 1 asks for before it counts them (loads in flight)
+struct ClassListLds {
+  int wpos[16][MAX_CLASSES];  // wave, class: the wave's count, then the first position of its share of the span's range
+  int tcnt[3][MAX_CLASSES];   // tier, class: the span's long rows, then the next free position of the span's range
+};
+template <typename ClsOf>
+__device__ __forceinline__ void ld_build_class_lists(int n, int* __restrict__ lists, int* __restrict__ cls_count, int n_cls,
+                                                     const TierDst& tiers, ClassListLds& s, ClsOf cls_of) {
+  const int lane = threadIdx.x & 63, wv = threadIdx.x >> 6;
+  const int chunks = (n + 1023) >> 10;
+  const int per = (chunks + (int)gridDim.x - 1) / (int)gridDim.x;
+  const int ch0 = (int)blockIdx.x * per, ch1 = min(chunks, ch0 + per);
+  if (threadIdx.x < 3 * MAX_CLASSES) (&s.tcnt[0][0])[threadIdx.x] = 0;
+  __syncthreads();
+  int mine = 0;  // lane c: the wave's vertices of class c
+  for (int cb = ch0; cb < ch1; cb += LIST_BATCH) {
+    int cl[LIST_BATCH];
+#pragma unroll
+    for (int j = 0; j < LIST_BATCH; ++j) {
+      const int v = (cb + j) * 1024 + (int)threadIdx.x;
+      cl[j] = (cb + j < ch1 && v < n) ? cls_of(v, false) : -1;
+    }
+#pragma unroll
+    for (int j = 0; j < LIST_BATCH; ++j) {
+      const int cls = cl[j];
+      if (!__ballot(cls >= 0)) continue;  // (the same for every lane of the wave)
+      for (int c = 0; c < n_cls; ++c) {
+        const unsigned long long m = __ballot(cls == c);
+        if (lane == c) mine += __popcll(m);
+      }
+      list_long_rows<false>(cls, long_row_tier(cls, (cb + j) * 1024 + (int)threadIdx.x, tiers), 0, n, lane, s.tcnt, tiers);
+    }
+  }
+  if (lane < MAX_CLASSES) s.wpos[wv][lane] = mine;
+  __syncthreads();
+  if ((int)threadIdx.x < n_cls) {
+    const int c = threadIdx.x;
+    int tot = 0;
+    for (int i = 0; i < 16; ++i) tot += s.wpos[i][c];
+    int at = tot ? atomicAdd(&cls_count[c], tot) : 0;
+    for (int i = 0; i < 16; ++i) {
+      const int t = s.wpos[i][c];
+      s.wpos[i][c] = at;
+      at += t;
+    }
+  } else if (threadIdx.x >= 64 && threadIdx.x < 64 + 3 * MAX_CLASSES) {
+    const int t = (threadIdx.x - 64) / MAX_CLASSES, c = (threadIdx.x - 64) % MAX_CLASSES;
+    const int tot = s.tcnt[t][c];
+    if (tot) s.tcnt[t][c] = atomicAdd(&cls_count[MAX_CLASSES + CTR_STRIDE * c + CTR_N_MID + t], tot);
+  }
+  __syncthreads();
+  if (!__ballot(mine != 0)) return;  // (the wave lists nothing; no barrier follows)
+  int pos = lane < MAX_CLASSES ? s.wpos[wv][lane] : 0;  // lane c: where the wave's next vertex of class c goes
+  for (int ch = ch0; ch < ch1; ++ch) {
+    const int v = ch * 1024 + (int)threadIdx.x;
+    const int cls = v < n ? cls_of(v, true) : -1;
+    if (!__ballot(cls >= 0)) continue;
+    int w = 0;
+    for (int c = 0; c < n_cls; ++c) {
+      const unsigned long long m = __ballot(cls == c);
+      const int at = __shfl(pos, c);
+      if (cls == c) w = at + __popcll(m & ((1ull << lane) - 1ull));
+      if (lane == c) pos += __popcll(m);
+    }
+    if (cls >= 0) lists[(size_t)cls * n + w] = v;
+    list_long_rows<true>(cls, long_row_tier(cls, v, tiers), w, n, lane, s.tcnt, tiers);
   }
 }
 
 __global__ __launch_bounds__(1024) void ld_compact_cls_kernel(int n, int* __restrict__ flag, int* __restrict__ lists,
                                                               int* __restrict__ cls_count, int n_cls, unsigned int salt,
                                                               TierDst tiers, int* __restrict__ clear_next, int clear_words) {
-  __shared__ int wcnt[16][MAX_CLASSES];
-  __shared__ int base[MAX_CLASSES];
+  __shared__ ClassListLds s;
   // (the counter block the NEXT sweep will count into: its last users were the sub-rounds of the sweep before this one)
   if (clear_next && blockIdx.x == 0)
     for (int i = threadIdx.x; i < clear_words; i += 1024) clear_next[i] = 0;
-  const int v = blockIdx.x * 1024 + threadIdx.x;
-  const int lane = threadIdx.x & 63, wv = threadIdx.x >> 6;
-  int cls = -1;
-  if (v < n) {
-    int f = 1;
+  // (the flag words are read twice, the second time from L2; the second pass clears them)
+  ld_build_class_lists(n, lists, cls_count, n_cls, tiers, s, [&](int v, bool second_pass) {
     if (flag) {
-      f = flag[v];
-      if (f) flag[v] = 0;
+      if (!flag[v]) return -1;
+      if (second_pass) flag[v] = 0;
     }
-    if (f) cls = lm_class(v, salt, n_cls);
-  }
-  const int tier = long_row_tier(cls, v, tiers);
-  int rank = 0;
-  for (int c = 0; c < n_cls; ++c) {
-    const unsigned long long m = __ballot(cls == c);
-    if (cls == c) rank = __popcll(m & ((1ull << lane) - 1ull));
-    if (lane == 0) wcnt[wv][c] = __popcll(m);
-  }
-  __syncthreads();
-  if ((int)threadIdx.x < n_cls) {
-    const int c = threadIdx.x;
-    int tot = 0;
-    for (int i = 0; i < 16; ++i) {
-      const int t = wcnt[i][c];
-      wcnt[i][c] = tot;
-      tot += t;
-    }
-    base[c] = tot ? atomicAdd(&cls_count[c], tot) : 0;
-  }
-  __syncthreads();
-  const int w = cls >= 0 ? base[cls] + wcnt[wv][cls] + rank : 0;
-  if (cls >= 0) lists[(size_t)cls * n + w] = v;
-  list_long_rows(cls, tier, w, n, lane, cls_count, tiers);
+    return lm_class(v, salt, n_cls);
+  });
 }
 
 // Packed mirrors of the refinement's state (round 4).  Counters of the decision kernels (profiles/r04n_leiden_kernels_pmc*.csv):
@@ -1211,6 +1275,30 @@ __global__ __launch_bounds__(256) void ld_within_kernel(int n, const int64_t* __
   if (sub == 0) a_in[v] = s;
 }
 
+// The long rows of ld_refine_candidates_kernel, which builds its lists in one pass (below):
+// w: the vertex's position in the list of its class.  One atomic per wave, class and tier (coarse levels of unstructured
+// graphs are mostly long rows); waves without long rows -- nearly all of a kNN graph's -- pay three ballots.  Every lane of
+// the wave calls it.
+__device__ __forceinline__ void list_long_rows_per_wave(int cls, int tier, int w, int n, int lane, int* __restrict__ cls_count, const TierDst& d) {
+  for (int t = 1; t <= 3; ++t) {
+    unsigned long long todo = __ballot(tier == t);
+    while (todo) {  // (the same for every lane)
+      const int c = __shfl(cls, __ffsll((long long)todo) - 1);
+      const unsigned long long m = __ballot(tier == t && cls == c);
+      todo &= ~m;
+      int base = 0;
+      if (lane == 0) base = atomicAdd(&cls_count[MAX_CLASSES + CTR_STRIDE * c + (t == 1 ? CTR_N_MID : (t == 2 ? CTR_N_BLK : CTR_N_GIANT))], __popcll(m));
+      base = __shfl(base, 0);
+      if (tier == t && cls == c) {
+        const int pos = base + __popcll(m & ((1ull << lane) - 1ull));
+        if (t == 1) d.lists[(size_t)c * n + pos] = w;
+        else if (t == 2) d.lists[(size_t)c * n + (n - 1 - pos)] = w;
+        else d.giant[(size_t)c * d.giant_stride + pos] = w;
+      }
+    }
+  }
+}
+
 // candidates of the refinement: vertices that are well connected inside their community
 // (w(v, C - v) >= gamma k_v (K_C - k_v) / 2m); all of them start as singletons.  They are written as n_cls class lists
 // (lists[c * n ..], counts in cls_count[0 .. n_cls)): class c is visited in sub-round c of the refinement.
@@ -1249,7 +1337,7 @@ __global__ __launch_bounds__(1024) void ld_refine_candidates_kernel(
   __syncthreads();
   const int w = cls >= 0 ? base[cls] + wcnt[wv][cls] + rank : 0;
   if (cls >= 0) lists[(size_t)cls * n + w] = v;
-  list_long_rows(cls, tier, w, n, lane, cls_count, tiers);
+  list_long_rows_per_wave(cls, tier, w, n, lane, cls_count, tiers);
 }
 
 // Exact incremental update of w(r, C - r) after a round of merges.  For a vertex v that joined t this round
@@ -1650,8 +1738,8 @@ __global__ __launch_bounds__(1024) void ld_coarse_ids_kernel(int n, const int* _
     mn[i] = 0x7fffffff;
   }
   __syncthreads();
-  const int v = blockIdx.x * 1024 + threadIdx.x;
-  if (v < n) {
+  // (at most COUNT_GRID workgroups, as ld_totals_kernel: each ends with one atomicMin per community it saw)
+  for (int v = blockIdx.x * 1024 + threadIdx.x; v < n; v += gridDim.x * 1024) {
     const int c = (int)newid_of_ref[ref[v]];
     cid[v] = c;
     const int cm = comm[v];
@@ -1674,8 +1762,7 @@ __global__ __launch_bounds__(1024) void ld_coarse_rep_kernel(int n, const int* _
     mn[i] = 0x7fffffff;
   }
   __syncthreads();
-  const int v = blockIdx.x * 1024 + threadIdx.x;
-  if (v < n) {
+  for (int v = blockIdx.x * 1024 + threadIdx.x; v < n; v += gridDim.x * 1024) {
     const int c = cid[v];
     const int cm = comm[v];
     const int slot = bh_find_slot(keys, cm);
@@ -2905,6 +2992,7 @@ struct LeidenCtx {
   // (SCAMD_LEIDEN_AGG_WAVE_WORK / _MID_WORK)
   int agg_wave_work = 2048;
   int agg_mid_work = 65536;
+  int count_grid = COUNT_GRID;  // SCAMD_LEIDEN_COUNT_GRID: most workgroups that touch one counter word in a launch (tests: 1, 2)
   int hub_try_probes = HUB_TRY_PROBES;  // 0: no optimistic single pass over multi-pass rows (SCAMD_LEIDEN_HUB_TRY_PROBES; tests)
   int64_t agg_split_chunk = 0, agg_split_work = 0;  // (agg_split_chunk() / agg_split_work(): as the workspace query saw them)
   // rows the last aggregate() handed to the 512-thread builder, the 1024-thread builder, the split path (the debug trace and
@@ -2936,9 +3024,13 @@ static void read_knobs(LeidenCtx& cx) {
   cx.agg_wave_work = std::max(1, env_int("SCAMD_LEIDEN_AGG_WAVE_WORK", 2048));
   cx.agg_mid_work = std::max(1, env_int("SCAMD_LEIDEN_AGG_MID_WORK", 65536));
   cx.hub_try_probes = std::max(0, env_int("SCAMD_LEIDEN_HUB_TRY_PROBES", HUB_TRY_PROBES));
+  cx.count_grid = std::max(1, std::min(env_int("SCAMD_LEIDEN_COUNT_GRID", COUNT_GRID), (int)COUNT_GRID_MAX));
   cx.agg_split_chunk = agg_split_chunk();
   cx.agg_split_work = agg_split_work();
 }
+
+// grid of a launch whose 1024-thread workgroups each end on the same counter words: one per 1024 elements, at most cx.count_grid
+static dim3 count_grid(const LeidenCtx& cx, int cnt) { return dim3((unsigned)std::max(1, std::min(cx.count_grid, ceil_div(cnt, 1024)))); }
 
 // SCAMD_LEIDEN_DEBUG=2: drain the stream after every launch of the class sub-rounds and name it (a device fault then
 // surfaces at the launch that caused it)
@@ -3000,7 +3092,7 @@ static int compute_totals(LeidenCtx& cx, const LevelGraph& g, const int* comm, F
   extra.add(cx.b.Ktot, sizeof(unsigned long long) * g.n).add(cx.b.csize, sizeof(int) * g.n);
   const int rcf = run_fill(cx, extra);
   if (rcf != SCAMD_OK) return rcf;
-  hipLaunchKernelGGL(ld_totals_kernel, dim3((unsigned)std::min(REDUCE_GRID, ceil_div(g.n, 1024))), dim3(1024), 0, cx.s, comm, g.k, g.n, cx.b.Ktot, cx.b.csize,
+  hipLaunchKernelGGL(ld_totals_kernel, count_grid(cx, g.n), dim3(1024), 0, cx.s, comm, g.k, g.n, cx.b.Ktot, cx.b.csize,
                      cx.b.total + 1);
   SCAMD_LAUNCH_CHECK();
   return SCAMD_OK;
@@ -3170,7 +3262,7 @@ static int local_moving(LeidenCtx& cx, const LevelGraph& g, int* total_moves) {
     // [0, MAX_CLASSES): class list lengths of the sweep; then one block per sub-round: hub / overflow counts
     int* sw = b.rcounters + (sweep & 1) * CTR_AREA;
     const unsigned int salt = hash32(cx.seed + 0x85EBCA77u * (unsigned int)(sweep + 1) + 0xC2B2AE3Du * (unsigned int)cx.iter);
-    hipLaunchKernelGGL(ld_compact_cls_kernel, dim3((unsigned)ceil_div(g.n, 1024)), dim3(1024), 0, cx.s, g.n,
+    hipLaunchKernelGGL(ld_compact_cls_kernel, count_grid(cx, g.n), dim3(1024), 0, cx.s, g.n,
                        sweep == 0 ? (int*)nullptr : b.flag, b.cls_lists, sw, n_cls, salt, tier_dst(cx, g, lanes),
                        b.rcounters + ((sweep + 1) & 1) * CTR_AREA, (int)CTR_AREA);
     SCAMD_LAUNCH_CHECK();
@@ -3230,7 +3322,7 @@ static int local_moving(LeidenCtx& cx, const LevelGraph& g, int* total_moves) {
       rc = decide_tiers(cx, "lm move", g, c, lanes, i > 0 ? &prev : nullptr, hc + MAX_CLASSES + CTR_STRIDE * c,
                         MoveArgs{cnt, list, g.indptr, g.indices, g.wq, g.k, b.comm, b.Ktot, b.csize, gg, dir_round, cx.seed, tg, TierLists{}});
       if (rc != SCAMD_OK) return rc;
-      hipLaunchKernelGGL(ld_apply_kernel, GRID1(cnt), 0, cx.s, cnt, list, tg, g.k, b.comm, b.Ktot, b.csize, b.flag,
+      hipLaunchKernelGGL(ld_apply_kernel, count_grid(cx, cnt), dim3(APPLY_THREADS), 0, cx.s, cnt, list, tg, g.k, b.comm, b.Ktot, b.csize, b.flag,
                          b.counters);
       SCAMD_LAUNCH_CHECK();
       prev = RequeueHead{cnt, list, tg};
@@ -3309,7 +3401,7 @@ static int polish_level0(LeidenCtx& cx, const LevelGraph& g, PolishPass* out) {
   bool full = true;  // the next round decides for every vertex (else: for the flagged ones)
   for (;;) {
     int* sw = b.rcounters + (area & 1u) * CTR_AREA;
-    hipLaunchKernelGGL(ld_compact_cls_kernel, dim3((unsigned)ceil_div(g.n, 1024)), dim3(1024), 0, cx.s, g.n,
+    hipLaunchKernelGGL(ld_compact_cls_kernel, count_grid(cx, g.n), dim3(1024), 0, cx.s, g.n,
                        full ? (int*)nullptr : b.flag, b.cls_lists, sw, 1, 0u, tier_dst(cx, g, lanes),
                        b.rcounters + ((area + 1u) & 1u) * CTR_AREA, (int)(MAX_CLASSES + CTR_STRIDE));
     SCAMD_LAUNCH_CHECK();
@@ -3361,7 +3453,7 @@ static int polish_level0(LeidenCtx& cx, const LevelGraph& g, PolishPass* out) {
     if (rc != SCAMD_OK) return rc;
     hipLaunchKernelGGL(ld_polish_lock_kernel, GRID1(cnt), 0, cx.s, cnt, list, (const int*)b.target, (const int*)b.comm, lock, round);
     SCAMD_LAUNCH_CHECK();
-    hipLaunchKernelGGL(ld_polish_apply_kernel, GRID1(cnt), 0, cx.s, cnt, list, b.target, g.k, b.comm, b.Ktot, b.csize,
+    hipLaunchKernelGGL(ld_polish_apply_kernel, count_grid(cx, cnt), dim3(APPLY_THREADS), 0, cx.s, cnt, list, b.target, g.k, b.comm, b.Ktot, b.csize,
                        (const unsigned long long*)lock, round, b.flag, b.counters);
     SCAMD_LAUNCH_CHECK();
     hipLaunchKernelGGL(ld_requeue_kernel, GRID1(cnt), 0, cx.s, cnt, list, (const int*)b.target, g.indptr, g.indices,
@@ -3495,7 +3587,7 @@ static int aggregate(LeidenCtx& cx, const LevelGraph& g, int n_orig, int level, 
   rc = place_level(cx, g, level, (int)nn, &sl);
   if (rc != SCAMD_OK) return rc;
   int* cid = const_cast<int*>(sl.cid);
-  hipLaunchKernelGGL(ld_coarse_ids_kernel, GRIDK(g.n), 0, cx.s, g.n, b.ref, b.newid, b.comm, cid, b.rep);
+  hipLaunchKernelGGL(ld_coarse_ids_kernel, count_grid(cx, g.n), dim3(1024), 0, cx.s, g.n, b.ref, b.newid, b.comm, cid, b.rep);
   SCAMD_LAUNCH_CHECK();
   // (+ the cursors of the member scatter and the phase counters cleared: two memsets until round 6)
   hipLaunchKernelGGL(ld_coarse_comm_kernel, GRID1(g.n), 0, cx.s, g.n, cid, b.comm, b.rep, b.comm_tmp, (int)nn, b.cursor, b.counters);
@@ -3616,7 +3708,7 @@ static int reuse_level(LeidenCtx& cx, const LevelGraph& g, int n_orig, int level
   }
   int rc = run_fill(cx, Filler().add(b.rep, sizeof(int) * (size_t)g.n, 0x7f7f7f7fu));
   if (rc != SCAMD_OK) return rc;
-  hipLaunchKernelGGL(ld_coarse_rep_kernel, GRIDK(g.n), 0, cx.s, g.n, sl.cid, (const int*)b.comm, b.rep);
+  hipLaunchKernelGGL(ld_coarse_rep_kernel, count_grid(cx, g.n), dim3(1024), 0, cx.s, g.n, sl.cid, (const int*)b.comm, b.rep);
   SCAMD_LAUNCH_CHECK();
   hipLaunchKernelGGL(ld_coarse_comm_kernel, GRID1(g.n), 0, cx.s, g.n, sl.cid, (const int*)b.comm, (const int*)b.rep, b.comm_tmp, nn, b.cursor, b.counters);
   SCAMD_LAUNCH_CHECK();
@@ -3777,7 +3869,7 @@ static int renumber(LeidenCtx& cx, int n, int* n_comm, int* out) {
     const int rcf = run_fill(cx, Filler().add(b.minmember, sizeof(int) * n, 0x7f7f7f7fu).add(b.csize, sizeof(int) * n));
     if (rcf != SCAMD_OK) return rcf;
   }
-  hipLaunchKernelGGL(ld_minmember_kernel, dim3((unsigned)std::min(REDUCE_GRID, ceil_div(n, 1024))), dim3(1024), 0, cx.s, n, b.memb, b.minmember, b.csize);
+  hipLaunchKernelGGL(ld_minmember_kernel, count_grid(cx, n), dim3(1024), 0, cx.s, n, b.memb, b.minmember, b.csize);
   SCAMD_LAUNCH_CHECK();
   hipLaunchKernelGGL(ld_flag_kernel, GRID1(n), 0, cx.s, n, b.csize, b.flag, (int*)nullptr);
   SCAMD_LAUNCH_CHECK();
@@ -4175,7 +4267,7 @@ extern "C" int scamd_leiden_debug_level_f32(const int64_t* indptr, const int32_t
   if (refined_in) {
     rc = run_fill(cx, Filler().add(b.Kref, sizeof(unsigned long long) * n).add(b.Eref, sizeof(unsigned long long) * n).add(b.refsize, sizeof(int) * n));
     if (rc != SCAMD_OK) return rc;
-    hipLaunchKernelGGL(ld_totals_kernel, dim3((unsigned)std::min(REDUCE_GRID, ceil_div(in, 1024))), dim3(1024), 0, cx.s, (const int*)b.ref,
+    hipLaunchKernelGGL(ld_totals_kernel, count_grid(cx, in), dim3(1024), 0, cx.s, (const int*)b.ref,
                        g0.k, in, b.Kref, b.refsize, (unsigned long long*)nullptr);
     SCAMD_LAUNCH_CHECK();
   } else {
@@ -4214,6 +4306,77 @@ extern "C" int scamd_leiden_debug_level_f32(const int64_t* indptr, const int32_t
   info_host[5] = skipped ? 0 : cx.agg_rows_split;
   info_host[6] = skipped ? 1 : 0;
   info_host[7] = 0;
+  return SCAMD_OK;
+}
+
+// Test entry: the counters of one local-moving sub-round structure on a GIVEN partition, by the functions and kernels the run
+// itself uses -- compute_totals, the class-list builder of a sweep (ld_compact_cls_kernel; flags_in == NULL: every vertex is
+// listed, as in the first sweep of a level) and ld_apply_kernel once per non-empty class, with the caller's decisions
+// (decision[v]: >= 0 the community v moves to, -2 blocked, anything else stays) gathered to list positions.
+extern "C" int scamd_leiden_debug_counters_f32(const int64_t* indptr, const int32_t* indices, const float* weights, int64_t n,
+                                               int64_t nnz, const int32_t* membership, const int32_t* flags_in, int n_cls,
+                                               uint32_t salt, const int32_t* decision, int32_t* lists, int32_t* tier_lists,
+                                               int32_t* giant_lists, uint64_t* Ktot_before, int32_t* csize_before,
+                                               int32_t* comm_after, uint64_t* Ktot_after, int32_t* csize_after, int32_t* flags_after,
+                                               int32_t* counts_host, int64_t* info_host, void* workspace, size_t workspace_bytes,
+                                               scamd_stream_t stream) {
+  SCAMD_REQUIRE(membership && decision && lists && tier_lists && giant_lists && Ktot_before && csize_before && comm_after && Ktot_after &&
+                    csize_after && flags_after && counts_host && info_host,
+                SCAMD_EINVAL, "leiden counters: null pointer");
+  // (the workspace holds MAX_CLASSES lists for levels of at most 4096 vertices, DEF_CLASSES beyond: leiden_carve, rf_classes)
+  const int most_cls = n <= 4096 ? MAX_CLASSES : DEF_CLASSES;
+  SCAMD_REQUIRE(n_cls >= 1 && n_cls <= most_cls && (n_cls & (n_cls - 1)) == 0, SCAMD_EINVAL,
+                "leiden counters: n_cls %d (a power of two up to %d at n = %lld)", n_cls, most_cls, (long long)n);
+  LeidenCtx cx;
+  set_rule(cx, 1.0, 0.01, 0);
+  LevelGraph g;
+  int rc = leiden_open(cx, "leiden counters", indptr, indices, weights, n, nnz, workspace, workspace_bytes, stream, &g);
+  if (rc != SCAMD_OK) return rc;
+  LeidenBuffers& b = cx.b;
+  const int in = (int)n;
+  hipLaunchKernelGGL(ld_copy_membership_kernel, GRID1(n), 0, cx.s, in, membership, b.comm, b.counters + PHASE_ERR);
+  SCAMD_LAUNCH_CHECK();
+  int bad = 0;
+  LD_FETCH(&bad, b.counters + PHASE_ERR, sizeof(int), cx.s);
+  LD_SYNC(cx.s);
+  SCAMD_REQUIRE(bad == 0, SCAMD_EINVAL, "leiden counters: ids must lie in [0, n)");
+  rc = compute_totals(cx, g, b.comm, Filler().add(b.flag, sizeof(int) * n).add(b.counters, sizeof(int) * PH_PER_PHASE).add(b.rcounters, sizeof(int) * CTR_AREA));
+  if (rc != SCAMD_OK) return rc;
+  SCAMD_HIP_CHECK(hipMemcpyAsync(Ktot_before, b.Ktot, sizeof(unsigned long long) * n, hipMemcpyDeviceToDevice, cx.s));
+  SCAMD_HIP_CHECK(hipMemcpyAsync(csize_before, b.csize, sizeof(int) * n, hipMemcpyDeviceToDevice, cx.s));
+  if (flags_in) SCAMD_HIP_CHECK(hipMemcpyAsync(b.flag, flags_in, sizeof(int) * n, hipMemcpyDeviceToDevice, cx.s));
+  const int lanes = level_lanes(cx, g);
+  hipLaunchKernelGGL(ld_compact_cls_kernel, count_grid(cx, g.n), dim3(1024), 0, cx.s, g.n, flags_in ? b.flag : (int*)nullptr, b.cls_lists,
+                     b.rcounters, n_cls, (unsigned int)salt, tier_dst(cx, g, lanes), b.rcounters + CTR_AREA, (int)CTR_AREA);
+  SCAMD_LAUNCH_CHECK();
+  LD_FETCH(counts_host, b.rcounters, sizeof(int) * CTR_AREA, cx.s);
+  LD_SYNC(cx.s);
+  const size_t gs = (size_t)giant_stride(g);
+  SCAMD_HIP_CHECK(hipMemcpyAsync(lists, b.cls_lists, sizeof(int) * n * n_cls, hipMemcpyDeviceToDevice, cx.s));
+  SCAMD_HIP_CHECK(hipMemcpyAsync(tier_lists, b.tier_lists, sizeof(int) * n * n_cls, hipMemcpyDeviceToDevice, cx.s));
+  SCAMD_HIP_CHECK(hipMemcpyAsync(giant_lists, b.giant_lists, sizeof(int) * gs * n_cls, hipMemcpyDeviceToDevice, cx.s));
+  for (int c = 0; c < n_cls; ++c) {
+    const int cnt = counts_host[c];
+    SCAMD_REQUIRE(cnt >= 0 && cnt <= in, SCAMD_EINTERNAL, "leiden counters: class %d lists %d of %d vertices", c, cnt, in);
+    if (cnt == 0) continue;
+    const int* list = b.cls_lists + (size_t)c * n;
+    hipLaunchKernelGGL(ld_gather_kernel, GRID1(cnt), 0, cx.s, cnt, decision, list, b.target);
+    SCAMD_LAUNCH_CHECK();
+    hipLaunchKernelGGL(ld_apply_kernel, count_grid(cx, cnt), dim3(APPLY_THREADS), 0, cx.s, cnt, list, (const int*)b.target, g.k, b.comm,
+                       b.Ktot, b.csize, b.flag, b.counters);
+    SCAMD_LAUNCH_CHECK();
+  }
+  int ph[PH_PER_PHASE];
+  LD_FETCH(ph, b.counters, sizeof(ph), cx.s);
+  SCAMD_HIP_CHECK(hipMemcpyAsync(comm_after, b.comm, sizeof(int) * n, hipMemcpyDeviceToDevice, cx.s));
+  SCAMD_HIP_CHECK(hipMemcpyAsync(Ktot_after, b.Ktot, sizeof(unsigned long long) * n, hipMemcpyDeviceToDevice, cx.s));
+  SCAMD_HIP_CHECK(hipMemcpyAsync(csize_after, b.csize, sizeof(int) * n, hipMemcpyDeviceToDevice, cx.s));
+  SCAMD_HIP_CHECK(hipMemcpyAsync(flags_after, b.flag, sizeof(int) * n, hipMemcpyDeviceToDevice, cx.s));
+  LD_SYNC(cx.s);
+  info_host[0] = ph[PH_MOVED];
+  info_host[1] = ph[PH_BLOCKED];
+  info_host[2] = (int64_t)gs;
+  info_host[3] = lanes;
   return SCAMD_OK;
 }
 
